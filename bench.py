@@ -22,7 +22,11 @@ forward last touched half a rotation ago: otherwise the part's 256 MB Infinity C
 "HBM" fraction is not one (DESIGN_HISTORY.md section 7).  `--buffers 1` re-uses one set.
 
 Rank 0 prints ONE JSON line; `value` is the whole-job aggregate: (elements of all ranks * K) / time,
-time = max over ranks of the K-step wall time bracketed by barrier + synchronize.
+time = max over ranks of the K-step wall time bracketed by barrier + synchronize; `ms_per_step` is that time / K.
+
+`--dump-outputs DIR` writes what the headline's last timed step returned -- y, dx, d_scale, d_shift -- as DIR/<name>.npy (float32;
+float64 storage: float64), at most 64 MB in all: outputs too large for that are sampled at fixed, seeded positions.  The
+inputs are seeded (torchlsq.synth), so two builds run with the same arguments can be compared output for output.
 
 Extra objects on the same line:
   roofline      HBM roofline of the dominant kernel (the fused backward: read grad + read x + write dx = 3 storage
@@ -137,6 +141,10 @@ def parse_args(argv=None):
                          "told it has a peer (the `cfg4_shard_collective` record of the default run as a workload of its own: for profilers)")
     ap.add_argument("--variant-fwd", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--variant-bwd", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's LAST timed step returned (y, dx, d_scale, d_shift) as "
+                         "DIR/<name>.npy in float32 (float64 storage: float64), at most 64 MB in all: larger outputs are sampled at "
+                         "fixed, seeded positions (the same positions for every output of one size).  Rank 0 only at N > 1")
     return ap.parse_args(argv)
 
 
@@ -267,6 +275,79 @@ def measure_traffic(a, kernel_substr):
             "dispatches_averaged": raw["FETCH_SIZE"][1], "kernel": raw["FETCH_SIZE"][2][:120],
             "formula": "(2 * FETCH_SIZE + WRITE_SIZE) * 1024"}
     return int(round((2.0 * fetch_kib + write_kib) * 1024.0)), info
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000     # --dump-outputs: all files together
+DUMP_WHOLE_MAX = 1 << 16        # outputs of at most this many elements are written whole even when others are sampled
+DUMP_SEED = 20240917
+
+
+def named_outputs(y, r, reduced=None):
+    """{name: tensor} of what one step hands its caller: the forward's y and the backward's (dx, d_scale, d_shift) -- or, for
+    the forms that return them differently, dx and the [d_scale, d_shift] sums (`reduced`: the fp64 sums of the last
+    all-reduce when the backward itself returned dx alone).  Lists (the multi-tensor ops) get an index suffix."""
+    import torch
+    out = {}
+
+    def put(name, t):
+        if isinstance(t, (list, tuple)):
+            for i, u in enumerate(t):
+                put("%s_%d" % (name, i), u)
+        elif isinstance(t, torch.Tensor):
+            out[name] = t
+
+    put("y", y)
+    if isinstance(r, (list, tuple)) and len(r) == 3:
+        for name, t in zip(("dx", "d_scale", "d_shift"), r):
+            put(name, t)
+    elif isinstance(r, (list, tuple)) and len(r) == 2:
+        put("dx", r[0])
+        put("d_scale_d_shift", r[1])
+    else:
+        put("dx", r)
+        if reduced is not None:
+            if reduced[0] == "wide":
+                put("d_scale_d_shift", reduced[1])
+            else:
+                put("d_scale", reduced[1])
+                put("d_shift", reduced[2])
+    return out
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy: float64 storage as float64, everything else as float32 (exact for the 16-bit
+    types).  When the whole set would exceed `limit` bytes, every output of more than DUMP_WHOLE_MAX elements is reduced to the
+    same share of the remaining budget, at sorted positions drawn from a fixed seed (so the samples of two outputs of one size
+    -- y and dx -- sit at the same elements, and two runs sample the same elements).  Returns {name: description}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {k: v.detach().reshape(-1) for k, v in outputs.items()}
+    isz = {k: 8 if v.dtype == torch.float64 else 4 for k, v in flat.items()}
+    header = 128                                                   # np.save's header, per file
+    need = sum(v.numel() * isz[k] + header for k, v in flat.items())
+    large = [k for k, v in flat.items() if need > limit and v.numel() > DUMP_WHOLE_MAX]
+    keep = None
+    if large:
+        fixed = sum(flat[k].numel() * isz[k] + header for k in flat if k not in large) + header * len(large)
+        keep = (limit - fixed) // sum(isz[k] for k in large)
+        if keep < 1:
+            raise SystemExit("--dump-outputs: %d outputs do not fit %d bytes" % (len(flat), limit))
+    picks, info = {}, {}
+    for k, v in flat.items():
+        if k in large and v.numel() > keep:
+            n = v.numel()
+            if n not in picks:
+                idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=keep, dtype=np.int64))
+                picks[n] = (idx, torch.from_numpy(idx).to(v.device))
+            v = v.index_select(0, picks[n][1])
+            info[k] = {"shape": list(outputs[k].shape), "sampled": int(v.numel()), "of": n}
+        else:
+            v = v.view(outputs[k].shape)
+            info[k] = {"shape": list(outputs[k].shape)}
+        a = v.to(torch.float64 if isz[k] == 8 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return info
 
 
 def carried_traffic(workload, n_local):
@@ -530,7 +611,7 @@ def run_rank(a):
         return {"collective_verified": col, "parity_vs_reference": par}
 
     def measure(workload, steps, warmup, graph=False, buffers=0, ops=ops, warm_ms=0.0, extra_blocks=0, shard_of=0, multi=0,
-                collective=None, inputs=None, shape_override=None, event_every=0):
+                collective=None, inputs=None, shape_override=None, event_every=0, keep_outputs=False):
         """Time `steps` steps (forward op + backward op) of one workload after `warmup` untimed ones; returns the raw
         measurements (K-step wall time bracketed by barrier + synchronize, max over ranks; per-op HIP-event times).
         shard_of = R (single rank only): the step ONE rank of an R-rank job runs on this shape -- the `*_wide` backward with
@@ -539,7 +620,8 @@ def run_rank(a):
         collective = "native" | "c10d" (single rank, with shard_of): the N > 1 step itself -- sharded_backward(async_op=True) and
         its drain -- with the process group told it has peers (torchlsq.distributed.assume_peers), over the named route.
         inputs = (xs, gs, scale, shift) of an earlier measure() of the same workload: run on those very buffers.
-        shape_override: another shape for the same workload's operator (the host-cost probe on a tiny tensor)."""
+        shape_override: another shape for the same workload's operator (the host-cost probe on a tiny tensor).
+        keep_outputs: return what the last timed step handed back (`outputs`, see named_outputs) for --dump-outputs."""
         cfg_name, dtype_name, axis_override = WORKLOADS[workload]
         c = dict(synth.CONFIGS[cfg_name])
         if axis_override is not None:
@@ -813,6 +895,7 @@ def run_rank(a):
             dist.barrier()
             torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        last = (y, r) if keep_outputs else None        # the last timed step's outputs (a graph's: its last step, as replayed)
         if step_graphs is not None:
             for i, e in enumerate(ev):
                 if e is not None:
@@ -836,6 +919,8 @@ def run_rank(a):
                 torch.cuda.synchronize()
                 block_times.append(time.perf_counter() - tb)
             elapsed = sorted(block_times)[len(block_times) // 2]
+            if keep_outputs:
+                last = (y, r)
 
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if world > 1:
@@ -875,7 +960,8 @@ def run_rank(a):
                     scaling=scaling, n_local=n_local, n_global=n_global, n_sets=n_sets, set_bytes=set_bytes, steps=steps,
                     warmup=warmup, elapsed_max=elapsed_max, fwd_ms=fwd_ms, bwd_ms=bwd_ms, fwd_avg=fwd_avg, bwd_avg=bwd_avg,
                     xs=xs, gs=gs, x=x, scale=scale, shift=shift, solo_ms=solo_ms, block_times=block_times, graph=bool(graph),
-                    graph_steps=graph_steps, collective_route=route)
+                    graph_steps=graph_steps, collective_route=route,
+                    outputs=named_outputs(last[0], last[1], last_reduced[0]) if last is not None else None)
 
     # the non-headline workloads are small (20-100 us per step): W warm-up steps are over before the GPU's clocks have come up,
     # so they warm up for at least 60 ms of wall time (the headline workload, cfg2, does exactly its W steps)
@@ -891,7 +977,12 @@ def run_rank(a):
         native_preflight()
         if a.assume_peers:
             head_kw["collective"] = a.collective
-    m = measure(a.workload, a.steps, a.warmup, a.graph, a.buffers, warm_ms=warm_floor_ms, extra_blocks=extra_blocks, **head_kw)
+    m = measure(a.workload, a.steps, a.warmup, a.graph, a.buffers, warm_ms=warm_floor_ms, extra_blocks=extra_blocks,
+                keep_outputs=bool(a.dump_outputs), **head_kw)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(m["outputs"], a.dump_outputs)
+    m["outputs"] = None
     c, dtype_name, esz, per_channel, shape, axis = m["c"], m["dtype_name"], m["esz"], m["per_channel"], m["shape"], m["axis"]
     scaling, n_local, n_global, n_sets, set_bytes = m["scaling"], m["n_local"], m["n_global"], m["n_sets"], m["set_bytes"]
     elapsed_max, fwd_ms, bwd_ms, fwd_avg, bwd_avg = m["elapsed_max"], m["fwd_ms"], m["bwd_ms"], m["fwd_avg"], m["bwd_avg"]
@@ -974,6 +1065,8 @@ def run_rank(a):
                          "step_reads_only_achieved": round(step_gbs * 0.6, 1),
                          "step_reads_only_frac": round(step_gbs * 0.6 / HBM_PEAK_GBS, 4)},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": a.dump_outputs, "files": dumped}
         if world > 1 or a.assume_peers:
             line["config"]["collective"] = m["collective_route"] + (" (" + a.collective + ")" if a.assume_peers else "")
             if preflight:

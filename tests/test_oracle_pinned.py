@@ -1,8 +1,8 @@
 """CPU: pin the oracle (oracle/lsq_oracle.c) against the reference.
 
   * golden vectors produced by the reference's real CPU op library (tests/golden/make_golden.py);
-  * the reference's own scalar header compiled from /root/reference (oracle/_ref/liblsq_ref_scalar.so),
-    when that build is present (build container; it also travels to the GPU box).
+  * the reference's own scalar header (oracle/_ref/liblsq_ref_scalar.so, built by oracle/build_ref.py): its outputs pinned
+    as digests under tests/golden/, and the build itself where it is present.
 """
 import ctypes
 import os
@@ -105,67 +105,101 @@ def test_oracle_matches_reference_config_digests(config_digests, name):
     assert_reduction_close(r.db_wide, d["db"], d["oracle_abs_db"], name + " db")
 
 
-# ---- against the reference's scalar header, compiled where it lies -----------------------------
+# ---- against the reference's scalar header ------------------------------------------------------
+# Its outputs on the inputs below are pinned as sha256 digests (tests/golden/ref_scalar_digests.json, written by
+# tests/golden/make_ref_pinned.py from oracle/_ref/liblsq_ref_scalar.so); where that build is present the oracle is also held
+# to it live.
 _REF_SCALAR = os.path.join(ROOT, "oracle", "_ref", "liblsq_ref_scalar.so")
+_PT_TRIALS = [(0, 127, 0, 255, 0, 0, 0, 0.03, 0.1), (-64, 63, -128, 127, 1, 0, 0, 0.02, -0.0), (0, 255, 0, 255, 0, 1, 0, 0.05, -0.7),
+              (-8, 7, -128, 127, 0, 0, 1, 0.3, 0.2), (0, 15, -128, 127, 0, 0, 0, 1e-12, 0.0), (-128, 127, -128, 127, 1, 1, 0, -0.01, 0.0)]
 
 
-@pytest.mark.skipif(not os.path.isfile(_REF_SCALAR), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_oracle_bitwise_vs_reference_scalar_header(dtype):
-    ref = ctypes.CDLL(_REF_SCALAR)
-    suf = "f32" if dtype == np.float32 else "f64"
-    cT = ctypes.c_float if dtype == np.float32 else ctypes.c_double
-    vp = ctypes.c_void_p
+def scalar_header_inputs(dtype):
+    """the seeded inputs of the comparison: six per-tensor trials of 200 003 elements, then one per-channel walk"""
     rng = np.random.default_rng(7)
     n = 200_003
-    eps = np.finfo(dtype).eps
-    for trial, (qmin, qmax, tmin, tmax, sym, init, evalm, scale0, shift0) in enumerate([
-            (0, 127, 0, 255, 0, 0, 0, 0.03, 0.1), (-64, 63, -128, 127, 1, 0, 0, 0.02, -0.0), (0, 255, 0, 255, 0, 1, 0, 0.05, -0.7),
-            (-8, 7, -128, 127, 0, 0, 1, 0.3, 0.2), (0, 15, -128, 127, 0, 0, 0, 1e-12, 0.0), (-128, 127, -128, 127, 1, 1, 0, -0.01, 0.0)]):
+    trials = []
+    for params in _PT_TRIALS:
         x = (rng.standard_normal(n) * 2 + 0.5).astype(dtype)
         x[:7] = [np.nan, np.inf, -np.inf, 0.0, -0.0, np.finfo(dtype).tiny / 2, 1e30]
         g = rng.standard_normal(n).astype(dtype)
-        s = dtype(max(abs(dtype(scale0)), eps))
-        inv_s = dtype(1) / s
-        gs = dtype(O.grad_scaler_pt(n, qmax, True, 1.0, dtype=dtype))
-        # forward
-        y_ref = np.empty_like(x)
-        f = getattr(ref, "ref_fwd_pt_" + suf)
-        f.argtypes = [vp, vp, ctypes.c_int64] + [cT] * 7 + [ctypes.c_int]
-        f(x.ctypes.data, y_ref.ctypes.data, n, s, inv_s, dtype(shift0), qmin, qmax, tmin, tmax, init)
-        assert_bits_equal(O.fwd_pt(x, scale0, shift0, qmin, qmax, tmin, tmax, init), y_ref, "fwd trial %d" % trial)
-        # backward incl. the per-element ds/db buffers the reference materialises
-        dx_ref, dsb, dbb = np.empty_like(x), np.empty_like(x), np.empty_like(x)
-        f = getattr(ref, "ref_bwd_pt_" + suf)
-        f.argtypes = [vp] * 5 + [ctypes.c_int64] + [cT] * 8 + [ctypes.c_int] * 3
-        f(g.ctypes.data, x.ctypes.data, dx_ref.ctypes.data, dsb.ctypes.data, dbb.ctypes.data, n, s, inv_s, dtype(shift0),
-          qmin, qmax, tmin, tmax, gs, sym, evalm, init)
-        r = O.bwd_pt(g, x, scale0, shift0, qmin, qmax, tmin, tmax, True, 1.0, sym, evalm, init, want_buffers=True)
-        assert_bits_equal(r.dx, dx_ref, "dx trial %d" % trial)
-        assert_bits_equal(r.ds_buf, dsb, "ds_buffer trial %d" % trial)
-        assert_bits_equal(r.db_buf, dbb, "db_buffer trial %d" % trial)
-    # per-channel walk
+        trials.append((params, x, g))
     outer, C, inner = 5, 37, 11
     x = rng.standard_normal(outer * C * inner).astype(dtype)
     g = rng.standard_normal(x.size).astype(dtype)
     sc = rng.uniform(-0.1, 0.1, C).astype(dtype)
     sc[3] = 0
     sh = rng.standard_normal(C).astype(dtype) * dtype(0.05)
+    return trials, (outer, C, inner, x, g, sc, sh)
+
+
+def oracle_scalar_outputs(dtype):
+    """{label: array} of the oracle on scalar_header_inputs(dtype)"""
+    trials, (outer, C, inner, x, g, sc, sh) = scalar_header_inputs(dtype)
+    out = {}
+    for trial, ((qmin, qmax, tmin, tmax, sym, init, evalm, scale0, shift0), xt, gt) in enumerate(trials):
+        out["fwd trial %d" % trial] = O.fwd_pt(xt, scale0, shift0, qmin, qmax, tmin, tmax, init)
+        r = O.bwd_pt(gt, xt, scale0, shift0, qmin, qmax, tmin, tmax, True, 1.0, sym, evalm, init, want_buffers=True)
+        out["dx trial %d" % trial], out["ds_buffer trial %d" % trial], out["db_buffer trial %d" % trial] = r.dx, r.ds_buf, r.db_buf
+    out["fwd_pc"] = O.fwd_pc(x, sc, sh, outer, C, inner, -8, 7, -128, 127)
+    r = O.bwd_pc(g, x, sc, sh, outer, C, inner, -8, 7, -128, 127, True, 1.0, False, want_buffers=True)
+    out["dx_pc"], out["ds_buffer_pc"], out["db_buffer_pc"] = r.dx, r.ds_buf, r.db_buf
+    return out
+
+
+def ref_scalar_outputs(ref, dtype):
+    """{label: array} of the reference's scalar header (the loaded oracle/_ref/liblsq_ref_scalar.so) on the same inputs"""
+    suf = "f32" if dtype == np.float32 else "f64"
+    cT = ctypes.c_float if dtype == np.float32 else ctypes.c_double
+    vp = ctypes.c_void_p
+    eps = np.finfo(dtype).eps
+    trials, (outer, C, inner, x, g, sc, sh) = scalar_header_inputs(dtype)
+    out = {}
+    for trial, ((qmin, qmax, tmin, tmax, sym, init, evalm, scale0, shift0), xt, gt) in enumerate(trials):
+        n = xt.size
+        s = dtype(max(abs(dtype(scale0)), eps))
+        inv_s = dtype(1) / s
+        gs = dtype(O.grad_scaler_pt(n, qmax, True, 1.0, dtype=dtype))
+        y_ref = np.empty_like(xt)
+        f = getattr(ref, "ref_fwd_pt_" + suf)
+        f.argtypes = [vp, vp, ctypes.c_int64] + [cT] * 7 + [ctypes.c_int]
+        f(xt.ctypes.data, y_ref.ctypes.data, n, s, inv_s, dtype(shift0), qmin, qmax, tmin, tmax, init)
+        # backward incl. the per-element ds/db buffers the reference materialises
+        dx_ref, dsb, dbb = np.empty_like(xt), np.empty_like(xt), np.empty_like(xt)
+        f = getattr(ref, "ref_bwd_pt_" + suf)
+        f.argtypes = [vp] * 5 + [ctypes.c_int64] + [cT] * 8 + [ctypes.c_int] * 3
+        f(gt.ctypes.data, xt.ctypes.data, dx_ref.ctypes.data, dsb.ctypes.data, dbb.ctypes.data, n, s, inv_s, dtype(shift0),
+          qmin, qmax, tmin, tmax, gs, sym, evalm, init)
+        out["fwd trial %d" % trial], out["dx trial %d" % trial] = y_ref, dx_ref
+        out["ds_buffer trial %d" % trial], out["db_buffer trial %d" % trial] = dsb, dbb
+    # per-channel walk
     gs = dtype(O.grad_scaler_pc(x.size, 7, C, True, 1.0, dtype=dtype))
     y_ref = np.empty_like(x)
     f = getattr(ref, "ref_fwd_pc_" + suf)
     f.argtypes = [vp, vp] + [ctypes.c_int64] * 3 + [vp, vp] + [cT] * 4 + [ctypes.c_int, cT]
     f(x.ctypes.data, y_ref.ctypes.data, outer, C, inner, sc.ctypes.data, sh.ctypes.data, -8, 7, -128, 127, 0, eps)
-    assert_bits_equal(O.fwd_pc(x, sc, sh, outer, C, inner, -8, 7, -128, 127), y_ref, "fwd_pc")
     dx_ref, dsb, dbb = np.empty_like(x), np.empty_like(x), np.empty_like(x)
     f = getattr(ref, "ref_bwd_pc_" + suf)
     f.argtypes = [vp] * 5 + [ctypes.c_int64] * 3 + [vp, vp] + [cT] * 5 + [ctypes.c_int] * 3 + [cT]
     f(g.ctypes.data, x.ctypes.data, dx_ref.ctypes.data, dsb.ctypes.data, dbb.ctypes.data, outer, C, inner, sc.ctypes.data,
       sh.ctypes.data, -8, 7, -128, 127, gs, 0, 0, 0, eps)
-    r = O.bwd_pc(g, x, sc, sh, outer, C, inner, -8, 7, -128, 127, True, 1.0, False, want_buffers=True)
-    assert_bits_equal(r.dx, dx_ref, "dx_pc")
-    assert_bits_equal(r.ds_buf, dsb, "ds_buffer_pc")
-    assert_bits_equal(r.db_buf, dbb, "db_buffer_pc")
+    out["fwd_pc"], out["dx_pc"], out["ds_buffer_pc"], out["db_buffer_pc"] = y_ref, dx_ref, dsb, dbb
+    return out
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_oracle_bitwise_vs_reference_scalar_header(dtype):
+    import json
+    got = oracle_scalar_outputs(dtype)
+    with open(os.path.join(ROOT, "tests", "golden", "ref_scalar_digests.json")) as f:
+        pinned = json.load(f)["f32" if dtype == np.float32 else "f64"]
+    assert sorted(pinned) == sorted(got)
+    for label, arr in got.items():
+        assert sha(arr) == pinned[label], label + ": the oracle is not bit-identical with the reference's scalar header"
+    if os.path.isfile(_REF_SCALAR):         # the reference's build itself, where it was made
+        want = ref_scalar_outputs(ctypes.CDLL(_REF_SCALAR), dtype)
+        for label, arr in got.items():
+            assert_bits_equal(arr, want[label], label)
 
 
 def test_oracle_meanstd_pinned(traces):

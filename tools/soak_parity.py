@@ -2,6 +2,7 @@
 oracle at the sizes the launch policy was written for.
 
     python3 tools/soak_parity.py --minutes 15 [--seed 1] > profiles/rNN_soak.txt
+    python3 tools/soak_parity.py --against pinned        # the cases of tests/golden/soak_reference.json, against the reference's results
 
 tests/test_fuzz_gpu.py draws shapes of at most 600 000 elements (the oracle has to keep a test fast), where only the
 256-lane windows and the segment walk are the policy's own choice and the other families are reached by forcing them.  Here
@@ -26,7 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "lsqfakequantize-pytorch_amd"))
 
-from helpers import assert_bits_equal, assert_reduction_close  # noqa: E402
+from helpers import assert_bits_equal, assert_reduction_close, sha  # noqa: E402
 from oracle import lsq_oracle as O  # noqa: E402
 
 RANGES = [(0, 127, 0, 255), (-64, 63, -128, 127), (-128, 127, -128, 127), (0, 255, 0, 255), (-8, 7, -128, 127), (0, 15, 0, 255)]
@@ -81,6 +82,9 @@ def narrow_equal(got, want, x, what):
 EXTREME = [0.0]
 AGAINST = ["oracle"]
 REF = [None]          # --against reference: the worker process that runs the reference's own CPU ops
+PINNED = [None, None]  # --against pinned: (tests/golden/soak_reference.json, its .npz of d_scale / d_shift)
+CASE = [0]            # the number of the case being run
+PINNED_JSON = os.path.join(ROOT, "tests", "golden", "soak_reference.json")
 
 
 def ref_worker():
@@ -140,9 +144,9 @@ def ref_call(xs, gsh, scale, shift, args):
         shutil.rmtree(d, ignore_errors=True)
 
 
-def one_case(rng, dev, lsq, E, counts):
+def draw_lsq_case(rng, against_ref):
+    """the inputs and arguments of one `--ops lsq` case, drawn from `rng` alone (no device involved)"""
     extreme = rng.random() < EXTREME[0]
-    against_ref = AGAINST[0] == "reference"
     shape, axis, lab = draw_shape(rng)
     n = int(np.prod(shape))
     dtype = [torch.float32, torch.float32, torch.bfloat16, torch.bfloat16, torch.float16, torch.float64][int(rng.integers(0, 6))]
@@ -192,6 +196,23 @@ def one_case(rng, dev, lsq, E, counts):
                     g = torch.from_numpy(g).to(dtype).to(torch.float32).numpy()
         tag += " extreme=%d" % what
     xs, gsh = x.reshape(shape), g.reshape(shape)
+    return dict(shape=shape, axis=axis, n=n, dtype=dtype, npdt=npdt, narrow=narrow, per_channel=per_channel, C=C, qmin=qmin, qmax=qmax,
+                tmin=tmin, tmax=tmax, affine=affine, eval_mode=eval_mode, init_mode=init_mode, use_gs=use_gs, gs=gs, offset=offset,
+                tag=tag, xs=xs, gsh=gsh, scale=scale, shift=shift)
+
+
+def ref_args(d):
+    return dict(qmin=d["qmin"], qmax=d["qmax"], tmin=d["tmin"], tmax=d["tmax"], axis=d["axis"], use_gs=d["use_gs"], gs=d["gs"],
+                affine=d["affine"], per_channel=d["per_channel"], eval_mode=d["eval_mode"], init_mode=d["init_mode"])
+
+
+def one_case(rng, dev, lsq, E, counts):
+    against_ref = AGAINST[0] in ("reference", "pinned")
+    d = draw_lsq_case(rng, against_ref)
+    shape, axis, n, dtype, npdt, narrow, per_channel, C = (d[k] for k in ("shape", "axis", "n", "dtype", "npdt", "narrow", "per_channel", "C"))
+    qmin, qmax, tmin, tmax, affine, eval_mode, init_mode, use_gs, gs, offset, tag = (d[k] for k in (
+        "qmin", "qmax", "tmin", "tmax", "affine", "eval_mode", "init_mode", "use_gs", "gs", "offset", "tag"))
+    xs, gsh, scale, shift = d["xs"], d["gsh"], d["scale"], d["shift"]
 
     def on_gpu(a):
         t = torch.from_numpy(a).to(dev).to(dtype)
@@ -222,11 +243,26 @@ def one_case(rng, dev, lsq, E, counts):
         oy = O.fwd_pt(xs, scale[0], shift[0], qmin, qmax, tmin, tmax, init_mode)
         r = O.bwd_pt(gsh, xs, scale[0], shift[0], qmin, qmax, tmin, tmax, use_gs, gs, not affine, eval_mode, init_mode)
     tag = "[%s] %s" % (family, tag)
+    if AGAINST[0] == "pinned":
+        # the reference's own CPU ops on these very inputs, as stored (tests/golden/make_ref_pinned.py): y, dx by sha256 (bit for
+        # bit), d_scale / d_shift inside the bar
+        want = PINNED[0]["cases"][str(CASE[0])]
+        assert want["tag"] == d["tag"], "the pinned case %d was drawn as %r, now %r" % (CASE[0], want["tag"], d["tag"])
+        assert sha(y.detach().cpu().numpy()) == want["y_sha256"], tag + " y vs the reference"
+        assert sha(xt.grad.cpu().numpy()) == want["dx_sha256"], tag + " dx vs the reference"
+        assert sha(oy) == want["y_sha256"] and sha(r.dx) == want["dx_sha256"], tag + " ORACLE y / dx vs the reference"
+        rds, rdb = PINNED[1]["c%d_ds" % CASE[0]], PINNED[1]["c%d_db" % CASE[0]]
+        ds = st.grad.cpu().numpy() if st.grad is not None else np.zeros(C, npdt)
+        db = bt.grad.cpu().numpy() if bt.grad is not None else np.zeros(C, npdt)
+        if rds.size == C:
+            assert_reduction_close(ds, rds, r.abs_ds, tag + " ds vs the reference")
+        if rdb.size == C:
+            assert_reduction_close(db, rdb, r.abs_db, tag + " db vs the reference")
+        return n, tag
     if against_ref:
         # the same inputs through the reference's own CPU ops: y, dx bit for bit; d_scale / d_shift inside the bar, with the
         # oracle's sum|terms| as the yardstick (the reference does not report one)
-        ry, rdx, rds, rdb = ref_call(xs, gsh, scale, shift, dict(qmin=qmin, qmax=qmax, tmin=tmin, tmax=tmax, axis=axis, use_gs=use_gs, gs=gs,
-                                                                 affine=affine, per_channel=per_channel, eval_mode=eval_mode, init_mode=init_mode))
+        ry, rdx, rds, rdb = ref_call(xs, gsh, scale, shift, ref_args(d))
         assert_bits_equal(y.detach().cpu().numpy(), ry, tag + " y vs the reference")
         assert_bits_equal(xt.grad.cpu().numpy(), rdx, tag + " dx vs the reference")
         assert_bits_equal(oy, ry, tag + " ORACLE y vs the reference")
@@ -476,8 +512,10 @@ def main():
                     "side: levels, mask backward, min / max, mean / std; foreach: lsq_foreach against N single calls; "
                     "shards: dim 0 cut into uneven shards, their fp64 sums added, against the oracle on the whole tensor")
     ap.add_argument("--only", type=int, default=-1, help="replay: run this case number of the seed only")
-    ap.add_argument("--against", choices=["oracle", "reference"], default="oracle", help="--ops lsq: reference = the reference's own CPU "
-                    "ops (oracle/_ref/libtorchlsq_ref_ops.so, in a worker process; fp32 / fp64 storage only)")
+    ap.add_argument("--against", choices=["oracle", "reference", "pinned"], default="oracle", help="--ops lsq: reference = the reference's "
+                    "own CPU ops (oracle/_ref/libtorchlsq_ref_ops.so, in a worker process; fp32 / fp64 storage only); pinned = their "
+                    "results for the cases of tests/golden/soak_reference.json (its seed, --extreme and case count; no --minutes)")
+    ap.add_argument("--cases", type=int, default=0, help="run exactly this many cases (0: as many as --minutes allows)")
     ap.add_argument("--ref-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--extreme", type=float, default=0.0, help="--ops lsq: share of the cases with a subnormal / huge / inf / NaN scale, "
                     "an inf / NaN shift or inf / NaN / 1e30 gradients")
@@ -485,6 +523,12 @@ def main():
     if a.ref_worker:
         return ref_worker()
     AGAINST[0] = a.against
+    if a.against == "pinned":
+        import json
+        with open(PINNED_JSON) as f:
+            PINNED[0] = json.load(f)
+        PINNED[1] = np.load(PINNED_JSON[:-5] + ".npz")
+        a.seed, a.extreme, a.cases = PINNED[0]["seed"], PINNED[0]["extreme"], len(PINNED[0]["cases"])
     import torchlsq  # noqa: F401
     from torchlsq import extension as E
     from torchlsq.functional import lsq
@@ -494,8 +538,9 @@ def main():
     EXTREME[0] = a.extreme
     counts, failures, elements, case = {}, [], 0, 0
     t_end = time.time() + a.minutes * 60.0
-    while time.time() < t_end:
+    while (case < a.cases) if a.cases > 0 else (time.time() < t_end):
         rng = np.random.default_rng([a.seed, case])       # a case replays from (seed, case) alone
+        CASE[0] = case
         if a.only >= 0 and case != a.only:
             case += 1
             continue
@@ -518,7 +563,8 @@ def main():
               "shards": "through torchlsq.distributed.sharded_backward, shard by shard,"}[a.ops],
              "against N single calls" if a.ops == "foreach" else
              ("against the REFERENCE's CPU ops (oracle/_ref/libtorchlsq_ref_ops.so) -- and the oracle against them" if a.against == "reference"
-              else "against oracle/lsq_oracle.c")))
+              else "against the REFERENCE's CPU ops as pinned in tests/golden/soak_reference.json -- and the oracle against them"
+              if a.against == "pinned" else "against oracle/lsq_oracle.c")))
     if a.ops == "foreach":
         print("# bar: every output and gradient bit-identical to N single lsq calls (which --ops lsq holds to the oracle)")
     elif a.ops == "shards":
