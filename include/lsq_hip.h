@@ -186,13 +186,15 @@ int lsq_hip_backward_per_tensor(int dtype, const void* grad, const void* x, void
 size_t lsq_hip_backward_per_channel_workspace(int dtype, int64_t outer, int64_t channels, int64_t inner);
 
 /* Replaces lsq_forward_per_channel_impl, lsq_cuda.cu:147-199 (CPU twin lsq_cpu.cpp:145-193).
- * scale, shift: device pointers to `channels` elements. */
+ * scale, shift: device pointers to `channels` elements.  x and y must be element-aligned (every tensor view is): LSQ_EINVAL
+ * otherwise. */
 int lsq_hip_forward_per_channel(int dtype, const void* x, void* y, int64_t outer, int64_t channels,
                                 int64_t inner, const void* scale, const void* shift,
                                 const lsq_params* p, const lsq_fwd_extras* extras, void* stream);
 
 /* Replaces lsq_backward_per_channel_impl, lsq_cuda.cu:202-297 (CPU twin lsq_cpu.cpp:197-294).
  * ds, db: `channels` elements each.  dsdb_wide (optional): double[2*channels], ds sums first.
+ * grad, x and dx must be element-aligned (every tensor view is): LSQ_EINVAL otherwise.
  * NOTE the gradient scaler follows the CPU oracle (/C inside the sqrt, lsq_cpu.cpp:250), not the
  * reference's CUDA kernel (lsq_cuda.cu:274), which omits it. */
 int lsq_hip_backward_per_channel(int dtype, const void* grad, const void* x, void* dx, void* ds,
@@ -260,8 +262,9 @@ int lsq_hip_backward_per_channel_multi(int dtype, const lsq_pc_item* items, int3
  *           instantiation (0: not asked), kernel family -- 1 = 256-lane windows, 2 = row-group windows, 3 = segment walk,
  *           4 = owner windows (one launch, no workspace) --, LDS-DMA ring depth (0 = register loops), workgroup size,
  *           ring copies issued with the streaming hint]
- * It is the same code path the launch takes (the sizes of lsq_hip_backward_per_channel_workspace come from it too), so a
- * test on the SHIPPED library can tell which kernel family a shape runs without a debug build (tests/test_shipped_binary_gpu.py).
+ * It is the plan the launch itself is made from (lsq_per_channel.hip, plan_backward; the sizes of
+ * lsq_hip_backward_per_channel_workspace come from the same plans), so a test on the SHIPPED library can tell which kernel
+ * family a shape runs without a debug build (tests/test_shipped_binary_gpu.py).
  * Depends on the current device (CU count, the instantiation's register count): needs a GPU. */
 int lsq_hip_plan_backward_per_channel(int dtype, int64_t outer, int64_t channels, int64_t inner, int aligned16,
                                       const lsq_params* p, int32_t* out8);

@@ -43,6 +43,11 @@ int hip_status(hipError_t e, const char* what) {
 
 bool dtype_ok(int dtype) { return dtype >= LSQ_F32 && dtype <= LSQ_F16; }
 int io_vec(int dtype) { return dtype == LSQ_F32 ? 4 : dtype == LSQ_F64 ? 2 : 8; }
+// a buffer address that is a multiple of the element size (every tensor view's is; a raw C caller's may not be)
+bool elem_aligned(int dtype, const void* a) {
+    const uintptr_t esz = dtype == LSQ_F64 ? 8 : (dtype == LSQ_F32 ? 4 : 2);
+    return (reinterpret_cast<uintptr_t>(a) & (esz - 1)) == 0;
+}
 
 int check_common(int dtype, const lsq_params* p) {
     if (!dtype_ok(dtype)) return fail(LSQ_EINVAL, "unknown dtype code %d", dtype);
@@ -117,7 +122,7 @@ size_t lsq_hip_backward_per_tensor_workspace(int dtype, int64_t n) {
 
 size_t lsq_hip_backward_per_channel_workspace(int dtype, int64_t outer, int64_t channels, int64_t inner) {
     if (!dtype_ok(dtype) || outer <= 0 || channels <= 0 || inner <= 0) return 256;
-    // The size is what the launch policy will ask for (lsq::bwd_pc_workspace_bytes: the policy run as a plan); callers ask
+    // The size is what the launch policy will ask for (lsq::bwd_pc_workspace_bytes: the workspace of its plans); callers ask
     // once per backward with the same few shapes, so the answers of this thread are kept -- every distinct
     // (device, dtype, shape) of a model, not just the last few.  (The answer depends on the CU count of the current device.)
     struct Key {
@@ -209,6 +214,7 @@ LSQ_EX_LINKAGE int lsq_hip_forward_per_channel_ex(int dtype, const void* x, void
     if (int rc = check_ocl(outer, channels, inner)) return rc;
     if (outer == 0 || inner == 0) return LSQ_OK;
     if (!x || !scale || !shift || (!y && !(extras && extras->levels))) return fail(LSQ_EINVAL, "forward_per_channel: NULL buffer");
+    if (!elem_aligned(dtype, x) || !elem_aligned(dtype, y)) return fail(LSQ_EINVAL, "forward_per_channel: x and y must be element-aligned");
     if (int rc = check_levels(p, extras)) return rc;
     hipError_t e = hipSuccess;
     LSQ_DISPATCH_IO(dtype, e = lsq::forward_per_channel<IO>(x, y, outer, channels, inner, scale, shift, *p, extras,
@@ -232,12 +238,15 @@ LSQ_EX_LINKAGE int lsq_hip_backward_per_channel_ex(int dtype, const void* grad, 
     if (outer == 0 || inner == 0)
         return fail(LSQ_EINVAL, "backward_per_channel: empty tensor (the caller handles it, reference lsq_cpu.cpp:221-223)");
     if (!grad || !x || !dx || !ds || !db || !scale || !shift) return fail(LSQ_EINVAL, "backward_per_channel: NULL buffer");
+    // (the launch policy plans for element-aligned buffers only: lsq::bwd_pc_workspace_bytes)
+    if (!elem_aligned(dtype, grad) || !elem_aligned(dtype, x) || !elem_aligned(dtype, dx))
+        return fail(LSQ_EINVAL, "backward_per_channel: grad, x and dx must be element-aligned");
     if (!workspace) return fail(LSQ_EWORKSPACE, "backward_per_channel: NULL workspace");
     if (reinterpret_cast<uintptr_t>(workspace) & 15u) return fail(LSQ_EWORKSPACE, "workspace must be 16-byte aligned");
     (void)extras;      // lsq_bwd_extras.ticket: accepted and ignored by the per-channel backward (include/lsq_hip.h)
     hipError_t e = hipSuccess;
     LSQ_DISPATCH_IO(dtype, e = lsq::backward_per_channel<IO>(grad, x, dx, ds, db, dsdb_wide, outer, channels, inner,
-                                                              scale, shift, *p, workspace, workspace_bytes, nullptr, variant,
+                                                              scale, shift, *p, workspace, workspace_bytes, variant,
                                                               static_cast<hipStream_t>(stream)));
     if (e == hipErrorInvalidValue)
         return fail(LSQ_EWORKSPACE, "backward_per_channel: workspace of %zu bytes is too small (ask "
@@ -259,14 +268,8 @@ int lsq_hip_plan_backward_per_channel(int dtype, int64_t outer, int64_t channels
     if (outer <= 0 || channels <= 0 || inner <= 0 || !out8)
         return fail(LSQ_EINVAL, "plan_backward_per_channel: positive [outer, C, inner] and an output array");
     lsq::LaunchNote note{0, 0, 0, 0, 0, 0, 0, 0};
-    size_t need = 0;
     hipError_t e = hipSuccess;
-    // only the alignment of the (never dereferenced) buffer addresses matters to a plan
-    LSQ_DISPATCH_IO(dtype, {
-        void* const fake = reinterpret_cast<void*>(static_cast<uintptr_t>(aligned16 ? 4096 : 4096 + sizeof(typename IO::elem)));
-        e = lsq::backward_per_channel<IO>(fake, fake, fake, fake, fake, nullptr, outer, channels, inner, fake, fake, *p, fake, 0,
-                                          nullptr, 0, nullptr, &need, &note);
-    });
+    LSQ_DISPATCH_IO(dtype, e = lsq::plan_backward_per_channel<IO>(outer, channels, inner, *p, aligned16 != 0, note));
     if (int rc = hip_status(e, "lsq_hip_plan_backward_per_channel")) return rc;
     out8[0] = note.grid_x; out8[1] = note.grid_y; out8[2] = note.resident_per_cu; out8[3] = note.vgprs_hint;
     out8[4] = note.kind; out8[5] = note.dma_depth; out8[6] = note.block; out8[7] = note.ring_nt;

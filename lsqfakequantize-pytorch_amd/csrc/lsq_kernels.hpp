@@ -200,9 +200,9 @@ inline int resident_blocks_per_cu(const void* kernel, size_t lds_bytes) {
     return n;
 }
 
-// what a per-channel backward launch looks like: filled by a PLAN of the launch policy (lsq_hip_plan_backward_per_channel,
-// production and tools build alike) and -- tools build only -- kept per thread for the last real launch
-// (lsq_hip_debug_last_launch)
+// what a per-channel launch looks like: part of its plan (lsq_per_channel.hip, plan_forward / plan_backward), reported by
+// lsq_hip_plan_backward_per_channel (production and tools build alike) and -- tools build only -- kept per thread for the
+// last real launch (lsq_hip_debug_last_launch)
 struct LaunchNote {
     int grid_x, grid_y, resident_per_cu, vgprs_hint;
     int kind;        // 1 = 256-lane windows, 2 = row-group windows, 3 = segment mode, 4 = owner windows
@@ -340,8 +340,12 @@ template <typename IO>
 hipError_t backward_per_channel(const void* grad, const void* x, void* dx, void* ds, void* db, double* wide,
                                 int64_t outer, int64_t channels, int64_t inner, const void* scale,
                                 const void* shift, const lsq_params& p, void* workspace, size_t workspace_bytes,
-                                uint32_t* ticket, int variant, hipStream_t stream, size_t* plan_need = nullptr,
-                                LaunchNote* plan_note = nullptr);
+                                int variant, hipStream_t stream);
+// the note of the launch backward_per_channel would make for such buffers (aligned16: grad, x, dx 16-byte aligned; they
+// are element-aligned in any case); nothing is launched
+template <typename IO>
+hipError_t plan_backward_per_channel(int64_t outer, int64_t channels, int64_t inner, const lsq_params& p, bool aligned16,
+                                     LaunchNote& note);
 
 // many per-channel quantizers in one launch (lsq_multi.hip)
 template <typename IO>

@@ -28,6 +28,8 @@
 // is padding: a walk of n rows is cut into groups of UNROLL, then UNROLL/2, ..., 1 rows.  Only the software-pipelined
 // loop of the 16-bit backward, whose prefetch can run past the end, re-reads the last row (clamped address, served
 // by L2) and masks its effects.  No global atomics, no zero-initialised buffers.
+#include <optional>
+
 #include "lsq_kernels.hpp"
 #include "lsq_pc_geom.hpp"
 #include "lsq_seg_body.hpp"
@@ -1334,73 +1336,11 @@ static inline int pick_cpl(int vec, int64_t inner) {
     if (vec == 1 || inner % vec == 0) return 1;
     return inner >= vec ? 2 : vec;
 }
-#ifdef LSQ_TOOLS
-// Tools build: a caller may force any launch variant or knob, so the size is the maximum over every geometry the tuning
-// range allows (tens of milliseconds of host time; lsq_capi.hip memoises it).
-static size_t bwd_pc_workspace_bytes_any(int io_vec, int64_t outer, int64_t channels, int64_t inner) {
-    const DeviceInfo& dev = device_info();
-    size_t need = 0;
-    const int vecs[3] = {io_vec, 1, 4};   // full packets, single elements, half packets (16-bit window backward)
-    for (int vi = 0; vi < 3; ++vi) {
-        for (int bpc = 1; bpc <= 2 * kMaxBlocksPerCU; ++bpc) {   // pick_splits may go up to twice the requested count
-            for (int res = 0; res <= 8; ++res) {   // residency of the instantiation that will run: 0 (not used) .. 8 per CU
-                const PcGeom g = make_geom(outer, channels, inner, vecs[vi], dev.cu_count * bpc, 27, dev.cu_count * res);
-                need = std::max(need, static_cast<size_t>(g.splits) * g.n_windows * g.k_slots * sizeof(double2));
-            }
-            if (vi == 0 && inner == 1 && io_vec > 1 && channels % io_vec == 0) {
-                const int ovr = knob::get(knob::kWwMinRows);
-                const int min_rows = ovr > 0 ? ovr : (io_vec > 4 ? 16 : (107 + (16 / io_vec) - 1) / (16 / io_vec));   // kWwMinRows of the storage type
-                for (int res = 0; res <= 8; ++res) {
-                    for (int s64 = 0; s64 < 3; ++s64) {     // whole rows, 64-lane windows, 1024-lane workgroups
-                        const PcGeom g = make_geom_ww(outer, channels, io_vec, dev.cu_count * bpc, min_rows, dev.cu_count * res, s64 == 1,
-                                                      s64 == 2 ? (io_vec > 4 ? kBigBlockOf<2> : kBigBlockOf<4>) : kBlock);
-                        need = std::max(need, static_cast<size_t>(g.splits) * g.n_windows * g.k_slots * sizeof(double2));
-                    }
-                }
-            }
-            if (vi < 2 && pick_segment_mode(vecs[vi], outer, channels, inner, dev.cu_count)) {
-                const SegGeom sgm = make_seg_geom(outer, channels, inner, vecs[vi], dev.cu_count * bpc);
-                need = std::max(need, static_cast<size_t>(channels) * sgm.segs * sgm.osplits * sizeof(double2));
-            }
-        }
-    }
-    return need + 256;
-}
-
-
-#endif
-
-// Scratch bytes of the backward: exactly what backward_per_channel (the library's own launch policy) asks for -- the same
-// code run as a PLAN (BwdPcCall::plan_need: geometry and kernel choice, nothing launched) for the argument properties the
-// size does not take: symmetric or not, init mode or not, 16-byte-aligned buffers or not; eval mode needs none.  A few
-// microseconds of host time (eight plans).
-template <typename IO>
-size_t bwd_pc_workspace_bytes(int64_t outer, int64_t channels, int64_t inner) {
-    size_t need = 0;
-#ifdef LSQ_TOOLS
-    need = bwd_pc_workspace_bytes_any(IO::VEC, outer, channels, inner);
-#else
-    lsq_params p{};
-    p.quant_min = 0; p.quant_max = 127; p.type_min = 0; p.type_max = 255;
-    p.use_grad_scaling = 1; p.grad_scaler = 1.0; p.numel_for_scaler = 0;
-    for (int al = 0; al < 2; ++al) {
-        // only the alignment of the (never dereferenced) buffer addresses matters to the plan
-        void* const fake = reinterpret_cast<void*>(static_cast<uintptr_t>(al ? 4096 + sizeof(typename IO::elem) : 4096));
-        for (int mode = 0; mode < 4; ++mode) {
-            p.sym = mode & 1;
-            p.init_mode = (mode >> 1) & 1;
-            (void)backward_per_channel<IO>(fake, fake, fake, fake, fake, nullptr, outer, channels, inner, fake, fake, p, fake, 0,
-                                           nullptr, 0, nullptr, &need);
-        }
-    }
-#endif
-    return need + 256;
-}
 
 // LDS-DMA ring in the window-mode kernels by default, with the grid it likes: fewer, longer workgroups than the register
 // loops (it needs rows to keep its ring full).  A/B on one box, profiles/r02_dma_ab.txt: 8-16 % faster on every large shape
 // in both directions when the tensors are cache-resident; on cold buffers (profiles/r02_cold_buffers_pc.txt) it keeps that
-// lead for 16-bit storage only, hence the size rules further down (forward_per_channel, ring_nt_for).
+// lead for 16-bit storage only, hence the size rules further down (plan_forward, ring_nt_for).
 template <typename IO>
 constexpr bool kDmaDefault = true;
 template <typename IO>
@@ -1409,86 +1349,95 @@ template <typename IO>
 constexpr int kDmaFwdBlocksPerCU = sizeof(typename IO::elem) < 4 ? 4 : 8;
 constexpr int kFwdDmaDepth = 8;      // one 1 KiB stage per row and wave in the forward (x only); the backward rings are 4 deep
 
+// ---- plans ----------------------------------------------------------------------------------------
+// A per-channel launch is decided in full before anything is enqueued.  plan_forward / plan_backward hold the whole launch
+// policy: they pick the kernel instantiation, the geometry, the grid and the finalize, and call nothing of HIP but the
+// cached queries (device_info, registers_of, resident_blocks_per_cu).  forward_per_channel / backward_per_channel launch
+// what the plan says; lsq_hip_plan_backward_per_channel and the workspace size read the plan and launch nothing.
+template <typename T>
+using FwdPcKernel = void (*)(const void*, void*, int8_t*, int, int, PcGeom, const T*, const T*, Range<T>);
+template <typename T>
+using FwdSegKernel = void (*)(const void*, void*, int8_t*, int, int, SegGeom, const T*, const T*, Range<T>);
+template <typename T>
+using BwdPcKernel = void (*)(const void*, const void*, void*, PcGeom, const T*, const T*, Range<T>, T, double2*, PcDirect<T>);
+template <typename T>
+using BwdSegKernel = void (*)(const void*, const void*, void*, SegGeom, const T*, const T*, Range<T>, T, double2*, SegDirect<T>);
+template <typename T, typename G>
+using FinalizeKernel = void (*)(const double2*, G, int, int, int, T, T*, T*, double*);
+
+// Exactly one of `win` (window kernels over g) and `seg` (segment walk over sg) is set.
+template <typename T>
+struct FwdPcPlan {
+    FwdPcKernel<T> win = nullptr;
+    FwdSegKernel<T> seg = nullptr;
+    PcGeom g{};
+    SegGeom sg{};
+    dim3 grid;
+    size_t lds = 0;
+    LaunchNote note{};
+};
+
+template <typename T>
+struct BwdPcPlan {
+    BwdPcKernel<T> win = nullptr;
+    BwdSegKernel<T> seg = nullptr;
+    // the finalize that folds the partials (null for both: the kernel stores d_scale / d_shift itself -- owner windows, and
+    // the segment walk with one workgroup per channel)
+    FinalizeKernel<T, PcGeom> fin_win = nullptr;
+    FinalizeKernel<T, SegGeom> fin_seg = nullptr;
+    PcGeom g{};
+    SegGeom sg{};
+    dim3 grid, fin_grid;
+    int fin_ch = 0;
+    size_t lds = 0;
+    size_t workspace = 0;    // bytes of partials the launch writes
+    LaunchNote note{};
+};
+
 // ---- forward --------------------------------------------------------------------------------------
 template <typename IO, int V, int CPL, bool INIT, bool LEVELS>
-static hipError_t launch_fwd_pc(const void* x, void* y, int8_t* levels, int bias, int aux_kind, const PcGeom& g, const void* scale,
-                                const void* shift, const lsq_params& p, const Variant& v, hipStream_t stream) {
-    using T = typename IO::arith;
-    const Range<T> r = make_range<T>(p);
-    const dim3 grid(static_cast<unsigned>(g.n_windows), static_cast<unsigned>(g.splits));
-    const size_t table_bytes = static_cast<size_t>(g.k_slots) * sizeof(QSlot<T>);
-    const size_t lds = g.direct ? 0 : table_bytes;     // (direct: every lane reads its own channels)
-    // LDS-DMA ring (16-byte packets): forward_per_channel decided (v.dma == 2) and sized the grid for it
-    constexpr bool kDmaAble = V * sizeof(typename IO::elem) == 16;
-    constexpr int kDmaDepth = kFwdDmaDepth;
-    if constexpr (kDmaAble) {
-        const size_t lds_dma = ((table_bytes + 1023) & ~size_t(1023)) + static_cast<size_t>(kBlock / 64) * kDmaDepth * 1024;
-        if (v.dma == 2 && lds_dma <= 64 * 1024) {
-            hipLaunchKernelGGL((fwd_pc_kernel<IO, V, CPL, INIT, LEVELS, 1, true, true, kDmaDepth>), grid, dim3(kBlock), lds_dma, stream,
-                               x, y, levels, bias, aux_kind, g, static_cast<const T*>(scale), static_cast<const T*>(shift), r);
-            return hipGetLastError();
+static hipError_t pick_fwd_pc(FwdPcPlan<typename IO::arith>& pl, const Variant& v) {
+    // LDS-DMA ring (16-byte packets): plan_forward decided (v.dma == 2) and sized the grid and the LDS for it
+    if constexpr (V * sizeof(typename IO::elem) == 16) {
+        if (v.dma == 2) {
+            pl.win = fwd_pc_kernel<IO, V, CPL, INIT, LEVELS, 1, true, true, kFwdDmaDepth>;
+            return hipSuccess;
         }
     }
-#define LSQ_LAUNCH(U, NTLF, NTSF)                                                                                       \
-    hipLaunchKernelGGL((fwd_pc_kernel<IO, V, CPL, INIT, LEVELS, U, NTLF, NTSF>), grid, dim3(kBlock), lds, stream, x, y, levels, \
-                       bias, aux_kind, g, static_cast<const T*>(scale), static_cast<const T*>(shift), r)
+#define LSQ_PICK(U, NTLF, NTSF) pl.win = fwd_pc_kernel<IO, V, CPL, INIT, LEVELS, U, NTLF, NTSF>
     [[maybe_unused]] constexpr bool kFull = !INIT && !LEVELS && V > 1 && !std::is_same<IO, io_f64>::value &&
                                             !std::is_same<IO, io_f16>::value;
-    LSQ_DISPATCH_VARIANT(kFull, 4, v, LSQ_LAUNCH);
-#undef LSQ_LAUNCH
-    return hipGetLastError();
+    LSQ_DISPATCH_VARIANT(kFull, 4, v, LSQ_PICK);
+#undef LSQ_PICK
+    return hipSuccess;
 }
 
 template <typename IO, bool INIT, bool LEVELS>
-static hipError_t launch_fwd_seg(const void* x, void* y, int8_t* levels, int bias, int aux_kind, const SegGeom& g, const void* scale,
-                                 const void* shift, const lsq_params& p, const Variant& v, hipStream_t stream) {
-    using T = typename IO::arith;
-    const Range<T> r = make_range<T>(p);
-    const dim3 grid(static_cast<unsigned>(g.C * g.segs), static_cast<unsigned>(g.osplits));
-    // the most iterations a workgroup walks: short walks (a weight's channel) and long ones are two kernels (seg_forward)
-    // (not for a big grid whose iterations are rows 16 MB apart instead of neighbouring sub-rows: [4,8,1048576] bf16 forward
-    // 23.7 us with the loop, 26.4 us with the group -- profiles/r03_seg_up_front_ab.txt)
-    const bool short_walk = g.sub_per_seg * g.o_per_split <= kSegUpFront && knob::get(knob::kSegNoUpFront) == 0 &&
-                            (g.o_per_split == 1 || g.C * g.segs * g.osplits <= 8 * static_cast<int64_t>(device_info().cu_count));
-#define LSQ_LAUNCH(U, NTLF, NTSF)                                                                                              \
-    do {                                                                                                                       \
-        if (short_walk)                                                                                                        \
-            hipLaunchKernelGGL((fwd_seg_kernel<IO, IO::VEC, INIT, LEVELS, U, NTLF, NTSF, 1>), grid, dim3(kBlock), 0, stream, x, y, \
-                               levels, bias, aux_kind, g, static_cast<const T*>(scale), static_cast<const T*>(shift), r);     \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((fwd_seg_kernel<IO, IO::VEC, INIT, LEVELS, U, NTLF, NTSF, 2>), grid, dim3(kBlock), 0, stream, x, y, \
-                               levels, bias, aux_kind, g, static_cast<const T*>(scale), static_cast<const T*>(shift), r);     \
+static hipError_t pick_fwd_seg(FwdPcPlan<typename IO::arith>& pl, bool short_walk, const Variant& v) {
+#define LSQ_PICK(U, NTLF, NTSF)                                                         \
+    do {                                                                                \
+        if (short_walk) pl.seg = fwd_seg_kernel<IO, IO::VEC, INIT, LEVELS, U, NTLF, NTSF, 1>; \
+        else pl.seg = fwd_seg_kernel<IO, IO::VEC, INIT, LEVELS, U, NTLF, NTSF, 2>;      \
     } while (0)
     [[maybe_unused]] constexpr bool kFull = !INIT && !LEVELS && (std::is_same<IO, io_f32>::value || std::is_same<IO, io_bf16>::value);
-    LSQ_DISPATCH_VARIANT(kFull, kSegUnroll<IO>, v, LSQ_LAUNCH);
-#undef LSQ_LAUNCH
-    return hipGetLastError();
+    LSQ_DISPATCH_VARIANT(kFull, kSegUnroll<IO>, v, LSQ_PICK);
+#undef LSQ_PICK
+    return hipSuccess;
 }
 
 template <typename IO, int V, int CPL>
-static hipError_t fwd_pc_modes(const void* x, void* y, int8_t* levels, int bias, int aux_kind, const PcGeom& g, const void* scale,
-                               const void* shift, const lsq_params& p, const Variant& v, hipStream_t stream) {
-    if (p.init_mode) {
-        return levels ? launch_fwd_pc<IO, V, CPL, true, true>(x, y, levels, bias, aux_kind, g, scale, shift, p, v, stream)
-                      : launch_fwd_pc<IO, V, CPL, true, false>(x, y, levels, bias, aux_kind, g, scale, shift, p, v, stream);
-    }
-    return levels ? launch_fwd_pc<IO, V, CPL, false, true>(x, y, levels, bias, aux_kind, g, scale, shift, p, v, stream)
-                  : launch_fwd_pc<IO, V, CPL, false, false>(x, y, levels, bias, aux_kind, g, scale, shift, p, v, stream);
+static hipError_t fwd_pc_modes(FwdPcPlan<typename IO::arith>& pl, bool init, bool levels, const Variant& v) {
+    if (init) return levels ? pick_fwd_pc<IO, V, CPL, true, true>(pl, v) : pick_fwd_pc<IO, V, CPL, true, false>(pl, v);
+    return levels ? pick_fwd_pc<IO, V, CPL, false, true>(pl, v) : pick_fwd_pc<IO, V, CPL, false, false>(pl, v);
 }
 
+// packets_ok: every buffer is aligned for packets (forward_per_channel); ring_ok: x and y are 16-byte aligned
 template <typename IO>
-hipError_t forward_per_channel(const void* x, void* y, int64_t outer, int64_t channels, int64_t inner,
-                               const void* scale, const void* shift, const lsq_params& p,
-                               const lsq_fwd_extras* ex, int variant, hipStream_t stream) {
-    int8_t* levels = ex ? static_cast<int8_t*>(ex->levels) : nullptr;
-    const int bias = ex ? ex->level_bias : 0;
-    const int aux_kind = ex ? ex->aux_kind : 0;
+static hipError_t plan_forward(int64_t outer, int64_t channels, int64_t inner, bool init, bool levels, bool packets_ok,
+                               bool ring_ok, int variant, FwdPcPlan<typename IO::arith>& pl) {
+    using T = typename IO::arith;
     const DeviceInfo& dev = device_info();
-    // Packets need ELEMENT alignment only (lsq_math.hpp, PacketWord): a sliced view runs the packet kernels' register loops.
-    // What wants 16-byte sources is the LDS-DMA ring (ring_ok); the level bytes of a packet are stored as one word.
-    const bool aligned = is_elem_aligned<IO>(x) && is_elem_aligned<IO>(y) && (!levels || (reinterpret_cast<uintptr_t>(levels) & 7u) == 0);
-    const bool ring_ok = is_aligned16(x) && is_aligned16(y);
-    const int vec = pick_vec(IO::VEC, channels * inner, aligned);
+    const int vec = pick_vec(IO::VEC, channels * inner, packets_ok);
     const bool seg = pick_segment_mode(vec, outer, channels, inner, dev.cu_count);
     const Variant v = decode_variant(variant, seg ? (sizeof(typename IO::elem) >= 4 ? kDefaultPcSegVariant : kDefaultPcSegNarrowVariant)
                                                   : kDefaultPcFwdVariant);
@@ -1496,18 +1445,23 @@ hipError_t forward_per_channel(const void* x, void* y, int64_t outer, int64_t ch
     if (seg) {
         const SegGeom sg = make_seg_geom(outer, channels, inner, vec, target);
         if (!grid_fits(sg)) return hipErrorInvalidConfiguration;
-#ifdef LSQ_TOOLS
-        last_launch_note() = LaunchNote{static_cast<int>(sg.C * sg.segs), sg.osplits, 0, 0, 3, 0, kBlock, 0};
-#endif
-        if (p.init_mode) {
-            return levels ? launch_fwd_seg<IO, true, true>(x, y, levels, bias, aux_kind, sg, scale, shift, p, v, stream)
-                          : launch_fwd_seg<IO, true, false>(x, y, levels, bias, aux_kind, sg, scale, shift, p, v, stream);
-        }
-        return levels ? launch_fwd_seg<IO, false, true>(x, y, levels, bias, aux_kind, sg, scale, shift, p, v, stream)
-                      : launch_fwd_seg<IO, false, false>(x, y, levels, bias, aux_kind, sg, scale, shift, p, v, stream);
+        pl.sg = sg;
+        pl.grid = dim3(static_cast<unsigned>(sg.C * sg.segs), static_cast<unsigned>(sg.osplits));
+        pl.note = LaunchNote{static_cast<int>(sg.C * sg.segs), sg.osplits, 0, 0, 3, 0, kBlock, 0};
+        // the most iterations a workgroup walks: short walks (a weight's channel) and long ones are two kernels (seg_forward)
+        // (not for a big grid whose iterations are rows 16 MB apart instead of neighbouring sub-rows: [4,8,1048576] bf16 forward
+        // 23.7 us with the loop, 26.4 us with the group -- profiles/r03_seg_up_front_ab.txt)
+        const bool short_walk = sg.sub_per_seg * sg.o_per_split <= kSegUpFront && knob::get(knob::kSegNoUpFront) == 0 &&
+                                (sg.o_per_split == 1 || sg.C * sg.segs * sg.osplits <= 8 * static_cast<int64_t>(dev.cu_count));
+        if (init) return levels ? pick_fwd_seg<IO, true, true>(pl, short_walk, v) : pick_fwd_seg<IO, true, false>(pl, short_walk, v);
+        return levels ? pick_fwd_seg<IO, false, true>(pl, short_walk, v) : pick_fwd_seg<IO, false, false>(pl, short_walk, v);
     }
     const int cpl = pick_cpl(vec, inner);
     PcGeom g = make_geom(outer, channels, inner, vec, target, kFwdPerSlotRows<IO>);
+    auto ring_lds = [](const PcGeom& gg) {      // the channel table, then one 1 KiB stage per row and wave
+        return ((static_cast<size_t>(gg.k_slots) * sizeof(QSlot<T>) + 1023) & ~size_t(1023)) +
+               static_cast<size_t>(kBlock / 64) * kFwdDmaDepth * 1024;
+    };
     // The forward's LDS-DMA ring is NOT a default any more: it wins only when the same buffers are read again and again
     // (profiles/r02_dma_ab.txt: config 5 fp32 35.2 -> 32.2 us).  On input the previous kernel has just written
     // (profiles/r02_producer_consumer.txt: config 5 bf16 14.2 us with the register loops at 16 workgroups per CU, 17.5 us on
@@ -1535,9 +1489,7 @@ hipError_t forward_per_channel(const void* x, void* y, int64_t outer, int64_t ch
         const int tgt = variant == 0 ? dev.cu_count * kDmaFwdBlocksPerCU<IO> : target;
         const PcGeom gd = make_geom(outer, channels, inner, vec, tgt, kFwdPerSlotRows<IO>);
         const int64_t tiles_each = gd.n_tiles / std::max(1, gd.splits);
-        const size_t lds_ring = ((static_cast<size_t>(gd.k_slots) * sizeof(QSlot<typename IO::arith>) + 1023) & ~size_t(1023)) +
-                                static_cast<size_t>(kBlock / 64) * kFwdDmaDepth * 1024;
-        const bool table_big = lds_ring > 64 * 1024;
+        const bool table_big = ring_lds(gd) > 64 * 1024;
         // (tiles_each >= 8 on the ring's grid with a 2048-slot table already implies >= 2^24 elements: no separate size rule)
         if (v.dma == 2 || (table_big && tiles_each >= kFwdDmaDepth && tiles_each <= 64)) {
             g = gd;
@@ -1547,42 +1499,54 @@ hipError_t forward_per_channel(const void* x, void* y, int64_t outer, int64_t ch
         }
     }
     if (!grid_fits(g)) return hipErrorInvalidConfiguration;
+    pl.g = g;
+    pl.grid = dim3(static_cast<unsigned>(g.n_windows), static_cast<unsigned>(g.splits));
+    // the ring's stages, else the channel table (direct: none, every lane reads its own channels)
+    pl.lds = vv.dma == 2 ? ring_lds(g) : g.direct ? 0 : static_cast<size_t>(g.k_slots) * sizeof(QSlot<T>);
+    pl.note = LaunchNote{static_cast<int>(g.n_windows), g.splits, 0, 0, 1, vv.dma == 2 ? kFwdDmaDepth : 0, kBlock, g.ring_nt};
+    if (vec == 1) return fwd_pc_modes<IO, 1, 1>(pl, init, levels, vv);
+    if (cpl == 1) return fwd_pc_modes<IO, IO::VEC, 1>(pl, init, levels, vv);
+    if (cpl == 2) return fwd_pc_modes<IO, IO::VEC, 2>(pl, init, levels, vv);
+    return fwd_pc_modes<IO, IO::VEC, IO::VEC>(pl, init, levels, vv);
+}
+
+template <typename IO>
+hipError_t forward_per_channel(const void* x, void* y, int64_t outer, int64_t channels, int64_t inner,
+                               const void* scale, const void* shift, const lsq_params& p,
+                               const lsq_fwd_extras* ex, int variant, hipStream_t stream) {
+    using T = typename IO::arith;
+    int8_t* levels = ex ? static_cast<int8_t*>(ex->levels) : nullptr;
+    const int bias = ex ? ex->level_bias : 0;
+    const int aux_kind = ex ? ex->aux_kind : 0;
+    // Packets need ELEMENT alignment only (lsq_math.hpp, PacketWord), which x and y have (lsq_capi.hip): a sliced view runs
+    // the packet kernels' register loops.  What wants 16-byte sources is the LDS-DMA ring (ring_ok); the level bytes of a
+    // packet are stored as one word.
+    const bool packets_ok = !levels || (reinterpret_cast<uintptr_t>(levels) & 7u) == 0;
+    FwdPcPlan<T> pl;
+    if (hipError_t e = plan_forward<IO>(outer, channels, inner, p.init_mode != 0, levels != nullptr, packets_ok,
+                                        is_aligned16(x) && is_aligned16(y), variant, pl))
+        return e;
 #ifdef LSQ_TOOLS
-    last_launch_note() = LaunchNote{static_cast<int>(g.n_windows), g.splits, 0, 0, 1, vv.dma == 2 ? kFwdDmaDepth : 0, kBlock, g.ring_nt};
+    last_launch_note() = pl.note;
 #endif
-    if (vec == 1) return fwd_pc_modes<IO, 1, 1>(x, y, levels, bias, aux_kind, g, scale, shift, p, vv, stream);
-    if (cpl == 1) return fwd_pc_modes<IO, IO::VEC, 1>(x, y, levels, bias, aux_kind, g, scale, shift, p, vv, stream);
-    if (cpl == 2) return fwd_pc_modes<IO, IO::VEC, 2>(x, y, levels, bias, aux_kind, g, scale, shift, p, vv, stream);
-    return fwd_pc_modes<IO, IO::VEC, IO::VEC>(x, y, levels, bias, aux_kind, g, scale, shift, p, vv, stream);
+    const Range<T> r = make_range<T>(p);
+    const T* sc = static_cast<const T*>(scale);
+    const T* sh = static_cast<const T*>(shift);
+    if (pl.seg) hipLaunchKernelGGL(pl.seg, pl.grid, dim3(kBlock), 0, stream, x, y, levels, bias, aux_kind, pl.sg, sc, sh, r);
+    else hipLaunchKernelGGL(pl.win, pl.grid, dim3(kBlock), pl.lds, stream, x, y, levels, bias, aux_kind, pl.g, sc, sh, r);
+    return hipGetLastError();
 }
 
 // ---- backward -------------------------------------------------------------------------------------
-// Everything a window-mode backward launch needs besides the kernel's template arguments.
-template <typename T>
+// Everything a window-mode backward plan needs besides the kernel's template arguments.
 struct BwdPcCall {
-    const void* grad;
-    const void* x;
-    void* dx;
-    T* ds;
-    T* db;
-    double* wide;
     int64_t outer, C, inner;
-    const void* scale;
-    const void* shift;
-    const lsq_params* p;
-    T gs, sym_term;
-    double2* partials;
-    size_t workspace_bytes;
     int target_blocks;     // requested workgroups (CUs x workgroups per CU)
-    bool default_variant;  // the caller passed variant 0: the launcher may pick the grid of the code path it chooses
+    bool default_variant;  // the caller passed variant 0: the plan may pick the grid of the code path it chooses
     bool whole_rounds;     // size the grid in whole rounds of what the chip holds at once (make_geom)
     bool ring_ok;          // grad / x / dx are 16-byte aligned: the LDS-DMA ring (and the owner windows built on it) may be used
     Variant v;
-    hipStream_t stream;
-    size_t* plan_need;     // not null: PLAN only -- record the workspace bytes the launch would need, launch nothing
-    LaunchNote* plan_note; // PLAN only, may be null: what the launch would look like (lsq_hip_plan_backward_per_channel)
 };
-
 
 // rows a row-group-window workgroup walks at least.  4- and 8-byte storage: enough to keep its 16-byte-per-slot partial
 // row under ~5 % of what it streams.  16-bit storage: 16 -- the tensors this floor binds on (fewer rows than workgroups
@@ -1599,10 +1563,8 @@ static inline int ww_min_rows() {
 }
 
 template <typename IO, int V, int CPL, bool SYM, bool INIT, bool EVAL, bool WW = false>
-static hipError_t launch_bwd_pc(const BwdPcCall<typename IO::arith>& c) {
+static hipError_t plan_bwd_pc(const BwdPcCall& c, BwdPcPlan<typename IO::arith>& pl) {
     using T = typename IO::arith;
-    const Range<T> r = make_range<T>(*c.p);
-    const lsq_params& p = *c.p;
     // (tuning builds also compile the variant table of the dx-only EVAL kernel: the streaming rate of the access pattern)
     [[maybe_unused]] constexpr bool kFull = !SYM && !INIT && V > 1 && !std::is_same<IO, io_f64>::value &&
                                             !std::is_same<IO, io_f16>::value;
@@ -1613,12 +1575,12 @@ static hipError_t launch_bwd_pc(const BwdPcCall<typename IO::arith>& c) {
     // storage runs the pipelined loop at unroll 2 there (profiles/r01_lastaxis_sweep.txt).
     constexpr bool kNarrow = sizeof(typename IO::elem) < 4;
     constexpr int kDefU = kNarrow ? ((CPL == V && V > 1 && !WW) ? 2 : 1) : 4;
-    hipError_t result = hipSuccess;
-    // The geometry depends on how many workgroups of the chosen instantiation fit on the chip at once, so it is built
-    // here, where the kernel is known, together with the launch and the finalize.
-    // returns false (nothing launched) when `min_tiles` is asked for and a workgroup would walk fewer row tiles than that
-    auto run = [&](auto kern, int dma_depth, int target_blocks, int64_t min_tiles, int64_t max_tiles = INT64_MAX,
-                   int block = kBlock) -> bool {
+    // One candidate: 256-lane or row-group windows with `kern`.  The geometry depends on how many workgroups of the chosen
+    // instantiation fit on the chip at once, so it is built here, where the kernel is known, together with the finalize.
+    // No value (nothing planned, the next candidate's turn) when there is no room for the ring or a workgroup would walk
+    // fewer row tiles than `min_tiles`.
+    auto window = [&](BwdPcKernel<T> kern, int dma_depth, int target_blocks, int64_t min_tiles,
+                      int block = kBlock) -> std::optional<hipError_t> {
         const DeviceInfo& dev = device_info();
         auto geom = [&](int resident) {
             // rows of 128 / 192 / 256 lanes: 4- and 8-byte storage cuts them into 64-lane windows of four row groups
@@ -1627,23 +1589,19 @@ static hipError_t launch_bwd_pc(const BwdPcCall<typename IO::arith>& c) {
             return WW ? make_geom_ww(c.outer, c.C, V, target_blocks, ww_min_rows<IO>(), resident, split64, block)
                       : make_geom(c.outer, c.C, c.inner, V, target_blocks, 27, resident);
         };
-        auto lds_of = [&](const PcGeom& gg) {
-            // row groups: every group parks its sums ([R][k_slots] double2); narrow windows add one row per walk of a slot
-            size_t b = WW ? (static_cast<size_t>(gg.R) * gg.k_slots + (gg.k_slots < gg.block_threads ? gg.block_threads : 0)) * sizeof(double2)
-                          : static_cast<size_t>(gg.k_slots) * (sizeof(QSlot<T>) + 2 * sizeof(double));
-            if (dma_depth > 0) {
-                const size_t ring = bwd_lds_front_bytes(gg, sizeof(QSlot<T>)) +
-                                    static_cast<size_t>(gg.block_threads / 64) * dma_depth * kDmaStageBytes;
-                b = WW ? std::max(b, ring) : ring;      // row groups: the combine buffer reuses the ring's LDS
-            }
-            return b;
-        };
         // the LDS a workgroup needs does not depend on the split count: size it first, then the residency, then the grid
         const PcGeom g0 = geom(0);
-        const size_t lds = lds_of(g0);
+        // row groups: every group parks its sums ([R][k_slots] double2); narrow windows add one row per walk of a slot
+        size_t lds = WW ? (static_cast<size_t>(g0.R) * g0.k_slots + (g0.k_slots < g0.block_threads ? g0.block_threads : 0)) * sizeof(double2)
+                        : static_cast<size_t>(g0.k_slots) * (sizeof(QSlot<T>) + 2 * sizeof(double));
+        if (dma_depth > 0) {
+            const size_t ring = bwd_lds_front_bytes(g0, sizeof(QSlot<T>)) +
+                                static_cast<size_t>(g0.block_threads / 64) * dma_depth * kDmaStageBytes;
+            lds = WW ? std::max(lds, ring) : ring;      // row groups: the combine buffer reuses the ring's LDS
+        }
         // no room for the ring next to a very wide channel table: register loop (a 1024-lane workgroup has the CU to itself)
-        if (dma_depth > 0 && lds > (block > kBlock ? 160 : 64) * 1024) return false;
-        if (lds > 160 * 1024) { result = hipErrorInvalidConfiguration; return true; }   // (gfx950: 160 KiB of LDS per workgroup)
+        if (dma_depth > 0 && lds > (block > kBlock ? 160 : 64) * 1024) return std::nullopt;
+        if (lds > 160 * 1024) return hipErrorInvalidConfiguration;   // (gfx950: 160 KiB of LDS per workgroup)
         int per_cu = c.whole_rounds ? resident_blocks_per_cu(reinterpret_cast<const void*>(kern), lds) : 0;
         if (block > kBlock && per_cu > 0) {      // the register bound counts four-wave workgroups: convert it
             const int by_regs = resident_blocks_by_registers(reinterpret_cast<const void*>(kern)) * 4 / std::max(1, g0.block_threads / 64);
@@ -1651,43 +1609,20 @@ static hipError_t launch_bwd_pc(const BwdPcCall<typename IO::arith>& c) {
         }
         PcGeom g = geom(per_cu * dev.cu_count);
         g.ring_nt = ring_nt_for(c.outer * c.C * c.inner * static_cast<int64_t>(sizeof(typename IO::elem)), true, WW);
-#if defined(LSQ_TOOLS) && defined(LSQ_TIMELINE)
-        g.timeline = knob::timeline_buffer().load();
-#endif
         const int64_t tiles_each = g.n_tiles / std::max<int64_t>(1, g.splits);
-        if (tiles_each < min_tiles || tiles_each > max_tiles) return false;
-        if (!grid_fits(g)) { result = hipErrorInvalidConfiguration; return true; }
-        const size_t need = static_cast<size_t>(g.splits) * g.n_windows * g.k_slots * sizeof(double2);
-        if (c.plan_need) {
-            if (!p.eval_mode) *c.plan_need = std::max(*c.plan_need, need);
-            if (c.plan_note)
-                *c.plan_note = LaunchNote{static_cast<int>(g.n_windows), g.splits, per_cu, registers_of(reinterpret_cast<const void*>(kern)),
-                                          WW ? 2 : 1, dma_depth, g.block_threads, g.ring_nt};
-            return true;
-        }
-        if (!p.eval_mode && c.workspace_bytes < need) { result = hipErrorInvalidValue; return true; }
-        const dim3 grid(static_cast<unsigned>(g.n_windows), static_cast<unsigned>(g.splits));
-#ifdef LSQ_TOOLS
-        last_launch_note() = LaunchNote{static_cast<int>(g.n_windows), g.splits, per_cu, registers_of(reinterpret_cast<const void*>(kern)),
-                                        WW ? 2 : 1, dma_depth, g.block_threads, g.ring_nt};
-#endif
-        hipLaunchKernelGGL(kern, grid, dim3(g.block_threads), lds, c.stream, c.grad, c.x, c.dx, g, static_cast<const T*>(c.scale),
-                           static_cast<const T*>(c.shift), r, c.gs, c.partials, PcDirect<T>{nullptr, nullptr, nullptr, c.sym_term, 0});
-        result = hipGetLastError();
-        if (result != hipSuccess) return true;
-        const int fin_ch = fin_channels(c.C);
-        if (WW) {
-            const unsigned fgrid = static_cast<unsigned>((g.n_windows * g.k_slots + fin_ch - 1) / fin_ch);
-            hipLaunchKernelGGL((finalize_ww_kernel<T>), dim3(fgrid), dim3(kBlock), 0, c.stream, c.partials, g, fin_ch,
-                               p.eval_mode ? 1 : 0, p.sym ? 1 : 0, c.sym_term, c.ds, c.db, c.wide);
-        }
-        else {
-            const unsigned fgrid_w = static_cast<unsigned>((c.C + fin_ch - 1) / fin_ch);
-            hipLaunchKernelGGL((finalize_pc_kernel<T>), dim3(fgrid_w), dim3(kBlock), 0, c.stream, c.partials, g, fin_ch,
-                               p.eval_mode ? 1 : 0, p.sym ? 1 : 0, c.sym_term, c.ds, c.db, c.wide);
-        }
-        result = hipGetLastError();
-        return true;
+        if (tiles_each < min_tiles) return std::nullopt;
+        if (!grid_fits(g)) return hipErrorInvalidConfiguration;
+        pl.win = kern;
+        pl.g = g;
+        pl.grid = dim3(static_cast<unsigned>(g.n_windows), static_cast<unsigned>(g.splits));
+        pl.lds = lds;
+        pl.workspace = EVAL ? 0 : static_cast<size_t>(g.splits) * g.n_windows * g.k_slots * sizeof(double2);
+        pl.fin_ch = fin_channels(c.C);
+        pl.fin_win = WW ? finalize_ww_kernel<T> : finalize_pc_kernel<T>;
+        pl.fin_grid = dim3(static_cast<unsigned>(((WW ? g.n_windows * g.k_slots : c.C) + pl.fin_ch - 1) / pl.fin_ch));
+        pl.note = LaunchNote{static_cast<int>(g.n_windows), g.splits, per_cu, registers_of(reinterpret_cast<const void*>(kern)),
+                             WW ? 2 : 1, dma_depth, g.block_threads, g.ring_nt};
+        return hipSuccess;
     };
     // LDS-DMA ring instead of register buffers (16-byte packets only): the default whenever a workgroup walks at least
     // as many row tiles as the ring is deep -- with the grid the ring likes, kDmaBwdBlocksPerCU workgroups per CU;
@@ -1702,44 +1637,30 @@ static hipError_t launch_bwd_pc(const BwdPcCall<typename IO::arith>& c) {
     if constexpr (kDmaAble && !WW && !EVAL && V > 1 && CPL <= 2) {
         const int own_knob = knob::get(knob::kOwn);     // tools builds: 1 = wherever the shape allows, 2 = never, 3 = 1 without the priority turns
         const int own = own_knob == 3 ? 1 : own_knob;
-        const int64_t bytes = c.outer * c.C * c.inner * static_cast<int64_t>(sizeof(typename IO::elem));
-        if (c.ring_ok && own != 2 && (own == 1 || (c.default_variant && c.outer * c.C * c.inner <= kOwnMaxElemsOf<static_cast<int>(sizeof(typename IO::elem))>))) {
-            const int64_t elems = c.outer * c.C * c.inner;
-            auto launch_own = [&](auto block_c) -> bool {
-                constexpr int OB = decltype(block_c)::value;
-                const int min_run = knob::get(knob::kOwnMinRun);           // tools builds: bytes, 0 = kOwnMinRunBytes
-                const int fat = knob::get(knob::kOwnFat);                  // tools builds: 1 = smallest channel group, 2 = fattest
-                const OwnPlan op = plan_own(c.outer, c.C, c.inner, V, static_cast<int>(sizeof(typename IO::elem)), kDmaDepth,
-                                            device_info().cu_count, OB, min_run > 0 ? min_run : kOwnMinRunBytes,
-                                            fat ? fat - 1 : kOwnFatDefault);
-                if (op.k == 0) return false;
-                if (own != 1 && op.run_bytes < kOwnShortRunBytes && op.run_bytes % 128 != 0 && elems > kOwnMaxElemsShortRun) return false;
+        const int64_t elems = c.outer * c.C * c.inner;
+        if (c.ring_ok && own != 2 && (own == 1 || (c.default_variant && elems <= kOwnMaxElemsOf<static_cast<int>(sizeof(typename IO::elem))>))) {
+            const int min_run = knob::get(knob::kOwnMinRun);           // tools builds: bytes, 0 = kOwnMinRunBytes
+            const int fat = knob::get(knob::kOwnFat);                  // tools builds: 1 = smallest channel group, 2 = fattest
+            const OwnPlan op = plan_own(c.outer, c.C, c.inner, V, static_cast<int>(sizeof(typename IO::elem)), kDmaDepth,
+                                        device_info().cu_count, kOwnBlock, min_run > 0 ? min_run : kOwnMinRunBytes,
+                                        fat ? fat - 1 : kOwnFatDefault);
+            const bool short_run_out = own != 1 && op.run_bytes < kOwnShortRunBytes && op.run_bytes % 128 != 0 && elems > kOwnMaxElemsShortRun;
+            if (op.k != 0 && !short_run_out) {
                 PcGeom g = make_geom_own(c.outer, c.C, c.inner, V, op);
-                g.ring_nt = ring_nt_for(bytes, true, false);
+                g.ring_nt = ring_nt_for(elems * static_cast<int64_t>(sizeof(typename IO::elem)), true, false);
                 g.own_prio = own_knob == 3 ? 0 : 1;
-#if defined(LSQ_TOOLS) && defined(LSQ_TIMELINE)
-                g.timeline = knob::timeline_buffer().load();
-#endif
                 const size_t lds = bwd_lds_front_bytes(g, sizeof(QSlot<T>)) +
                                    static_cast<size_t>(g.block_threads / 64) * kDmaDepth * kDmaStageBytes;
-                if (lds > kLdsBytesPerWorkgroup) return false;     // (cannot happen with plan_own's sizing on gfx950: the other families then)
-                if (c.plan_need) {                       // no workspace
-                    if (c.plan_note)
-                        *c.plan_note = LaunchNote{static_cast<int>(g.n_windows), 1, op.per_cu, 0, 4, kDmaDepth, g.block_threads, g.ring_nt};
-                    return true;
+                // (cannot fail with plan_own's sizing on gfx950: the other families otherwise)
+                if (lds <= kLdsBytesPerWorkgroup) {
+                    pl.win = bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, 1, true, true, false, false, kDmaDepth, kOwnBlock>;
+                    pl.g = g;
+                    pl.grid = dim3(static_cast<unsigned>(g.n_windows));
+                    pl.lds = lds;
+                    pl.note = LaunchNote{static_cast<int>(g.n_windows), 1, op.per_cu, 0, 4, kDmaDepth, g.block_threads, g.ring_nt};
+                    return hipSuccess;
                 }
-                constexpr auto kern = bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, 1, true, true, false, false, kDmaDepth, OB>;
-#ifdef LSQ_TOOLS
-                last_launch_note() = LaunchNote{static_cast<int>(g.n_windows), 1, op.per_cu, registers_of(reinterpret_cast<const void*>(kern)),
-                                                4, kDmaDepth, g.block_threads, g.ring_nt};
-#endif
-                hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(g.n_windows)), dim3(g.block_threads), lds, c.stream, c.grad, c.x,
-                                   c.dx, g, static_cast<const T*>(c.scale), static_cast<const T*>(c.shift), r, c.gs, c.partials,
-                                   PcDirect<T>{c.ds, c.db, c.wide, c.sym_term, p.sym ? 1 : 0});
-                result = hipGetLastError();
-                return true;
-            };
-            if (launch_own(std::integral_constant<int, kOwnBlock>{})) return result;
+            }
         }
     }
     if constexpr (kDmaAble) {
@@ -1798,66 +1719,58 @@ static hipError_t launch_bwd_pc(const BwdPcCall<typename IO::arith>& c) {
                                      (w_lanes >= 64 || kBlock % static_cast<int>(w_lanes) != 0 || elems < (int64_t{5} << 22));
                 const bool use_big = big == 1 || (big == 0 && c.default_variant && w_lanes <= kBlock && fits && (low ? low_ok : band_ok));
                 constexpr int kBigBlock = kBigBlockOf<sizeof(typename IO::elem)>;
-                if (use_big &&
-                    run(bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, 1, true, true, false, WW, kDmaDepth, kBigBlock>, kDmaDepth,
-                        device_info().cu_count, (big == 1 || low) ? 0 : 2, INT64_MAX, kBigBlock))
-                    return result;
+                if (use_big) {
+                    if (auto e = window(bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, 1, true, true, false, WW, kDmaDepth, kBigBlock>,
+                                        kDmaDepth, device_info().cu_count, (big == 1 || low) ? 0 : 2, kBigBlock))
+                        return *e;
+                }
             }
             // The tiles-per-workgroup floor of the ring (as many as it is deep) does not hold for 16-bit row groups: there the
             // ring is ahead with ONE tile per workgroup too -- [1568,512] bf16 13.1 -> 11.0 us, [16384,128] 21.0 -> 15.8,
             // [1365,384] 11.9 -> 10.2, nothing behind by more than 2.5 % (profiles/r04_rowgroup_ring_small.txt)
             const int64_t floor_tiles = (WW && sizeof(typename IO::elem) < 4) ? 1 : kDmaDepth;
-            if (!((big_wide || small_wide) && c.v.dma != 2) &&
-                run(bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, 1, true, true, false, WW, kDmaDepth>, kDmaDepth, target,
-                    c.v.dma == 2 ? 0 : floor_tiles))
-                return result;
+            if (!((big_wide || small_wide) && c.v.dma != 2)) {
+                if (auto e = window(bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, 1, true, true, false, WW, kDmaDepth>, kDmaDepth, target,
+                                    c.v.dma == 2 ? 0 : floor_tiles))
+                    return *e;
+            }
         }
     }
-#define LSQ_LAUNCH_P(U, NTLF, NTSF, PIPEF) \
-    run(bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, U, NTLF, NTSF, PIPEF, WW>, 0, c.target_blocks, 0)
+    // register loops
+    BwdPcKernel<T> kern = nullptr;
+#define LSQ_PICK_P(U, NTLF, NTSF, PIPEF) kern = bwd_pc_kernel<IO, V, CPL, SYM, INIT, EVAL, U, NTLF, NTSF, PIPEF, WW>
 #ifdef LSQ_TUNING
     // tuning builds compile both loops for the swept kernels; the switch is the variant's `chunked` bit (unused here)
     const bool pipe = kFull ? c.v.chunked : kNarrow;
-#define LSQ_LAUNCH(U, NTLF, NTSF)                                   \
+#define LSQ_PICK(U, NTLF, NTSF)                                     \
     do {                                                            \
         if constexpr (kFull) {                                      \
-            if (pipe) LSQ_LAUNCH_P(U, NTLF, NTSF, true);            \
-            else LSQ_LAUNCH_P(U, NTLF, NTSF, false);                \
+            if (pipe) LSQ_PICK_P(U, NTLF, NTSF, true);              \
+            else LSQ_PICK_P(U, NTLF, NTSF, false);                  \
         } else {                                                    \
-            LSQ_LAUNCH_P(U, NTLF, NTSF, kNarrow);                   \
+            LSQ_PICK_P(U, NTLF, NTSF, kNarrow);                     \
         }                                                           \
     } while (0)
 #else
-#define LSQ_LAUNCH(U, NTLF, NTSF) LSQ_LAUNCH_P(U, NTLF, NTSF, kNarrow)
+#define LSQ_PICK(U, NTLF, NTSF) LSQ_PICK_P(U, NTLF, NTSF, kNarrow)
 #endif
-    LSQ_DISPATCH_VARIANT(kFull, kDefU, c.v, LSQ_LAUNCH);
-#undef LSQ_LAUNCH
-#undef LSQ_LAUNCH_P
-    return result;
+    LSQ_DISPATCH_VARIANT(kFull, kDefU, c.v, LSQ_PICK);
+#undef LSQ_PICK
+#undef LSQ_PICK_P
+    return *window(kern, 0, c.target_blocks, 0);     // (no ring, no tile floor: always an answer)
 }
 
 template <typename IO, bool SYM, bool INIT, bool EVAL>
-static hipError_t launch_bwd_seg(const void* grad, const void* x, void* dx, const SegGeom& g, const void* scale,
-                                 const void* shift, const lsq_params& p, typename IO::arith gs, double2* partials,
-                                 const SegDirect<typename IO::arith>& direct, const Variant& v, hipStream_t stream) {
-    using T = typename IO::arith;
-    const Range<T> r = make_range<T>(p);
-    const dim3 grid(static_cast<unsigned>(g.C * g.segs), static_cast<unsigned>(g.osplits));
-    const bool short_walk = g.sub_per_seg * g.o_per_split <= kSegUpFrontBwd<IO> && knob::get(knob::kSegNoUpFront) == 0 &&
-                            (g.o_per_split == 1 || g.C * g.segs * g.osplits <= 8 * static_cast<int64_t>(device_info().cu_count));
-#define LSQ_LAUNCH(U, NTLF, NTSF)                                                                                                 \
-    do {                                                                                                                          \
-        if (short_walk)                                                                                                           \
-            hipLaunchKernelGGL((bwd_seg_kernel<IO, IO::VEC, SYM, INIT, EVAL, U, NTLF, NTSF, 1>), grid, dim3(kBlock), 0, stream, grad, \
-                               x, dx, g, static_cast<const T*>(scale), static_cast<const T*>(shift), r, gs, partials, direct);  \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((bwd_seg_kernel<IO, IO::VEC, SYM, INIT, EVAL, U, NTLF, NTSF, 2>), grid, dim3(kBlock), 0, stream, grad, \
-                               x, dx, g, static_cast<const T*>(scale), static_cast<const T*>(shift), r, gs, partials, direct);  \
+static hipError_t pick_bwd_seg(BwdPcPlan<typename IO::arith>& pl, bool short_walk, const Variant& v) {
+#define LSQ_PICK(U, NTLF, NTSF)                                                                \
+    do {                                                                                       \
+        if (short_walk) pl.seg = bwd_seg_kernel<IO, IO::VEC, SYM, INIT, EVAL, U, NTLF, NTSF, 1>; \
+        else pl.seg = bwd_seg_kernel<IO, IO::VEC, SYM, INIT, EVAL, U, NTLF, NTSF, 2>;          \
     } while (0)
     [[maybe_unused]] constexpr bool kFull = !INIT && !EVAL && (std::is_same<IO, io_f32>::value || std::is_same<IO, io_bf16>::value);
-    LSQ_DISPATCH_VARIANT(kFull, kSegUnroll<IO>, v, LSQ_LAUNCH);
-#undef LSQ_LAUNCH
-    return hipGetLastError();
+    LSQ_DISPATCH_VARIANT(kFull, kSegUnroll<IO>, v, LSQ_PICK);
+#undef LSQ_PICK
+    return hipSuccess;
 }
 
 #define LSQ_MODE_SWITCH(CALL)                                  \
@@ -1876,18 +1789,8 @@ static hipError_t launch_bwd_seg(const void* grad, const void* x, void* dx, cons
     } while (0)
 
 template <typename IO, int V, int CPL, bool WW = false>
-static hipError_t bwd_pc_modes(const BwdPcCall<typename IO::arith>& c) {
-    const lsq_params& p = *c.p;
-#define LSQ_CASE(S, I, E) launch_bwd_pc<IO, V, CPL, S, I, E, WW>(c)
-    LSQ_MODE_SWITCH(LSQ_CASE);
-#undef LSQ_CASE
-}
-
-template <typename IO>
-static hipError_t bwd_seg_modes(const void* grad, const void* x, void* dx, const SegGeom& g, const void* scale,
-                                const void* shift, const lsq_params& p, typename IO::arith gs, double2* partials,
-                                const SegDirect<typename IO::arith>& direct, const Variant& v, hipStream_t stream) {
-#define LSQ_CASE(S, I, E) launch_bwd_seg<IO, S, I, E>(grad, x, dx, g, scale, shift, p, gs, partials, direct, v, stream)
+static hipError_t bwd_pc_modes(const BwdPcCall& c, const lsq_params& p, BwdPcPlan<typename IO::arith>& pl) {
+#define LSQ_CASE(S, I, E) plan_bwd_pc<IO, V, CPL, S, I, E, WW>(c, pl)
     LSQ_MODE_SWITCH(LSQ_CASE);
 #undef LSQ_CASE
 }
@@ -1902,55 +1805,41 @@ inline int64_t ww_max_elems() {
     return k > 0 ? int64_t{1} << k : (int64_t{512} << 20) / static_cast<int64_t>(sizeof(typename IO::elem));
 }
 
+// ring_ok: grad, x and dx are 16-byte aligned (they are element-aligned in any case, lsq_capi.hip)
 template <typename IO>
-hipError_t backward_per_channel(const void* grad, const void* x, void* dx, void* ds, void* db, double* wide,
-                                int64_t outer, int64_t channels, int64_t inner, const void* scale,
-                                const void* shift, const lsq_params& p, void* workspace, size_t workspace_bytes,
-                                uint32_t* ticket, int variant, hipStream_t stream, size_t* plan_need, LaunchNote* plan_note) {
+static hipError_t plan_backward(int64_t outer, int64_t channels, int64_t inner, const lsq_params& p, bool ring_ok, int variant,
+                                BwdPcPlan<typename IO::arith>& pl) {
     using T = typename IO::arith;
-    (void)ticket;
     const DeviceInfo& dev = device_info();
-    // (forward_per_channel: packets on any element-aligned view; the ring and the owner windows built on it want 16 bytes)
-    const bool aligned = is_elem_aligned<IO>(grad) && is_elem_aligned<IO>(x) && is_elem_aligned<IO>(dx);
-    const bool ring_ok = is_aligned16(grad) && is_aligned16(x) && is_aligned16(dx);
-    const int vec = pick_vec(IO::VEC, channels * inner, aligned);
+    // (plan_forward: packets on any element-aligned view; the ring and the owner windows built on it want 16 bytes)
+    const int vec = pick_vec(IO::VEC, channels * inner, true);
     const bool seg = pick_segment_mode(vec, outer, channels, inner, dev.cu_count);
     const Variant v = decode_variant(variant, seg ? (sizeof(typename IO::elem) >= 4 ? kDefaultPcSegVariant : kDefaultPcSegNarrowVariant)
                                                   : (sizeof(typename IO::elem) >= 4 ? kDefaultPcBwdWideVariant
                                                                                     : kDefaultPcBwdNarrowVariant));
     const int target = dev.cu_count * v.blocks_per_cu;
-    const int64_t numel = outer * channels * inner;
-    const int64_t n4s = p.numel_for_scaler > 0 ? p.numel_for_scaler : numel;
-    const T gs = grad_scaler_per_channel<T>(n4s, p.quant_max, channels, p.use_grad_scaling != 0, p.grad_scaler);
-    const T sym_term = static_cast<T>(0) * gs;
-    double2* partials = static_cast<double2*>(workspace);
-    const int fin_ch = fin_channels(channels);
-    const unsigned fgrid_w = static_cast<unsigned>((channels + fin_ch - 1) / fin_ch);
 
     if (seg) {
         const SegGeom sg = make_seg_geom(outer, channels, inner, vec, target);
         if (!grid_fits(sg)) return hipErrorInvalidConfiguration;
-        const size_t need = static_cast<size_t>(channels) * sg.segs * sg.osplits * sizeof(double2);
-        if (plan_need) {
-            if (!p.eval_mode) *plan_need = std::max(*plan_need, need);
-            if (plan_note) *plan_note = LaunchNote{static_cast<int>(sg.C * sg.segs), sg.osplits, 0, 0, 3, 0, kBlock, 0};
-            return hipSuccess;
+        pl.sg = sg;
+        pl.grid = dim3(static_cast<unsigned>(sg.C * sg.segs), static_cast<unsigned>(sg.osplits));
+        pl.workspace = p.eval_mode ? 0 : static_cast<size_t>(channels) * sg.segs * sg.osplits * sizeof(double2);
+        if (sg.segs != 1 || sg.osplits != 1) {      // (one workgroup per channel: it stores the sums itself, lsq_seg_body.hpp)
+            pl.fin_seg = finalize_seg_kernel<T>;
+            pl.fin_ch = fin_channels(channels);
+            pl.fin_grid = dim3(static_cast<unsigned>((channels + pl.fin_ch - 1) / pl.fin_ch));
         }
-        if (!p.eval_mode && workspace_bytes < need) return hipErrorInvalidValue;
-        const bool one_partial = sg.segs == 1 && sg.osplits == 1;
-#ifdef LSQ_TOOLS
-        last_launch_note() = LaunchNote{static_cast<int>(sg.C * sg.segs), sg.osplits, 0, 0, 3, 0, kBlock, 0};
-#endif
-        const SegDirect<T> direct{one_partial ? static_cast<T*>(ds) : nullptr, static_cast<T*>(db), wide, sym_term};
-        hipError_t e = bwd_seg_modes<IO>(grad, x, dx, sg, scale, shift, p, gs, partials, direct, v, stream);
-        if (e != hipSuccess || one_partial) return e;
-        hipLaunchKernelGGL((finalize_seg_kernel<T>), dim3(fgrid_w), dim3(kBlock), 0, stream, partials, sg, fin_ch,
-                           p.eval_mode ? 1 : 0, p.sym ? 1 : 0, sym_term, static_cast<T*>(ds), static_cast<T*>(db), wide);
-        return hipGetLastError();
+        pl.note = LaunchNote{static_cast<int>(sg.C * sg.segs), sg.osplits, 0, 0, 3, 0, kBlock, 0};
+        const bool short_walk = sg.sub_per_seg * sg.o_per_split <= kSegUpFrontBwd<IO> && knob::get(knob::kSegNoUpFront) == 0 &&
+                                (sg.o_per_split == 1 || sg.C * sg.segs * sg.osplits <= 8 * static_cast<int64_t>(dev.cu_count));
+#define LSQ_CASE(S, I, E) pick_bwd_seg<IO, S, I, E>(pl, short_walk, v)
+        LSQ_MODE_SWITCH(LSQ_CASE);
+#undef LSQ_CASE
     }
 
     constexpr int VB = kWindowBwdVec<IO>;
-    const int vecw = pick_vec(VB, channels * inner, aligned);
+    const int vecw = pick_vec(VB, channels * inner, true);
     const int cpl = pick_cpl(vecw, inner);
     // One channel per packet component (inner < V): a window spans 256 x V channels, so every workgroup ends with a
     // long epilogue and a 16-byte partial per slot, and the finalize has `splits` of them to fold per channel.  Fewer,
@@ -1961,19 +1850,122 @@ hipError_t backward_per_channel(const void* grad, const void* x, void* dx, void*
     if (last_axis && inner == 1 && !(variant & (1 << 11)) && (variant != 0 || outer * channels < ww_max_elems<IO>())) {
         // the quantized axis is the last one ([tokens, features], channels-last): row-group windows, one round of what
         // the chip holds (variant: workgroups per CU requested, rounded to whole rounds)
-        BwdPcCall<T> call{grad, x, dx, static_cast<T*>(ds), static_cast<T*>(db), wide, outer, channels, inner, scale, shift, &p,
-                          gs, sym_term, partials, workspace_bytes, variant == 0 ? dev.cu_count * kWwBwdBlocksPerCU : target,
-                          /*default_variant=*/variant == 0, /*whole_rounds=*/true, ring_ok, v, stream, plan_need, plan_note};
-        return bwd_pc_modes<IO, VB, VB, true>(call);
+        const BwdPcCall call{outer, channels, inner, variant == 0 ? dev.cu_count * kWwBwdBlocksPerCU : target,
+                             /*default_variant=*/variant == 0, /*whole_rounds=*/true, ring_ok, v};
+        return bwd_pc_modes<IO, VB, VB, true>(call, p, pl);
     }
     const int target_w = (variant == 0 && last_axis) ? dev.cu_count * kLastAxisBwdBlocksPerCU : target;
-    BwdPcCall<T> call{grad, x, dx, static_cast<T*>(ds), static_cast<T*>(db), wide, outer, channels, inner, scale, shift, &p,
-                      gs, sym_term, partials, workspace_bytes, target_w, /*default_variant=*/variant == 0,
-                      /*whole_rounds=*/!last_axis, ring_ok, v, stream, plan_need, plan_note};
-    if (vecw == 1) return bwd_pc_modes<IO, 1, 1>(call);
-    if (cpl == 1) return bwd_pc_modes<IO, VB, 1>(call);
-    if (cpl == 2) return bwd_pc_modes<IO, VB, 2>(call);
-    return bwd_pc_modes<IO, VB, VB>(call);
+    const BwdPcCall call{outer, channels, inner, target_w, /*default_variant=*/variant == 0, /*whole_rounds=*/!last_axis, ring_ok, v};
+    if (vecw == 1) return bwd_pc_modes<IO, 1, 1>(call, p, pl);
+    if (cpl == 1) return bwd_pc_modes<IO, VB, 1>(call, p, pl);
+    if (cpl == 2) return bwd_pc_modes<IO, VB, 2>(call, p, pl);
+    return bwd_pc_modes<IO, VB, VB>(call, p, pl);
+}
+
+template <typename IO>
+hipError_t backward_per_channel(const void* grad, const void* x, void* dx, void* ds, void* db, double* wide,
+                                int64_t outer, int64_t channels, int64_t inner, const void* scale,
+                                const void* shift, const lsq_params& p, void* workspace, size_t workspace_bytes,
+                                int variant, hipStream_t stream) {
+    using T = typename IO::arith;
+    BwdPcPlan<T> pl;
+    if (hipError_t e = plan_backward<IO>(outer, channels, inner, p, is_aligned16(grad) && is_aligned16(x) && is_aligned16(dx),
+                                         variant, pl))
+        return e;
+    if (workspace_bytes < pl.workspace) return hipErrorInvalidValue;
+#ifdef LSQ_TOOLS
+    last_launch_note() = pl.note;
+    if (pl.win) last_launch_note().vgprs_hint = registers_of(reinterpret_cast<const void*>(pl.win));   // (owner windows too)
+#ifdef LSQ_TIMELINE
+    pl.g.timeline = knob::timeline_buffer().load();
+#endif
+#endif
+    const int64_t n4s = p.numel_for_scaler > 0 ? p.numel_for_scaler : outer * channels * inner;
+    const T gs = grad_scaler_per_channel<T>(n4s, p.quant_max, channels, p.use_grad_scaling != 0, p.grad_scaler);
+    const T sym_term = static_cast<T>(0) * gs;
+    const Range<T> r = make_range<T>(p);
+    const T* sc = static_cast<const T*>(scale);
+    const T* sh = static_cast<const T*>(shift);
+    T* const dsT = static_cast<T*>(ds);
+    T* const dbT = static_cast<T*>(db);
+    double2* const partials = static_cast<double2*>(workspace);
+    const bool direct = !pl.fin_win && !pl.fin_seg;     // no finalize follows: the kernel stores d_scale / d_shift
+    if (pl.seg) {
+        const SegDirect<T> sd{direct ? dsT : nullptr, dbT, wide, sym_term};
+        hipLaunchKernelGGL(pl.seg, pl.grid, dim3(kBlock), 0, stream, grad, x, dx, pl.sg, sc, sh, r, gs, partials, sd);
+    } else {
+        const PcDirect<T> pd = direct ? PcDirect<T>{dsT, dbT, wide, sym_term, p.sym ? 1 : 0} : PcDirect<T>{nullptr, nullptr, nullptr, sym_term, 0};
+        hipLaunchKernelGGL(pl.win, pl.grid, dim3(pl.g.block_threads), pl.lds, stream, grad, x, dx, pl.g, sc, sh, r, gs, partials, pd);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || direct) return e;
+    const int eval = p.eval_mode ? 1 : 0, sym = p.sym ? 1 : 0;
+    if (pl.seg) hipLaunchKernelGGL(pl.fin_seg, pl.fin_grid, dim3(kBlock), 0, stream, partials, pl.sg, pl.fin_ch, eval, sym, sym_term, dsT, dbT, wide);
+    else hipLaunchKernelGGL(pl.fin_win, pl.fin_grid, dim3(kBlock), 0, stream, partials, pl.g, pl.fin_ch, eval, sym, sym_term, dsT, dbT, wide);
+    return hipGetLastError();
+}
+
+// lsq_hip_plan_backward_per_channel: what a backward over such buffers would launch
+template <typename IO>
+hipError_t plan_backward_per_channel(int64_t outer, int64_t channels, int64_t inner, const lsq_params& p, bool aligned16,
+                                     LaunchNote& note) {
+    BwdPcPlan<typename IO::arith> pl;
+    const hipError_t e = plan_backward<IO>(outer, channels, inner, p, aligned16, 0, pl);
+    note = pl.note;
+    return e;
+}
+
+#ifdef LSQ_TOOLS
+// Tools build: a caller may force any launch variant or knob, so the size is the maximum over every geometry the tuning
+// range allows (tens of milliseconds of host time; lsq_capi.hip memoises it).
+template <typename IO>
+static size_t bwd_pc_workspace_bytes_any(int64_t outer, int64_t channels, int64_t inner) {
+    const DeviceInfo& dev = device_info();
+    size_t need = 0;
+    const int vecs[3] = {IO::VEC, 1, 4};   // full packets, single elements, half packets (16-bit window backward)
+    for (int vi = 0; vi < 3; ++vi) {
+        for (int bpc = 1; bpc <= 2 * kMaxBlocksPerCU; ++bpc) {   // pick_splits may go up to twice the requested count
+            for (int res = 0; res <= 8; ++res) {   // residency of the instantiation that will run: 0 (not used) .. 8 per CU
+                const PcGeom g = make_geom(outer, channels, inner, vecs[vi], dev.cu_count * bpc, 27, dev.cu_count * res);
+                need = std::max(need, static_cast<size_t>(g.splits) * g.n_windows * g.k_slots * sizeof(double2));
+            }
+            if (vi == 0 && inner == 1 && IO::VEC > 1 && channels % IO::VEC == 0) {
+                for (int res = 0; res <= 8; ++res) {
+                    for (int s64 = 0; s64 < 3; ++s64) {     // whole rows, 64-lane windows, 1024-lane workgroups
+                        const PcGeom g = make_geom_ww(outer, channels, IO::VEC, dev.cu_count * bpc, ww_min_rows<IO>(), dev.cu_count * res,
+                                                      s64 == 1, s64 == 2 ? kBigBlockOf<sizeof(typename IO::elem)> : kBlock);
+                        need = std::max(need, static_cast<size_t>(g.splits) * g.n_windows * g.k_slots * sizeof(double2));
+                    }
+                }
+            }
+            if (vi < 2 && pick_segment_mode(vecs[vi], outer, channels, inner, dev.cu_count)) {
+                const SegGeom sgm = make_seg_geom(outer, channels, inner, vecs[vi], dev.cu_count * bpc);
+                need = std::max(need, static_cast<size_t>(channels) * sgm.segs * sgm.osplits * sizeof(double2));
+            }
+        }
+    }
+    return need + 256;
+}
+#endif
+
+// Scratch bytes of the backward: the most any plan_backward (the library's own launch policy) asks for over the argument
+// properties the size does not take: symmetric or not, init mode or not, 16-byte-aligned buffers or not (the launch
+// takes element-aligned buffers only, lsq_capi.hip); eval mode needs none.  A few microseconds of host time (eight plans).
+template <typename IO>
+size_t bwd_pc_workspace_bytes(int64_t outer, int64_t channels, int64_t inner) {
+    size_t need = 0;
+#ifdef LSQ_TOOLS
+    need = bwd_pc_workspace_bytes_any<IO>(outer, channels, inner);
+#else
+    lsq_params p{};
+    for (int mode = 0; mode < 8; ++mode) {
+        p.sym = mode & 1;
+        p.init_mode = (mode >> 1) & 1;
+        BwdPcPlan<typename IO::arith> pl;
+        if (plan_backward<IO>(outer, channels, inner, p, (mode >> 2) != 0, 0, pl) == hipSuccess) need = std::max(need, pl.workspace);
+    }
+#endif
+    return need + 256;
 }
 
 #define LSQ_INSTANTIATE(IO)                                                                                          \
@@ -1982,7 +1974,8 @@ hipError_t backward_per_channel(const void* grad, const void* x, void* dx, void*
                                                 hipStream_t);                                                        \
     template hipError_t backward_per_channel<IO>(const void*, const void*, void*, void*, void*, double*, int64_t,    \
                                                  int64_t, int64_t, const void*, const void*, const lsq_params&,      \
-                                                 void*, size_t, uint32_t*, int, hipStream_t, size_t*, LaunchNote*); \
+                                                 void*, size_t, int, hipStream_t);                                   \
+    template hipError_t plan_backward_per_channel<IO>(int64_t, int64_t, int64_t, const lsq_params&, bool, LaunchNote&); \
     template size_t bwd_pc_workspace_bytes<IO>(int64_t, int64_t, int64_t);
 // One translation unit per storage type (the Makefile compiles this file four times with -DLSQ_PC_IO=io_f32 ... in
 // parallel: the window kernels' template space takes minutes in one piece); without the macro, all four.

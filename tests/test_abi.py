@@ -9,6 +9,7 @@ import re
 import subprocess
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lsq_hip.h")
@@ -243,3 +244,25 @@ def test_plan_query_answers_without_launching_anything():
     assert kind(E.LSQ_BF16, 64, 2048, 49, aligned=0)[0] == 1                                            # unaligned: element-wise windows
     out = (ctypes.c_int32 * 8)()
     assert lib.lsq_hip_plan_backward_per_channel(E.LSQ_F32, 0, 8, 8, 1, ctypes.byref(p), ctypes.byref(out)) == -1
+
+
+def test_per_channel_ops_reject_buffers_that_are_not_element_aligned():
+    """include/lsq_hip.h: the per-channel forward and backward take element-aligned x / y / grad / dx only (the launch policy
+    plans for nothing else): a misaligned one is LSQ_EINVAL before anything is planned or launched.  Fake addresses, as in the
+    plan test above -- a library without the check would launch kernels on them, so this runs only where no GPU is visible."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("fake buffer addresses: checked on machines without a GPU only")
+    from torchlsq import extension as E
+    lib = E.library()
+    p = E.LsqParams(0, 127, 0, 255, 1, 0, 0, 0, 1.0, 0)
+    ok = 1 << 20
+    for code, esz in ((E.LSQ_F32, 4), (E.LSQ_F64, 8), (E.LSQ_BF16, 2), (E.LSQ_F16, 2)):
+        bad = ok + esz // 2
+        for x, y in ((bad, ok), (ok, bad)):
+            assert lib.lsq_hip_forward_per_channel(code, x, y, 64, 32, 49, ok, ok, ctypes.byref(p), None, None) == -1     # LSQ_EINVAL
+            assert b"element-aligned" in lib.lsq_hip_last_error()
+        for grad, x, dx in ((bad, ok, ok), (ok, bad, ok), (ok, ok, bad)):
+            assert lib.lsq_hip_backward_per_channel(code, grad, x, dx, ok, ok, None, 64, 32, 49, ok, ok, ctypes.byref(p), None,
+                                                    ok, 1 << 30, None) == -1
+            assert b"element-aligned" in lib.lsq_hip_last_error()
