@@ -172,6 +172,50 @@ def _load_cpu_library():
 _load_cpu_library()
 
 
+# The group-wise ops (include/lsq_hip_group.h): a companion library next to liblsq_hip.so, whose ABI (C_ABI above, pinned
+# against include/lsq_hip.h) it leaves as it is.  Loaded like the CPU kernels: the package works without it, the group ops
+# then raise with `group_error_str`.
+_GROUP_LIB = None
+_GROUP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblsq_hip_group.so")
+group_error_str = ""
+GROUP_ABI_VERSION = 1
+C_ABI_GROUP = {
+    "lsq_group_abi_version": (_int, []),
+    "lsq_group_last_error": (ctypes.c_char_p, []),
+    "lsq_group_forward": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _PP, _EP, _vp]),
+    "lsq_group_backward": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _PP, _vp]),
+    "lsq_group_plan": (_int, [_int, _i64, _i64, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+
+
+def _load_group_library():
+    global _GROUP_LIB, group_error_str
+    try:
+        lib = ctypes.CDLL(_GROUP_LIB_PATH)
+        for name, (res, args) in C_ABI_GROUP.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.lsq_group_abi_version() != GROUP_ABI_VERSION:
+            raise OSError("liblsq_hip_group.so has ABI version %d, this package needs %d" %
+                          (lib.lsq_group_abi_version(), GROUP_ABI_VERSION))
+        _GROUP_LIB = lib
+    except (OSError, AttributeError) as e:
+        group_error_str = str(e)
+
+
+_load_group_library()
+
+
+def group_library():
+    """The ctypes handle of liblsq_hip_group.so (raises if it is missing)."""
+    _assert_has_ops()
+    if _GROUP_LIB is None:
+        raise RuntimeError("torchlsq: the group-wise ops need liblsq_hip_group.so, which could not be loaded (build it with "
+                           "`python __graft_entry__.py`): %s" % group_error_str)
+    return _GROUP_LIB
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -32,11 +32,13 @@ from ._hip_host import (_SINGLE_LAUNCH_BWD, _TICKET_SLABS, _TICKETS, _WS_BYTES_P
                         LSQ_COMM_MAX, LSQ_COMM_MIN, LSQ_COMM_SUM,
                         saves_mask, set_single_launch_backward)
 from ._cpu_host import _cpu_meanstd, _cpu_minmax, cpu_backward, cpu_forward, cpu_levels, cpu_sharded_finish  # noqa: F401
+from ._group_host import check_group_args, group_backward, group_forward, group_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str", "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str", "group_error_str",
+                "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
@@ -85,6 +87,13 @@ _lib_def.define("lsq_levels_per_tensor(Tensor x, Tensor scale, Tensor shift, int
                 "int type_min, int type_max, int level_bias) -> Tensor")
 _lib_def.define("lsq_levels_per_channel(Tensor x, Tensor scale, Tensor shift, int axis, int quant_min, "
                 "int quant_max, int type_min, int type_max, int level_bias) -> Tensor")
+#  * `*_per_group`: one scale / shift per run of `group_size` consecutive elements of the last dim (liblsq_hip_group.so,
+#    include/lsq_hip_group.h): by definition the per-channel op on the [x.numel() // G, G] view, axis 0.
+_lib_def.define("lsq_forward_per_group(Tensor x, Tensor scale, Tensor shift, int group_size, " + _TAIL + ") -> Tensor")
+_lib_def.define("lsq_backward_per_group(Tensor grad, Tensor x, Tensor scale, Tensor shift, int group_size, " + _TAIL +
+                ") -> (Tensor, Tensor, Tensor)")
+_lib_def.define("lsq_levels_per_group(Tensor x, Tensor scale, Tensor shift, int group_size, int quant_min, int quant_max, "
+                "int type_min, int type_max, int level_bias) -> Tensor")
 
 
 
@@ -316,6 +325,63 @@ for _op, _nm in (("lsq_backward_per_tensor", "lsq_per_tensor"), ("lsq_backward_p
                  ("lsq_backward_per_tensor_wide", "lsq_per_tensor"),
                  ("lsq_backward_per_channel_wide", "lsq_per_channel")):
     torch.library.register_autograd("torchlsq::" + _op, _no_double_backward(_nm), lib=_lib_def)
+
+
+# -------------------------------------------------------------------------------------------------
+# the group-wise ops (_group_host.py): GPU tensors -> liblsq_hip_group.so, CPU tensors -> liblsq_cpu.so's per-channel
+# kernels on the [numel // G, G] view; shape-only kernels; autograd with the same double-backward refusal
+# -------------------------------------------------------------------------------------------------
+def _impl_fwd_grp(x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode):
+    return group_forward(x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
+
+
+def _impl_bwd_grp(grad, x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode):
+    return group_backward(grad, x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
+
+
+def _impl_levels_grp(x, scale, shift, group_size, qmin, qmax, tmin, tmax, level_bias):
+    return group_forward(x, scale, shift, group_size, qmin, qmax, tmin, tmax, True, 1.0, False, False, False,
+                         levels_bias=level_bias, levels_only=True)
+
+
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_forward_per_group", _impl_fwd_grp)
+    _lib_key.impl("lsq_backward_per_group", _impl_bwd_grp)
+    _lib_key.impl("lsq_levels_per_group", _impl_levels_grp)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_forward_per_group", lib=_lib_def)
+def _fake_fwd_grp(x, scale, shift, group_size, *a):
+    return torch.empty(x.shape, dtype=x.dtype, device=x.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_backward_per_group", lib=_lib_def)
+def _fake_bwd_grp(grad, x, scale, shift, group_size, *a):
+    pd = _param_dtype(x)
+    return (torch.empty(x.shape, dtype=x.dtype, device=x.device), torch.empty(scale.shape, dtype=pd, device=x.device),
+            torch.empty(shift.shape, dtype=pd, device=x.device))
+
+
+@torch.library.register_fake("torchlsq::lsq_levels_per_group", lib=_lib_def)
+def _fake_levels_grp(x, scale, shift, group_size, *a):
+    return torch.empty(x.shape, dtype=torch.int8, device=x.device)
+
+
+def _setup_grp(ctx, inputs, output):
+    x, scale, shift = inputs[:3]
+    ctx.save_for_backward(x, scale, shift)
+    ctx.lsq_scalars = tuple(inputs[3:])  # group_size first
+
+
+def _backward_grp(ctx, grad_out):
+    x, scale, shift = ctx.saved_tensors
+    dx, ds, db = torch.ops.torchlsq.lsq_backward_per_group(grad_out, x, scale, shift, *ctx.lsq_scalars)
+    return (dx, ds, db) + (None,) * 10
+
+
+torch.library.register_autograd("torchlsq::lsq_forward_per_group", _backward_grp, setup_context=_setup_grp, lib=_lib_def)
+torch.library.register_autograd("torchlsq::lsq_backward_per_group", _no_double_backward("lsq_per_group"), lib=_lib_def)
 
 
 # -------------------------------------------------------------------------------------------------

@@ -326,3 +326,107 @@ def lsq_foreach(xs, scales, shifts,
         for i, y in zip(idx, ys):
             out[i] = y
     return out
+
+
+class _LSQGroupOnDevice(torch.autograd.Function):
+    """`lsq_per_group` for GPU tensors straight to liblsq_hip_group.so (as _LSQOnDevice does for `lsq`): saves
+    {input, scale, shift}, or -- eval mode -- the forward's one-byte inside mask, whose backward is lsq_hip_backward_from_mask."""
+
+    @staticmethod
+    def forward(ctx, x, scale, shift, cfg):
+        (group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode) = cfg
+        masked = _E.saves_mask(eval_mode, init_mode, x.requires_grad, True)
+        y = _E.group_forward(x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode,
+                             want_mask=masked)
+        ctx.masked = masked
+        if masked:
+            y, mask = y
+            ctx.save_for_backward(mask, scale, shift)
+        else:
+            ctx.save_for_backward(x, scale, shift)
+        ctx.cfg = cfg
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, scale, shift = ctx.saved_tensors
+        if ctx.masked:      # x is the inside mask here; d_scale = d_shift = 0 (lsq_kernel.h:142-144)
+            return _E.hip_backward_from_mask(grad_out, x), torch.zeros_like(scale), torch.zeros_like(shift), None
+        dx, ds, db = _E.group_backward(grad_out, x, scale, shift, *ctx.cfg)
+        return dx, ds, db, None
+
+
+def _group_params(x, scale, shift, group_size):
+    """the front-op rule (lsq.cpp:124-126) for groups: a parameter of numel 1 is repeated once per group (differentiably)"""
+    groups = x.numel() // group_size if group_size > 0 else 0
+    if scale.numel() == 1 and groups != 1:
+        scale = scale.reshape(1).repeat(groups)
+    if shift.numel() == 1 and groups != 1:
+        shift = shift.reshape(1).repeat(groups)
+    return scale, shift
+
+
+def lsq_per_group(x: Tensor, scale: Tensor, shift: Tensor, group_size: int,
+                  quant_min: int = 0,
+                  quant_max: int = 255,
+                  type_min: int = None,
+                  type_max: int = None,
+                  use_grad_scaling: bool = True,
+                  grad_scaler: float = 1.,
+                  is_affine: bool = True,
+                  eval_mode: bool = False,
+                  init_mode: bool = False) -> Tensor:
+    """Group-wise LSQ (an addition of this build): one learned `scale` / `shift` per run of `group_size` (G) consecutive
+    elements of the last dimension -- the scheme of low-bit transformer weights (e.g. W4 with G = 128).
+
+    Group j is `x.reshape(-1, G)[j]`; x.shape[-1] must be a multiple of G.  `scale` / `shift` are documented with the shape
+    `x.shape[:-1] + (x.shape[-1] // G,)`, but any shape with x.numel() // G elements is taken (a one-element parameter is
+    repeated), and their gradients come back in their own shapes.  By definition the result -- y, dx, d_scale, d_shift, in
+    every mode -- is that of
+
+        lsq(x.reshape(-1, G), scale.reshape(-1), shift.reshape(-1), ..., axis=0, is_perchannel=True).reshape(x.shape)
+
+    including the per-channel gradient scaler 1 / sqrt(G * quant_max); the other arguments mean what they mean in `lsq`.
+    GPU tensors run the group kernels of liblsq_hip_group.so (one launch each way, no workspace), CPU tensors the
+    per-channel CPU kernels on that view.
+    """
+    _assert_has_ops()
+    if not is_affine:
+        assert quant_min <= 0 <= quant_max, 'quantization range must be covered 0 in symmetric quantization'
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    group_size = int(group_size)
+    scale, shift = _group_params(x, scale, shift, group_size)
+    on_gpu = x.is_cuda and scale.is_cuda and shift.is_cuda
+    if on_gpu and not torch.jit.is_tracing() and not torch.compiler.is_compiling():
+        _E.check_group_args(x, scale, shift, group_size)
+        cfg = (group_size, quant_min, quant_max, type_min, type_max, bool(use_grad_scaling), float(grad_scaler),
+               not is_affine, bool(eval_mode), bool(init_mode))
+        return _LSQGroupOnDevice.apply(x, scale, shift, cfg)
+    return torch.ops.torchlsq.lsq_forward_per_group(x, scale, shift, group_size, quant_min, quant_max, type_min, type_max,
+                                                    bool(use_grad_scaling), float(grad_scaler), not is_affine,
+                                                    bool(eval_mode), bool(init_mode))
+
+
+def lsq_levels_per_group(x: Tensor, scale: Tensor, shift: Tensor, group_size: int,
+                         quant_min: int = 0,
+                         quant_max: int = 255,
+                         type_min: int = None,
+                         type_max: int = None,
+                         dtype=torch.quint8) -> Tensor:
+    """The integer levels x_q of `lsq_per_group`'s forward, one byte per element in x's shape: torch.uint8 for
+    dtype=torch.quint8, torch.int8 for torch.qint8 (torch has no per-group quantized tensor; the constants that go with
+    them are s = max(|scale|, eps) and zp = round(clamp(-shift * (1 / s), type_min, type_max)) per group, so that
+    (x_q - zp) * s is `lsq_per_group`'s output -- bit for bit for float32 x).  One pass, one byte written per element."""
+    _assert_has_ops()
+    assert dtype in (torch.quint8, torch.qint8), "dtype must be torch.quint8 or torch.qint8"
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    lo, hi = (0, 255) if dtype == torch.quint8 else (-128, 127)
+    assert lo <= quant_min <= quant_max <= hi, "the quantized range must fit the quantized type"
+    group_size = int(group_size)
+    x, scale, shift = x.detach(), scale.detach(), shift.detach()
+    scale, shift = _group_params(x, scale, shift, group_size)
+    levels = torch.ops.torchlsq.lsq_levels_per_group(x, scale, shift, group_size, quant_min, quant_max, type_min, type_max, 0)
+    return levels.view(torch.uint8) if dtype == torch.quint8 else levels

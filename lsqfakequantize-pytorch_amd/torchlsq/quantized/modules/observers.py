@@ -159,6 +159,11 @@ class LSQFakeQuantizer(ObserverBase):
         avoid_torch_overflow: use 7-bit default ranges / reduce_range in the observer.
         debug_mode: forward is the identity.
         sync, process_group, sync_grads (this build): see `enable_rank_sync`; `process_group` alone implies sync=True.
+        group_size (this build): group-wise scales for weights -- one scale per run of `group_size` consecutive input
+            features (`torchlsq.functional.lsq_per_group`).  The weight is viewed as [out, numel / out] (conv weights
+            flattened), its row length must be a multiple of group_size, and `scale` / `shift` are [out, row / group_size].
+            Needs otype='weight', a per-channel qscheme (ch_axis 0) and learn_params=True; None = per-channel / per-tensor as
+            without it.
     """
     init_modes = ('learnable', 'observer')
     fuse_observer_tail = True     # observer-driven init batches on the GPU: one launch after the statistics pass
@@ -168,6 +173,7 @@ class LSQFakeQuantizer(ObserverBase):
     _ddp_numel = None       # sync_grads='ddp': the shard size the equal-shards shortcut was first used with
     _ddp_warned = False
     _group_ref = _GroupRef(None)
+    group_size = None       # group-wise weight scales (class default: modules pickled by an earlier build have none)
 
     @staticmethod
     def sign(x):
@@ -182,8 +188,21 @@ class LSQFakeQuantizer(ObserverBase):
                  init_batches=1000, init_mode='observer',
                  use_grad_scaling=True, grad_scaler=1.,
                  avoid_torch_overflow=True, debug_mode=False, sync=False, process_group=None, sync_grads='sum',
-                 **observer_kwargs):
+                 group_size=None, **observer_kwargs):
         super().__init__(dtype)
+        if group_size is not None:
+            # no observer produces per-group qparams: groups exist for learned weight scales only
+            if otype != 'weight':
+                raise ValueError("group_size is supported for otype='weight' only")
+            if not learn_params:
+                raise ValueError("group_size needs learn_params=True (no observer produces per-group qparams)")
+            if qscheme not in _PER_CHANNEL:
+                raise ValueError("group_size needs a per-channel qscheme")
+            if ch_axis not in (None, 0):
+                raise ValueError("group_size: the output channels must be dim 0 of the weight (ch_axis=0)")
+            if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+                raise ValueError("group_size must be a positive integer, got %r" % (group_size,))
+        self.group_size = group_size
         assert init_mode in self.init_modes, f'only following modes available: {("learnable", "observer")}'
         assert otype in OTYPES, f'otype must be on of {tuple(OTYPES.keys())}, but {otype} is given'
         assert self.dtype in TYPES_RANGE_MAPPING, \
@@ -430,6 +449,8 @@ class LSQFakeQuantizer(ObserverBase):
     # ---- parameters ------------------------------------------------------------------------------
     def _init_weights(self, x: Tensor, _init_device=torch.device('cpu')) -> None:
         """Create `scale` / `shift` from an example input (reference :314-342)."""
+        if self.group_size is not None and x is not None:
+            return self._init_group_weights(x)
         self._initialized = True
         n = x.shape[self.ch_axis] if (self.is_perchannel and x is not None) else 1
         device = x.device if x is not None else _init_device
@@ -452,6 +473,36 @@ class LSQFakeQuantizer(ObserverBase):
                 spread = torch.max(torch.abs(mu - 3 * sigma), torch.abs(mu + 3 * sigma))
                 scale = (spread.to(device) / 2 ** bits).to(torch.float32)
         shift = torch.full((n,), self.init_shift, dtype=torch.float32).to(device)
+        self.scale = torch.nn.Parameter(scale)
+        self.shift = torch.nn.Parameter(shift)
+        learn = bool(self._h['learning'])
+        self.scale.requires_grad = learn
+        self.shift.requires_grad = learn and self.is_affine
+
+    def _group_rows(self, x):
+        """(out, row): the [out, numel / out] view of a weight quantized in groups along its rows"""
+        out = x.shape[0] if x.dim() > 0 else 1
+        row = x.numel() // out if out > 0 else 0
+        if x.dim() < 1 or row % self.group_size != 0:
+            raise ValueError("group_size %d does not divide the weight's row length %d (weight shape %s viewed as [out, "
+                             "numel / out])" % (self.group_size, row, tuple(x.shape)))
+        return out, row
+
+    def _init_group_weights(self, x: Tensor) -> None:
+        """`_init_weights` for group-wise weight scales: the 3-sigma rule per group of the [numel / G, G] view"""
+        out, row = self._group_rows(x)
+        G = self.group_size
+        self._initialized = True
+        bits = ceil(log(self.quant_max - self.quant_min) / log(2)) - 1
+        w = x.detach().reshape(-1, G)
+        with torch.no_grad():
+            if w.is_cuda and w.numel() > 0:
+                mu, sigma = torch.ops.torchlsq.lsq_meanstd_per_channel(w, 0)
+            else:
+                mu, sigma = torch.mean(w, [1]), torch.std(w, [1])
+            spread = torch.max(torch.abs(mu - 3 * sigma), torch.abs(mu + 3 * sigma))
+            scale = (spread / 2 ** bits).to(torch.float32).reshape(out, row // G)
+        shift = torch.full((out, row // G), self.init_shift, dtype=torch.float32, device=x.device)
         self.scale = torch.nn.Parameter(scale)
         self.shift = torch.nn.Parameter(shift)
         learn = bool(self._h['learning'])
@@ -515,8 +566,33 @@ class LSQFakeQuantizer(ObserverBase):
         from torchlsq.functional import lsq_quantize
         assert self._initialized and self.scale is not None, "run the module on at least one batch before quantize()"
         tmin, tmax = TYPES_RANGE_MAPPING[self.dtype]['range']
+        if self.group_size is not None:
+            return self._quantize_groups(x, tmin, tmax)
         return lsq_quantize(x, self.scale, self.shift, quant_min=self.quant_min, quant_max=self.quant_max, type_min=tmin,
                             type_max=tmax, axis=self.ch_axis, is_perchannel=self.is_perchannel, dtype=self.dtype)
+
+    def _quantize_groups(self, x, tmin, tmax):
+        """quantize() of a group-wise quantizer: torch has no per-group quantized tensor, so (levels, scale, zero_point) --
+        int8 levels in x's shape and the [out, row / G] constants the kernels use, s = max(|scale|, eps) and
+        zp = round(clamp(-shift * (1 / s), type range)) (int64): (levels - zp) * s, each group's constants repeated over its
+        G elements, is the module's output, bit for bit for float32 weights."""
+        from torchlsq.functional import lsq_levels_per_group
+        out, row = self._group_rows(x)
+        levels = lsq_levels_per_group(x.reshape(out, row), self.scale, self.shift, self.group_size, quant_min=self.quant_min,
+                                      quant_max=self.quant_max, type_min=tmin, type_max=tmax, dtype=self.dtype)
+        with torch.no_grad():
+            s = self.scale.detach().abs().clamp_min(torch.finfo(self.scale.dtype).eps)
+            zp = torch.fmin(torch.full_like(s, tmax), torch.fmax(torch.full_like(s, tmin), -self.shift.detach() * (1.0 / s))).round()
+        return levels.reshape(x.shape), s, zp.to(torch.int64)
+
+    def _forward_groups(self, x, full_lsq, tmin, tmax):
+        """the LSQ call of a group-wise weight quantizer: `lsq_per_group` on the [out, numel / out] view"""
+        from torchlsq.functional import lsq_per_group
+        out, row = self._group_rows(x)
+        y = lsq_per_group(x.reshape(out, row), self.scale, self.shift, self.group_size, quant_min=self.quant_min,
+                          quant_max=self.quant_max, type_min=tmin, type_max=tmax, use_grad_scaling=self.use_grad_scaling,
+                          grad_scaler=self.grad_scaler, is_affine=self.is_affine, eval_mode=(not full_lsq))
+        return y.reshape(x.shape)
 
     # ---- the caller of the hot path ------------------------------------------------------------
     _prefetched = None      # (weight, its version, scale's, shift's, fake-quantized value) stashed by LSQWeightGroup.prequantize()
@@ -574,6 +650,8 @@ class LSQFakeQuantizer(ObserverBase):
             # before the first one's backward changes what the reference's eval backward sees (it recomputes the mask
             # from the saved x and the then-current parameters, lsq_autograd.cpp:46-73): keep that behaviour there
             # (save x); once the parameters are only changed by the optimizer, the one-byte saved mask is equivalent.
+            if self.group_size is not None:
+                return self._forward_groups(x, full_lsq, tmin, tmax)
             if sync_ws > 1 and full_lsq:
                 # the input is this rank's shard of the batch: one all-reduce per backward, scaler from the global count
                 from torchlsq.distributed import COLLECTIVE, lsq_sharded

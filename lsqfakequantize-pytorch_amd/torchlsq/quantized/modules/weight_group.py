@@ -14,7 +14,7 @@ node instead of dozens.
 
 Only quantizers in their steady state take part (created, learning or plain fake-quant without observer, per-channel or
 per-tensor symmetric/affine as configured, on the GPU); everything else -- the creating call, observer-driven calls,
-disabled fake-quant, debug mode, CPU -- runs through the quantizer's own forward as before.
+disabled fake-quant, debug mode, CPU, group-wise scales (`group_size`) -- runs through the quantizer's own forward as before.
 """
 import torch
 
@@ -66,6 +66,8 @@ class LSQWeightGroup:
         """the call `q(w)` would be a plain per-channel `lsq` call with fixed parameters: no creation, no observer, no init phase"""
         if q.debug_mode or not q._initialized or not q.is_perchannel or not w.is_cuda:
             return False
+        if q.group_size is not None:
+            return False        # group-wise scales: the quantizer's own call (lsq_per_group), not the per-channel fused launch
         if q._stamp != q._buffer_stamp():
             q._refresh_host_state()
         h = q._h
