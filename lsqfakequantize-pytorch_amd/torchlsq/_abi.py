@@ -216,6 +216,59 @@ def group_library():
     return _GROUP_LIB
 
 
+# Many group-wise tensors in one launch each way (include/lsq_hip_group_multi.h): a third library, so that the pinned
+# exports of liblsq_hip_group.so (C_ABI_GROUP above) stay as they are.  Loaded like the group library: the package works
+# without it, the fused group-wise calls then raise with `group_multi_error_str`.
+class LsqGroupItem(ctypes.Structure):
+    """lsq_group_item (include/lsq_hip_group_multi.h): one tensor of a multi-tensor group-wise launch."""
+    _fields_ = [("x", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("y", ctypes.c_void_p), ("dx", ctypes.c_void_p),
+                ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("ds", ctypes.c_void_p), ("db", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("group_size", ctypes.c_int64)]
+
+
+_GROUP_MULTI_LIB = None
+_GROUP_MULTI_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblsq_hip_group_multi.so")
+group_multi_error_str = ""
+GROUP_MULTI_ABI_VERSION = 1
+GROUP_MULTI_ITEMS = 28          # LSQ_GROUP_MULTI_ITEMS: items per launch
+_GIP = ctypes.POINTER(LsqGroupItem)
+C_ABI_GROUP_MULTI = {
+    "lsq_group_multi_abi_version": (_int, []),
+    "lsq_group_multi_last_error": (ctypes.c_char_p, []),
+    "lsq_group_multi_forward": (_int, [_int, _GIP, ctypes.c_int32, _PP, _vp]),
+    "lsq_group_multi_backward": (_int, [_int, _GIP, ctypes.c_int32, _PP, _vp]),
+    "lsq_group_multi_plan": (_int, [_int, _GIP, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+}
+
+
+def _load_group_multi_library():
+    global _GROUP_MULTI_LIB, group_multi_error_str
+    try:
+        lib = ctypes.CDLL(_GROUP_MULTI_LIB_PATH)
+        for name, (res, args) in C_ABI_GROUP_MULTI.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.lsq_group_multi_abi_version() != GROUP_MULTI_ABI_VERSION:
+            raise OSError("liblsq_hip_group_multi.so has ABI version %d, this package needs %d" %
+                          (lib.lsq_group_multi_abi_version(), GROUP_MULTI_ABI_VERSION))
+        _GROUP_MULTI_LIB = lib
+    except (OSError, AttributeError) as e:
+        group_multi_error_str = str(e)
+
+
+_load_group_multi_library()
+
+
+def group_multi_library():
+    """The ctypes handle of liblsq_hip_group_multi.so (raises if it is missing)."""
+    _assert_has_ops()
+    if _GROUP_MULTI_LIB is None:
+        raise RuntimeError("torchlsq: the fused group-wise calls need liblsq_hip_group_multi.so, which could not be loaded "
+                           "(build it with `python __graft_entry__.py`): %s" % group_multi_error_str)
+    return _GROUP_MULTI_LIB
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

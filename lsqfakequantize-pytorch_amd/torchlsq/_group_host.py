@@ -2,6 +2,8 @@
 
 GPU tensors go to liblsq_hip_group.so (include/lsq_hip_group.h) with one ctypes call per op; CPU tensors go to the
 per-channel kernels of liblsq_cpu.so on the [n / G, G] view (axis 0), which is what a group IS, value for value.
+`group_forward_multi` / `group_backward_multi`: many GPU tensors of one dtype in one ctypes call each way
+(liblsq_hip_group_multi.so, include/lsq_hip_group_multi.h), with the same checks and layout rules.
 Checks and layout rules as in _hip_host.py: the flat stream needs x in row-major order (a non-contiguous x is made
 contiguous first, like a non-dense per-channel input); element-aligned views (x[1:]) run in place.
 """
@@ -10,7 +12,7 @@ import ctypes
 import torch
 
 from . import _abi
-from ._abi import _DTYPE_CODE, _assert_has_ops, group_library
+from ._abi import _DTYPE_CODE, LsqGroupItem, _assert_has_ops, group_library, group_multi_library
 from ._hip_host import (_aux_output, _check, _on_device, _param_dtype, _params, _require_gpu, _stream_of,
                         check_backward_dtypes, check_forward_dtypes)
 from ._cpu_host import cpu_backward, cpu_forward, cpu_levels
@@ -113,3 +115,92 @@ def group_plan(dtype, n, group_size):
         _group_status(rc, "lsq_group_plan")
     return dict(fwd_grid=out[0], bwd_grid=out[1], block=out[2], form="packet" if out[3] else "element", lanes_per_group=out[4],
                 reduction="butterfly" if out[5] == 1 else "scan", vec=out[6])
+
+
+def _multi_status(rc, what):
+    if rc != 0:
+        raise RuntimeError("%s failed (%d): %s" % (what, rc,
+                                                   _abi._GROUP_MULTI_LIB.lsq_group_multi_last_error().decode("utf-8", "replace")))
+
+
+def _multi_common(what, xs, scales, shifts, group_sizes):
+    """checks of the single calls for every tensor; (device index, dtype code)"""
+    n = len(xs)
+    _check(n > 0 and len(scales) == n and len(shifts) == n and len(group_sizes) == n,
+           "%s: xs, scales, shifts and group sizes must be non-empty lists of the same length" % what)
+    x0 = xs[0]
+    for x, sc, sh, G in zip(xs, scales, shifts, group_sizes):
+        check_forward_dtypes(x, sc, sh)
+        check_group_args(x, sc, sh, G)
+        _check(x.dtype == x0.dtype, "%s: every tensor of one call must have the same dtype" % what)
+        _require_gpu(what, x0, x, sc, sh)
+    return x0.device.index, _DTYPE_CODE[x0.dtype]
+
+
+def group_forward_multi(xs, scales, shifts, group_sizes, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode):
+    """[y_i] = [group_forward(x_i, ...)]: one ctypes call, one launch per class of reduction and per 28 tensors"""
+    _assert_has_ops()
+    lib = group_multi_library()
+    idx, code = _multi_common("lsq_group_multi_forward", xs, scales, shifts, group_sizes)
+    _, pref = _params(qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
+    items = (LsqGroupItem * len(xs))()
+    keep, ys = [], []
+    for k, (x, sc, sh, G) in enumerate(zip(xs, scales, shifts, group_sizes)):
+        xd, scc, shc = x.contiguous(), sc.contiguous(), sh.contiguous()
+        y = torch.empty_like(xd)
+        keep += [xd, scc, shc]
+        ys.append(y)
+        it = items[k]
+        it.x, it.y, it.scale, it.shift = xd.data_ptr(), y.data_ptr(), scc.data_ptr(), shc.data_ptr()
+        it.n, it.group_size = xd.numel(), G
+    rc = _on_device(idx, lib.lsq_group_multi_forward, code, items, len(xs), pref, _stream_of(idx))
+    if rc:
+        _multi_status(rc, "lsq_group_multi_forward")
+    return ys
+
+
+def group_backward_multi(grads, xs, scales, shifts, group_sizes, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode):
+    """[(dx_i, d_scale_i, d_shift_i)] = [group_backward(grad_i, x_i, ...)]: one ctypes call; the parameter gradients come
+    back in the parameters' shapes"""
+    _assert_has_ops()
+    lib = group_multi_library()
+    idx, code = _multi_common("lsq_group_multi_backward", xs, scales, shifts, group_sizes)
+    _check(len(grads) == len(xs), "lsq_group_multi_backward: one gradient per tensor")
+    _, pref = _params(qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
+    items = (LsqGroupItem * len(xs))()
+    keep, outs = [], []
+    for k, (g, x, sc, sh, G) in enumerate(zip(grads, xs, scales, shifts, group_sizes)):
+        check_backward_dtypes(g, x, sc, sh)
+        _require_gpu("lsq_group_multi_backward", x, g)
+        xd = x.contiguous()
+        gd = g.contiguous() if g.shape == x.shape else g.reshape(x.shape).contiguous()
+        scc, shc = sc.contiguous(), sh.contiguous()
+        dx = torch.empty_like(xd)
+        pd = _param_dtype(x)
+        ds = torch.empty(sc.shape, dtype=pd, device=x.device)
+        db = torch.empty(sh.shape, dtype=pd, device=x.device)
+        keep += [xd, gd, scc, shc]
+        outs.append((dx, ds, db))
+        it = items[k]
+        it.x, it.grad, it.dx, it.scale, it.shift = xd.data_ptr(), gd.data_ptr(), dx.data_ptr(), scc.data_ptr(), shc.data_ptr()
+        it.ds, it.db, it.n, it.group_size = ds.data_ptr(), db.data_ptr(), xd.numel(), G
+    rc = _on_device(idx, lib.lsq_group_multi_backward, code, items, len(xs), pref, _stream_of(idx))
+    if rc:
+        _multi_status(rc, "lsq_group_multi_backward")
+    return outs
+
+
+def group_multi_plan(dtype, sizes, group_sizes):
+    """How liblsq_hip_group_multi.so launches tensors of `sizes` elements with `group_sizes` -- host only, nothing is
+    launched (lsq_group_multi_plan): (per tensor (launch index, forward workgroups, backward workgroups), launches)"""
+    lib = group_multi_library()
+    n = len(sizes)
+    items = (LsqGroupItem * max(n, 1))()
+    for k, (m, G) in enumerate(zip(sizes, group_sizes)):
+        items[k].n, items[k].group_size = int(m), int(G)
+    out = (ctypes.c_int32 * (3 * max(n, 1)))()
+    launches = ctypes.c_int32(0)
+    rc = lib.lsq_group_multi_plan(_DTYPE_CODE[dtype], items, n, out, ctypes.byref(launches))
+    if rc:
+        _multi_status(rc, "lsq_group_multi_plan")
+    return [(out[3 * k], out[3 * k + 1], out[3 * k + 2]) for k in range(n)], launches.value

@@ -32,13 +32,14 @@ from ._hip_host import (_SINGLE_LAUNCH_BWD, _TICKET_SLABS, _TICKETS, _WS_BYTES_P
                         LSQ_COMM_MAX, LSQ_COMM_MIN, LSQ_COMM_SUM,
                         saves_mask, set_single_launch_backward)
 from ._cpu_host import _cpu_meanstd, _cpu_minmax, cpu_backward, cpu_forward, cpu_levels, cpu_sharded_finish  # noqa: F401
-from ._group_host import check_group_args, group_backward, group_forward, group_plan  # noqa: F401
+from ._group_host import (check_group_args, group_backward, group_backward_multi, group_forward,  # noqa: F401
+                          group_forward_multi, group_multi_plan, group_plan)
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str", "group_error_str",
-                "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_GROUP_MULTI_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str",
+                "group_error_str", "group_multi_error_str", "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 

@@ -430,3 +430,99 @@ def lsq_levels_per_group(x: Tensor, scale: Tensor, shift: Tensor, group_size: in
     scale, shift = _group_params(x, scale, shift, group_size)
     levels = torch.ops.torchlsq.lsq_levels_per_group(x, scale, shift, group_size, quant_min, quant_max, type_min, type_max, 0)
     return levels.view(torch.uint8) if dtype == torch.quint8 else levels
+
+
+class _LSQGroupForeach(torch.autograd.Function):
+    """N group-wise quantizers of one dtype as ONE autograd node over the multi-tensor group kernels
+    (liblsq_hip_group_multi.so): one launch per reduction class and per 28 tensors each way instead of N.  Every tensor is
+    walked by the workgroups of its own single call, so outputs and gradients carry the same bits as N `lsq_per_group`
+    calls.  Saves {x_i, scale_i, shift_i}, as _LSQForeach does."""
+
+    @staticmethod
+    def forward(ctx, cfg, n, *tensors):
+        xs, scales, shifts = tensors[:n], tensors[n:2 * n], tensors[2 * n:]
+        (group_sizes, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode) = cfg
+        ys = _E.group_forward_multi(xs, scales, shifts, group_sizes, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode,
+                                    init_mode)
+        ctx.save_for_backward(*tensors)
+        ctx.cfg, ctx.n = cfg, n
+        ctx.set_materialize_grads(False)        # an unused output arrives as None in backward, not as a zero tensor
+        return tuple(ys)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_outs):
+        n = ctx.n
+        tensors = ctx.saved_tensors
+        xs, scales, shifts = tensors[:n], tensors[n:2 * n], tensors[2 * n:]
+        (group_sizes, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode) = ctx.cfg
+        # an output nobody used gets no gradients, as in _LSQForeach (with init_mode a zero-filled stand-in would invent
+        # d_scale / d_shift for it)
+        live = [i for i in range(n) if grad_outs[i] is not None]
+        dxs, dss, dbs = [None] * n, [None] * n, [None] * n
+        if live:
+            outs = _E.group_backward_multi([grad_outs[i] for i in live], [xs[i] for i in live], [scales[i] for i in live],
+                                           [shifts[i] for i in live], [group_sizes[i] for i in live], qmin, qmax, tmin, tmax,
+                                           use_gs, gs, sym, eval_mode, init_mode)
+            for i, o in zip(live, outs):
+                dxs[i], dss[i], dbs[i] = o
+        return (None, None) + tuple(dxs) + tuple(dss) + tuple(dbs)
+
+
+def lsq_foreach_per_group(xs, scales, shifts, group_size,
+                          quant_min: int = 0,
+                          quant_max: int = 255,
+                          type_min: int = None,
+                          type_max: int = None,
+                          use_grad_scaling: bool = True,
+                          grad_scaler: float = 1.,
+                          is_affine: bool = True,
+                          eval_mode: bool = False,
+                          init_mode: bool = False):
+    """`lsq_per_group(x_i, scale_i, shift_i, G_i, ...)` for every i, horizontally fused (an addition of this build).
+
+    The group-wise quantizers of many tensors -- typically all weights of a QAT model with W4 g128-style scales, most of
+    them too small to fill the GPU on their own -- run in one launch each way per reduction class and per 28 tensors:
+    one launch each way in the common case of one G that is a multiple of the 16-byte packet.  `group_size` is one int or
+    one per tensor; all other arguments are shared and mean what they mean in `lsq_per_group` (a one-element parameter is
+    repeated once per group, gradients come back in the parameters' own shapes).  Returns the list of outputs; outputs
+    and gradients are bit-identical to N separate `lsq_per_group` calls.  CPU tensors, empty tensors, calls under tracing
+    or torch.compile, and a dtype with a single GPU tensor go through `lsq_per_group` one by one.
+    """
+    _assert_has_ops()
+    n = len(xs)
+    assert len(scales) == n and len(shifts) == n, "xs, scales and shifts must have the same length"
+    if not is_affine:
+        assert quant_min <= 0 <= quant_max, 'quantization range must be covered 0 in symmetric quantization'
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    sizes = [int(group_size)] * n if isinstance(group_size, int) else [int(g) for g in group_size]
+    assert len(sizes) == n, "group_size must be one int or one per tensor"
+    fusable = not torch.jit.is_tracing() and not torch.compiler.is_compiling()
+    out = [None] * n
+    classes = {}
+    for i in range(n):
+        x, sc, sh = xs[i], scales[i], shifts[i]
+        if fusable and x.is_cuda and sc.is_cuda and sh.is_cuda and x.numel() > 0:
+            classes.setdefault((x.device, x.dtype), []).append(i)
+        else:
+            out[i] = lsq_per_group(x, sc, sh, sizes[i], quant_min, quant_max, type_min, type_max, use_grad_scaling,
+                                   grad_scaler, is_affine, eval_mode, init_mode)
+    for idx in classes.values():
+        if len(idx) == 1:       # nothing to fuse
+            i = idx[0]
+            out[i] = lsq_per_group(xs[i], scales[i], shifts[i], sizes[i], quant_min, quant_max, type_min, type_max,
+                                   use_grad_scaling, grad_scaler, is_affine, eval_mode, init_mode)
+            continue
+        sc_l, sh_l = [], []
+        for i in idx:
+            sc, sh = _group_params(xs[i], scales[i], shifts[i], sizes[i])
+            _E.check_group_args(xs[i], sc, sh, sizes[i])
+            sc_l.append(sc)
+            sh_l.append(sh)
+        cfg = (tuple(sizes[i] for i in idx), quant_min, quant_max, type_min, type_max, bool(use_grad_scaling),
+               float(grad_scaler), not is_affine, bool(eval_mode), bool(init_mode))
+        ys = _LSQGroupForeach.apply(cfg, len(idx), *[xs[i] for i in idx], *sc_l, *sh_l)
+        for i, y in zip(idx, ys):
+            out[i] = y
+    return out

@@ -14,11 +14,14 @@ node instead of dozens.
 
 Only quantizers in their steady state take part (created, learning or plain fake-quant without observer, per-channel or
 per-tensor symmetric/affine as configured, on the GPU); everything else -- the creating call, observer-driven calls,
-disabled fake-quant, debug mode, CPU, group-wise scales (`group_size`) -- runs through the quantizer's own forward as before.
+disabled fake-quant, debug mode, CPU -- runs through the quantizer's own forward as before.  Group-wise scales
+(`group_size`) take part only with `LSQWeightGroup(model, group_wise=True)`: their steady-state quantizers are then fused
+as well (`torchlsq.functional.lsq_foreach_per_group`, G may differ from layer to layer), counted in `last_fused_groups`;
+by default they run their own `lsq_per_group` calls.
 """
 import torch
 
-from torchlsq.functional import lsq_foreach
+from torchlsq.functional import lsq_foreach, lsq_foreach_per_group
 from .observers import LSQFakeQuantizer, TYPES_RANGE_MAPPING
 
 
@@ -34,14 +37,16 @@ def _qat_weight_layers(model):
 
 
 class LSQWeightGroup:
-    def __init__(self, model, register_hook=True):
+    def __init__(self, model, register_hook=True, group_wise=False):
         self.pairs = _qat_weight_layers(model)
+        self.group_wise = bool(group_wise)      # also fuse the group-wise (group_size) quantizers
         self.handle = model.register_forward_pre_hook(self._pre_hook) if register_hook else None
         # results a layer did not pick up (a branch that did not run, an exception mid-forward) are dropped when the model's
         # forward ends, whatever way it ends: a stashed non-leaf tensor would otherwise keep the whole fused graph alive, make
         # copy.deepcopy(model) raise and travel with torch.save(model)
         self.post_handle = model.register_forward_hook(self._post_hook, always_call=True) if register_hook else None
-        self.last_fused = 0          # tensors that went through the fused call at the last prequantize()
+        self.last_fused = 0          # per-channel / per-tensor weights that went through the fused call at the last prequantize()
+        self.last_fused_groups = 0   # group-wise weights that did (group_wise=True)
 
     def clear(self):
         for _, q in self.pairs:
@@ -61,12 +66,12 @@ class LSQWeightGroup:
     def _post_hook(self, module, args, output):
         self.clear()
 
-    @staticmethod
-    def _steady(q, w):
-        """the call `q(w)` would be a plain per-channel `lsq` call with fixed parameters: no creation, no observer, no init phase"""
+    def _steady(self, q, w):
+        """the call `q(w)` would be a plain per-channel `lsq` call (group_wise: or `lsq_per_group` call) with fixed
+        parameters: no creation, no observer, no init phase"""
         if q.debug_mode or not q._initialized or not q.is_perchannel or not w.is_cuda:
             return False
-        if q.group_size is not None:
+        if q.group_size is not None and not self.group_wise:
             return False        # group-wise scales: the quantizer's own call (lsq_per_group), not the per-channel fused launch
         if q._stamp != q._buffer_stamp():
             q._refresh_host_state()
@@ -88,14 +93,27 @@ class LSQWeightGroup:
             full_lsq = bool(q._h['learning'])
             q.scale.requires_grad = full_lsq
             q.shift.requires_grad = full_lsq and q.is_affine
-            key = (w.device, w.dtype, q.quant_min, q.quant_max, q.dtype, q.use_grad_scaling, q.grad_scaler, q.is_affine, full_lsq)
+            key = (w.device, w.dtype, q.quant_min, q.quant_max, q.dtype, q.use_grad_scaling, q.grad_scaler, q.is_affine, full_lsq,
+                   q.group_size is not None)
             by_cfg.setdefault(key, []).append((q, w))
         self.last_fused = 0
+        self.last_fused_groups = 0
         for key, items in by_cfg.items():
             if len(items) < 2:
                 continue
-            (_, _, qmin, qmax, qdtype, use_gs, gs, affine, full_lsq) = key
+            (_, _, qmin, qmax, qdtype, use_gs, gs, affine, full_lsq, grouped) = key
             tmin, tmax = TYPES_RANGE_MAPPING[qdtype]['range']
+            if grouped:
+                # the [out, numel / out] view of each weight, as LSQFakeQuantizer._forward_groups; G may differ per layer
+                views = [w.reshape(q._group_rows(w)) for q, w in items]
+                ys = lsq_foreach_per_group(views, [q.scale for q, _ in items], [q.shift for q, _ in items],
+                                           [q.group_size for q, _ in items], quant_min=qmin, quant_max=qmax, type_min=tmin,
+                                           type_max=tmax, use_grad_scaling=use_gs, grad_scaler=gs, is_affine=affine,
+                                           eval_mode=(not full_lsq), init_mode=False)
+                for (q, w), y in zip(items, ys):
+                    q._prefetched = (w, w._version, q.scale._version, q.shift._version, y.reshape(w.shape))
+                self.last_fused_groups += len(items)
+                continue
             ys = lsq_foreach([w for _, w in items], [q.scale for q, _ in items], [q.shift for q, _ in items], quant_min=qmin,
                              quant_max=qmax, type_min=tmin, type_max=tmax, axis=[q.ch_axis for q, _ in items],
                              use_grad_scaling=use_gs, grad_scaler=gs, is_affine=affine, eval_mode=(not full_lsq), init_mode=False)
@@ -104,4 +122,4 @@ class LSQWeightGroup:
                 # (optimizer.step(), w.mul_(), ...) between prequantize() and the layer's own call
                 q._prefetched = (w, w._version, q.scale._version, q.shift._version, y)
             self.last_fused += len(items)
-        return self.last_fused
+        return self.last_fused + self.last_fused_groups
