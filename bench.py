@@ -28,16 +28,26 @@ time = max over ranks of the K-step wall time bracketed by barrier + synchronize
 float64 storage: float64), at most 64 MB in all: outputs too large for that are sampled at fixed, seeded positions.  The
 inputs are seeded (torchlsq.synth), so two builds run with the same arguments can be compared output for output.
 
-Extra objects on the same line:
-  roofline      HBM roofline of the dominant kernel (the fused backward: read grad + read x + write dx = 3 storage
-                elements per element), from its average launch duration measured live with HIP events on the launch
-                stream inside the timed region.  `fwd` carries the same for the forward kernel and `step_frac` the
-                fwd+bwd figure BASELINE.md quotes the 70 % target on.  `traffic` = HBM bytes per backward launch from
-                the FETCH_SIZE / WRITE_SIZE counters: measured by this run (two `rocprofv3 --pmc` child passes of this
-                same command, `--measure-traffic`, default at N = 1) or carried from profiles/ -- `traffic_source` says which.
+A plain run does only what that line needs: it sets up, warms up, times the K steps, writes --dump-outputs if asked and
+prints the line.  Its `roofline` object is the HBM roofline of the dominant kernel (the fused backward: read grad, read x,
+write dx = 3 storage elements per element), from its average launch duration measured live with HIP events on the
+launch stream inside the timed region.  `fwd` carries the same for the forward kernel and `step_frac` the fwd+bwd figure
+BASELINE.md quotes the 70 % target on.  `traffic` = HBM bytes per backward launch from the FETCH_SIZE / WRITE_SIZE
+counters, in a plain run carried from profiles/ -- `traffic_source` says so.  At N > 1 rank 0's shard step alone
+(`per_gpu_efficiency`) still runs between the warm-up and the timed steps, as it always has.
+
+`--full` adds everything else the benchmark measures or checks, each part after the timed region, on the same line:
+  roofline.traffic  measured by this run: two `rocprofv3 --pmc` child passes of this same command (N = 1; `--no-measure-traffic`
+                    keeps the carried figure, `--measure-traffic` asks for the passes in a plain run too)
+  roofline.same_box_reference_kernels  ATen's add / copy rates on the same buffers (`--no-yardstick` skips them)
   cpu_baseline  the reference's own CPU csrc (oracle/_ref/libtorchlsq_ref_ops.so, kind "reference") -- or, if that
                 build is absent, the C restatement (kind "port") -- timed on this box's host cores on the workload's
                 full shape, at all cores and at 1 thread, rank 0 at N = 1 only.  A reported baseline, not the target.
+                (`--no-cpu-baseline` skips it)
+  secondary, roofline.sustained, config.python_ctypes_host_layer, strong_scaled  the other workloads, the headline for >= 1 s,
+                the Python / ctypes host layer, BASELINE config 4 next to an N > 1 headline (`--no-secondary` skips them)
+  config.collective_verified, parity_vs_reference  N > 1 and --assume-peers: the last timed step's reduced sums against the
+                ranks' contributions and against the reference's per-shard digests
 """
 import argparse
 import glob
@@ -112,15 +122,19 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS),
                     help="cfg2 (default; weak-scaled per GPU) | cfg4 (strong: [1024,1024,14,14] split over the ranks) | "
                          "cfg1 | cfg3, cfg5, cfg5_bf16, cfg5_axis0 (per-channel) | tok, vit (+ _bf16): [8192,4096] / [64,197,768], last axis")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures or checks: live PMC traffic, "
+                         "ATen yardsticks, the CPU baseline, the secondary records, the collective's verification "
+                         "(the --no-* options below skip parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--measure-traffic", dest="measure_traffic", action="store_true", default=None,
-                    help="measure roofline.traffic in this run with two rocprofv3 --pmc child passes (default at N = 1)")
+                    help="measure roofline.traffic in this run with two rocprofv3 --pmc child passes (default in a --full run at N = 1)")
     ap.add_argument("--no-measure-traffic", dest="measure_traffic", action="store_false")
     ap.add_argument("--buffers", type=int, default=0,
                     help="input buffer sets the steps rotate through (0 = auto: as many as make the streamed working set exceed "
                          "1 GiB, so that the 256 MB Infinity Cache cannot serve the reads of a small workload; 1 = re-use one set)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default run (cfg2, N = 1) only: skip the secondary records (cfg1, cfg3, cfg5, cfg5_bf16 timed in-process)")
+                    help="--full run only: skip the secondary records (cfg1, cfg3, cfg5, cfg5_bf16 timed in-process)")
     ap.add_argument("--secondary-steps", type=int, default=200, help=argparse.SUPPRESS)
     ap.add_argument("--no-yardstick", action="store_true", help="skip the ATen add / copy rates measured after the timed region")
     ap.add_argument("--host-binding", default="auto", choices=["auto", "native", "ctypes"],
@@ -946,7 +960,7 @@ def run_rank(a):
             D.set_native_collective(a.collective.startswith("native"))
 
         verified = None
-        if (collective or world > 1) and last_reduced[0] is not None:
+        if a.full and (collective or world > 1) and last_reduced[0] is not None:
             try:
                 verified = verify_sharded(last_reduced[0], workload, c, dt, shape, xs[0], gs[0], scale, shift, per_channel, axis, tail,
                                           n_scaler if collective else n_global, ops, fwd_of=(op_fwd_pc if per_channel else op_fwd_pt),
@@ -1012,9 +1026,9 @@ def run_rank(a):
             what = "per-tensor quint8 (qmin,qmax=%d,%d)" % (c["qmin"], c["qmax"])
             opnames = "lsq_forward_per_tensor + lsq_backward_per_tensor"
         traffic, traffic_source = None, "not measured"
-        # default: measure at N = 1 -- unless this process itself runs under a profiler (a nested rocprofv3 is asking for trouble)
+        # --full: measure at N = 1 -- unless this process itself runs under a profiler (a nested rocprofv3 is asking for trouble)
         profiled = any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
-        want_pmc = a.measure_traffic if a.measure_traffic is not None else (world == 1 and not a.graph and not profiled)
+        want_pmc = a.measure_traffic if a.measure_traffic is not None else (a.full and world == 1 and not a.graph and not profiled)
         if want_pmc and world == 1:
             traffic, info = measure_traffic(a, "lsq::" + kb)
             if traffic is not None:
@@ -1030,7 +1044,8 @@ def run_rank(a):
             "metric": metric,
             "value": round(value, 3), "unit": "GElem/s", "n_gpus": world, "steps": m["steps"], "warmup": a.warmup,
             "ms_per_step": round(elapsed_max / m["steps"] * 1e3, 5), "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "warmup_wall_floor_ms": warm_floor_ms,
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "run": "full" if a.full else "plain",
+            "warmup_wall_floor_ms": warm_floor_ms,
             "timed_blocks_ms_per_step": [round(tb / m["steps"] * 1e3, 5) for tb in m["block_times"]],
             "config": {"workload": "%s: %s %s %s per GPU, %s%s" % (a.workload, what, dtype_name, shape, opnames,
                                                                     "" if world == 1 else ", batch-sharded, 1 RCCL all-reduce of fp64 [ds,db] per step"),
@@ -1081,7 +1096,7 @@ def run_rank(a):
             # collective and the co-running ranks cost one GPU.  1.0 = none.
             line["per_gpu_efficiency"] = round(m["solo_ms"] / (elapsed_max / a.steps * 1e3), 4)
             line["rank0_shard_alone_ms_per_step"] = round(m["solo_ms"], 5)
-        if world == 1 and not a.no_yardstick:
+        if world == 1 and a.full and not a.no_yardstick:
             # Context for the roofline fraction, measured live on THIS box after the timed region: the framework's /
             # vendor's own kernels on the same two traffic shapes (ATen's vectorised add = 2 reads : 1 write like the
             # backward; its copy = 1 read : 1 write like the forward).  Not part of `value`.
@@ -1104,7 +1119,7 @@ def run_rank(a):
             except Exception as e:      # context only: never let it break the bench line
                 line["roofline"]["same_box_reference_kernels"] = {"error": repr(e)}
         sustained = None
-        if world == 1 and a.workload == "cfg2" and not a.graph and not a.no_secondary and not (a.variant_fwd or a.variant_bwd):
+        if world == 1 and a.workload == "cfg2" and not a.graph and a.full and not a.no_secondary and not (a.variant_fwd or a.variant_bwd):
             # The headline region is K steps (the driver's K = 20: 13 ms).  The SAME step, on the same buffers, for at least a
             # second, HIP events on 1 % of the steps: the sustained figure next to the burst.  DESIGN.md section 5 says which of
             # the two the 70 % claim rests on (both must clear it).
@@ -1133,7 +1148,7 @@ def run_rank(a):
                 del sm
             except Exception as e:      # context only
                 sustained = {"workload": "cfg2_sustained", "error": repr(e)}
-        if world == 1 and binding == "native" and not a.graph and not a.no_secondary:
+        if world == 1 and binding == "native" and not a.graph and a.full and not a.no_secondary:
             # north_star describes Python host code over the thin C ABI; the timed region above ran the C++ host binding (same C
             # entry points, less host time per call).  The same workload through the Python / ctypes host layer, 20 steps:
             try:
@@ -1157,9 +1172,9 @@ def run_rank(a):
                 del pm, nm, same
             except Exception as e:      # context only
                 line["config"]["python_ctypes_host_layer"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(shape, a.workload)
-        if world == 1 and a.workload == "cfg2" and not a.graph and not a.no_secondary:
+        if world == 1 and a.workload == "cfg2" and not a.graph and a.full and not a.no_secondary:
             # The other single-GPU BASELINE configs (the small per-tensor one and the per-channel half of the path), timed in
             # this process right after the headline region, the same way: eager launches, rotated input buffers, per-op HIP
             # events.  `value` / `ms_per_step` are wall-clock over the K steps; the fractions are of the 8 TB/s peak.
@@ -1242,7 +1257,7 @@ def run_rank(a):
             line["secondary"] = sec
             line["secondary_wall_s"] = round(time.perf_counter() - t_sec, 2)
     strong = None
-    if world > 1 and a.workload == "cfg2" and not a.no_secondary and 1024 % world == 0:
+    if world > 1 and a.workload == "cfg2" and a.full and not a.no_secondary and 1024 % world == 0:
         try:
             # BASELINE config 4 next to the weak-scaled headline: [1024,1024,14,14] split over the ranks (STRONG scaling), the same
             # sharded step (every rank takes part: collectives inside)

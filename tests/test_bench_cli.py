@@ -29,7 +29,7 @@ def test_self_spawned_ranks_on_one_device():
     """`--gpus 2` without a launcher: bench.py starts both ranks (here sharing the one GPU, collective over gloo
     because RCCL refuses two ranks on one device) and rank 0 reports n_gpus = 2 and twice the elements."""
     r = _run(["--gpus", "2", "--backend", "gloo", "--single-device", "--workload", "cfg1", "--steps", "6", "--warmup", "2",
-              "--no-cpu-baseline"])
+              "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -50,7 +50,7 @@ def test_a_wrong_sum_prints_the_line_with_ok_false():
     """a corrupted reduction (test switch: the reduced sums scaled by 1 + 1e-3 before they are checked) must not cost the line --
     it comes out with collective_verified.ok = false"""
     r = _run(["--gpus", "2", "--backend", "gloo", "--single-device", "--workload", "cfg1", "--steps", "4", "--warmup", "1",
-              "--no-cpu-baseline"], extra_env={"LSQ_BENCH_CORRUPT_REDUCED": "1"})
+              "--no-cpu-baseline", "--full"], extra_env={"LSQ_BENCH_CORRUPT_REDUCED": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     cv = out["config"]["collective_verified"]
@@ -61,7 +61,7 @@ def test_a_wrong_sum_prints_the_line_with_ok_false():
 def test_default_multi_rank_line_carries_the_strong_scaled_config_too():
     """the N > 1 default line (weak-scaled config 2 per rank) also reports BASELINE config 4, [1024,1024,14,14] split over the
     ranks, with its own per-GPU efficiency; here 2 ranks share the one GPU over gloo (the control flow, not the numbers)"""
-    r = _run(["--gpus", "2", "--backend", "gloo", "--single-device", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"])
+    r = _run(["--gpus", "2", "--backend", "gloo", "--single-device", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and "cfg2" in out["config"]["workload"]
@@ -81,7 +81,8 @@ def test_default_multi_rank_line_carries_the_strong_scaled_config_too():
 
 
 def test_default_line_has_secondary_records_declared():
-    """(CPU: the flag surface only) the default run appends `secondary` records for the other single-GPU BASELINE configs"""
+    """(CPU: the flag surface only) the default `--full` run appends `secondary` records for the other single-GPU BASELINE
+    configs; a plain run is the headline alone"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("_bench", BENCH)
     b = importlib.util.module_from_spec(spec)
@@ -89,6 +90,7 @@ def test_default_line_has_secondary_records_declared():
     assert b.SECONDARY == ("cfg1", "cfg3", "cfg5", "cfg5_bf16")
     a = b.parse_args([])
     assert a.workload == "cfg2" and a.gpus == 1 and not a.no_secondary
+    assert not a.full and b.parse_args(["--full"]).full and a.measure_traffic is None
     # the sharded step's collective: the library's own RCCL communicator by default, the record of the default run declared
     assert a.collective == "native" and not a.assume_peers
     assert b.parse_args(["--collective", "native-inline"]).collective == "native-inline"
@@ -122,7 +124,7 @@ def _timing_bounds(out, sec):
 
 @pytest.mark.gpu
 def test_default_line_carries_the_per_channel_half():
-    args = ["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-measure-traffic", "--secondary-steps", "20"]
+    args = ["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-measure-traffic", "--secondary-steps", "20", "--full"]
     r = _run(args)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -167,7 +169,7 @@ def test_four_ranks_control_flow_on_one_device():
     next to the test process is as many processes as one shared device should carry (at most six may hold it at once), so the
     eight-rank job is not run here; its per-rank step is the `cfg4_shard` record of the default line."""
     r = _run(["--gpus", "4", "--backend", "gloo", "--single-device", "--workload", "cfg4", "--steps", "3", "--warmup", "1",
-              "--no-cpu-baseline"], timeout=1500)
+              "--no-cpu-baseline", "--full"], timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -193,6 +195,23 @@ def test_a_failing_rank_shows_its_traceback():
 
 
 @pytest.mark.gpu
+def test_plain_run_is_the_headline_alone():
+    """without --full the line carries the headline and its in-region roofline, and nothing that needs runs of its own"""
+    r = _run(["--workload", "cfg1", "--steps", "6", "--warmup", "2"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-500:]
+    out = json.loads(lines[0])
+    assert out["run"] == "plain" and out["steps"] == 6 and out["warmup"] == 2 and out["n_gpus"] == 1
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "GElem/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["metric"] and out["roofline"]["frac"] > 0 and out["roofline"]["fwd"]["frac"] > 0
+    assert not {"cpu_baseline", "secondary", "strong_scaled", "parity_vs_reference"} & set(out), sorted(out)
+    assert not {"python_ctypes_host_layer", "collective_verified"} & set(out["config"]), sorted(out["config"])
+    assert not {"same_box_reference_kernels", "sustained"} & set(out["roofline"]), sorted(out["roofline"])
+    assert "measured by this run" not in str(out["roofline"]["traffic_source"])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("workload", ["cfg3", "cfg5_bf16"])
 def test_per_channel_workloads_report_their_kernel(workload):
     r = _run(["--workload", workload, "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-measure-traffic"])
@@ -212,8 +231,8 @@ def test_native_route_is_checked_before_anything_is_timed(how):
     are simulated (an env switch; a negative deadline, with which the communicator is treated as hung: not torn down,
     the process leaves through os._exit once the line is out)."""
     env = {"ok": {}, "wrong": {"LSQ_BENCH_PREFLIGHT_FAIL": "1"}, "hung": {"LSQ_BENCH_PREFLIGHT_S": "-1"}}[how]
-    r = _run(["--workload", "cfg4_shard", "--assume-peers", "--steps", "60", "--warmup", "20", "--no-secondary", "--no-cpu-baseline"],
-             extra_env=env)
+    r = _run(["--workload", "cfg4_shard", "--assume-peers", "--steps", "60", "--warmup", "20", "--no-secondary", "--no-cpu-baseline",
+              "--full"], extra_env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-500:]

@@ -6,7 +6,7 @@ mkdir -p $O
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -5 $O/smoke.txt | cut -c1-160
 timeout 3000 python3 -m pytest tests -m gpu -q > $O/tests_all.txt 2>&1
 tail -3 $O/tests_all.txt | cut -c1-300
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 - <<'PY'
 import json
 lines=[l for l in open("gpurun_out/final6/bench_default.json").read().splitlines()]
