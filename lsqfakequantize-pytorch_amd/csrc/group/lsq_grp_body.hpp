@@ -1,7 +1,8 @@
-// lsq_grp_body.hpp -- what the group-wise kernels share: the single-tensor ones (lsq_per_group.hip, liblsq_hip_group.so)
-// and the multi-tensor ones (lsq_per_group_multi.hip, liblsq_hip_group_multi.so).  lsq_per_group.hip describes the forms
-// and the reductions.
-//  * the device helpers and the launch plan (plan_group) below;
+// lsq_grp_body.hpp -- what the two translation units of liblsq_hip_group.so share: the single-tensor kernels
+// (lsq_per_group.hip, which also holds the C ABI) and the multi-tensor ones (lsq_per_group_multi.hip).  lsq_per_group.hip
+// describes the forms and the reductions.
+//  * the device helpers below, and on the host the launch plan (plan_group), the kernel arguments an item gets from its
+//    plan (grp_fwd_item / grp_bwd_item) and the entry points of the multi-tensor translation unit;
 //  * the kernel bodies, lsq_grp_fwd_body.inc and lsq_grp_bwd_body.inc: statement fragments that a kernel #includes as its
 //    body, with LSQ_GRP_BLOCK / LSQ_GRP_GRID defined as the workgroup's index and the number of workgroups that walk the
 //    tensor -- blockIdx.x / gridDim.x in a single-tensor kernel, the index within the item and the item's own grid in a
@@ -11,6 +12,7 @@
 #pragma once
 
 #include "../lsq_kernels.hpp"
+#include "../../../include/lsq_hip_group.h"
 
 namespace lsq {
 
@@ -81,7 +83,7 @@ __device__ __forceinline__ void store_group(T* __restrict__ ds, T* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side: the plan -- one rule for the launches of both libraries, lsq_group_plan and lsq_group_multi_plan
+// host side: the plan -- one rule for the single and the fused launches, lsq_group_plan and lsq_group_multi_plan
 // ------------------------------------------------------------------------------------------------
 struct GrpPlan {
     bool packet;            // G % V == 0
@@ -99,6 +101,12 @@ inline int log2_exact(int64_t v) {
     return k;
 }
 
+// the forward grid of the element form (one element per lane)
+inline int grp_elem_fwd_grid(int64_t n) {
+    const int64_t fwd_round = static_cast<int64_t>(device_info().cu_count) * kGrpFwdBlocksPerCU;
+    return static_cast<int>(std::min(std::max<int64_t>(1, (n + kBlock - 1) / kBlock), fwd_round));
+}
+
 inline GrpPlan plan_group(int vec, int64_t n, int64_t G) {
     const DeviceInfo& dev = device_info();
     GrpPlan pl;
@@ -114,7 +122,7 @@ inline GrpPlan plan_group(int vec, int64_t n, int64_t G) {
         const int64_t tiles = std::max<int64_t>(1, (n / vec + int64_t{kBlock} * kGrpUnroll - 1) / (int64_t{kBlock} * kGrpUnroll));
         pl.fwd_grid = static_cast<int>(std::min(tiles, fwd_round));
     } else {
-        pl.fwd_grid = static_cast<int>(std::min(std::max<int64_t>(1, (n + kBlock - 1) / kBlock), fwd_round));
+        pl.fwd_grid = grp_elem_fwd_grid(n);
     }
     const int64_t n_items = pl.packet ? n / vec : n;
     if (pl.mode == kP2) {
@@ -131,5 +139,80 @@ inline GrpPlan plan_group(int vec, int64_t n, int64_t G) {
     }
     return pl;
 }
+
+
+// The kernel arguments of one tensor, from its plan: the single-tensor launchers pass the fields to fwd_grp_kernel /
+// bwd_grp_kernel, the multi-tensor launchers put the structs in their kernel-argument tables -- so a fused item runs with
+// exactly the arguments of its single call.
+template <typename T>
+struct GrpFwdItem {
+    const void* x;
+    void* y;
+    const T* scale;
+    const T* shift;
+    int64_t n, G;
+    DivU64 per_group;   // packets per group in the packet form, G in the element form
+    int pg_shift;
+};
+
+template <typename T>
+struct GrpBwdItem {
+    const void* grad;
+    const void* x;
+    void* dx;
+    const T* scale;
+    const T* shift;
+    T* ds;
+    T* db;
+    int64_t n, G;
+    DivU64 per_group;
+    int64_t groups_per_wave;
+    int pg_shift;
+    T gs;               // the gradient scaler (numel_for_scaler or n, quant_max, n / G)
+    T sym_term;
+};
+
+template <typename T>
+inline GrpFwdItem<T> grp_fwd_item(const GrpPlan& pl, const lsq_group_item& s) {
+    GrpFwdItem<T> d;
+    d.x = s.x;
+    d.y = s.y;
+    d.scale = static_cast<const T*>(s.scale);
+    d.shift = static_cast<const T*>(s.shift);
+    d.n = s.n;
+    d.G = s.group_size;
+    d.per_group = make_div(pl.packet ? pl.items_per_group : s.group_size);
+    d.pg_shift = pl.packet ? pl.pg_shift : -1;
+    return d;
+}
+
+template <typename T>
+inline GrpBwdItem<T> grp_bwd_item(const GrpPlan& pl, const lsq_group_item& s, const lsq_params& p) {
+    GrpBwdItem<T> d;
+    d.grad = s.grad;
+    d.x = s.x;
+    d.dx = s.dx;
+    d.scale = static_cast<const T*>(s.scale);
+    d.shift = static_cast<const T*>(s.shift);
+    d.ds = static_cast<T*>(s.ds);
+    d.db = static_cast<T*>(s.db);
+    d.n = s.n;
+    d.G = s.group_size;
+    d.per_group = make_div(pl.items_per_group);
+    d.groups_per_wave = pl.groups_per_wave;
+    d.pg_shift = pl.pg_shift;
+    const int64_t n4s = p.numel_for_scaler > 0 ? p.numel_for_scaler : s.n;
+    d.gs = grad_scaler_per_channel<T>(n4s, p.quant_max, s.n / s.group_size, p.use_grad_scaling != 0, p.grad_scaler);
+    d.sym_term = static_cast<T>(0) * d.gs;
+    return d;
+}
+
+// lsq_per_group_multi.hip, for the C ABI (which has validated the items): the fused launches of one direction, and the
+// plan walk of lsq_group_multi_plan (per_item3 filled for the items with n > 0; returns the launches per direction)
+hipError_t forward_per_group_multi(int dtype, const lsq_group_item* items, int32_t count, const lsq_params& p,
+                                   hipStream_t stream);
+hipError_t backward_per_group_multi(int dtype, const lsq_group_item* items, int32_t count, const lsq_params& p,
+                                    hipStream_t stream);
+int32_t plan_group_multi(int vec, const lsq_group_item* items, int32_t count, int32_t* per_item3);
 
 }  // namespace lsq

@@ -1,5 +1,5 @@
-// lsq_per_group_multi.hip -- MANY group-wise quantizers in one launch each way (include/lsq_hip_group_multi.h,
-// liblsq_hip_group_multi.so).
+// lsq_per_group_multi.hip -- MANY group-wise quantizers in one launch each way: the kernels and launchers of the fused
+// calls of include/lsq_hip_group.h (their C ABI is in lsq_per_group.hip).
 //
 // A QAT model with group-wise weights runs one lsq_group_forward / lsq_group_backward pair per layer and step.  Most of
 // those tensors are small next to the chip: a ViT-B 768 x 768 fp32 weight at G = 128 gets 144 workgroups each way from
@@ -16,39 +16,9 @@
 // All indexing is 64-bit, as in the single-tensor kernels: one item may hold more than 2^31 elements.
 #include "lsq_grp_body.hpp"
 
-#include "../../../include/lsq_hip_group_multi.h"
-
 namespace lsq {
 
 constexpr int kGrpItems = LSQ_GROUP_MULTI_ITEMS;
-
-template <typename T>
-struct GrpFwdItem {     // one tensor of a forward launch (kernel-argument image)
-    const void* x;
-    void* y;
-    const T* scale;
-    const T* shift;
-    int64_t n, G;
-    DivU64 per_group;   // (as the single launch: packets per group in the packet form, G in the element form)
-    int pg_shift;
-};
-
-template <typename T>
-struct GrpBwdItem {     // one tensor of a backward launch
-    const void* grad;
-    const void* x;
-    void* dx;
-    const T* scale;
-    const T* shift;
-    T* ds;
-    T* db;
-    int64_t n, G;
-    DivU64 per_group;
-    int64_t groups_per_wave;
-    int pg_shift;
-    T gs;               // the item's own gradient scaler (n, quant_max, n / G), as in its single call
-    T sym_term;
-};
 
 template <typename Item, typename T>
 struct GrpMultiArgs {
@@ -168,18 +138,9 @@ static hipError_t launch_fwd_multi(const GrpLaunch& l, const lsq_group_item* ite
     a.r = make_range<T>(p);
     int64_t blocks = 0;
     for (int k = 0; k < l.count; ++k) {
-        const lsq_group_item& s = items[l.index[k]];
         const GrpPlan& pl = l.plan[k];
-        GrpFwdItem<T>& d = a.item[k];
         a.first[k] = static_cast<int32_t>(blocks);
-        d.x = s.x;
-        d.y = s.y;
-        d.scale = static_cast<const T*>(s.scale);
-        d.shift = static_cast<const T*>(s.shift);
-        d.n = s.n;
-        d.G = s.group_size;
-        d.pg_shift = pl.packet ? pl.pg_shift : -1;               // (launch_fwd_grp's arguments)
-        d.per_group = make_div(pl.packet ? pl.items_per_group : s.group_size);
+        a.item[k] = grp_fwd_item<T>(pl, items[l.index[k]]);
         blocks += pl.fwd_grid;
     }
     for (int k = l.count; k <= kGrpItems; ++k) a.first[k] = static_cast<int32_t>(blocks);
@@ -210,24 +171,9 @@ static hipError_t launch_bwd_multi(const GrpLaunch& l, const lsq_group_item* ite
     a.r = make_range<T>(p);
     int64_t blocks = 0;
     for (int k = 0; k < l.count; ++k) {
-        const lsq_group_item& s = items[l.index[k]];
         const GrpPlan& pl = l.plan[k];
-        GrpBwdItem<T>& d = a.item[k];
         a.first[k] = static_cast<int32_t>(blocks);
-        d.grad = s.grad;
-        d.x = s.x;
-        d.dx = s.dx;
-        d.scale = static_cast<const T*>(s.scale);
-        d.shift = static_cast<const T*>(s.shift);
-        d.ds = static_cast<T*>(s.ds);
-        d.db = static_cast<T*>(s.db);
-        d.n = s.n;
-        d.G = s.group_size;
-        d.pg_shift = pl.pg_shift;                                  // (launch_bwd_grp's arguments)
-        d.per_group = make_div(pl.items_per_group);
-        d.groups_per_wave = pl.groups_per_wave;
-        d.gs = grad_scaler_per_channel<T>(s.n, p.quant_max, s.n / s.group_size, p.use_grad_scaling != 0, p.grad_scaler);
-        d.sym_term = static_cast<T>(0) * d.gs;
+        a.item[k] = grp_bwd_item<T>(pl, items[l.index[k]], p);
         blocks += pl.bwd_grid;
     }
     for (int k = l.count; k <= kGrpItems; ++k) a.first[k] = static_cast<int32_t>(blocks);
@@ -248,7 +194,8 @@ static hipError_t launch_bwd_multi(const GrpLaunch& l, const lsq_group_item* ite
 }
 
 template <typename IO>
-hipError_t per_group_multi(bool backward, const lsq_group_item* items, int32_t count, const lsq_params& p, hipStream_t stream) {
+static hipError_t per_group_multi(bool backward, const lsq_group_item* items, int32_t count, const lsq_params& p,
+                                  hipStream_t stream) {
     hipError_t e = hipSuccess;
     for_each_launch(IO::VEC, items, count, [&](const GrpLaunch& l) {
         if (e != hipSuccess) return;
@@ -257,113 +204,29 @@ hipError_t per_group_multi(bool backward, const lsq_group_item* items, int32_t c
     return e;
 }
 
-}  // namespace lsq
-
-// ------------------------------------------------------------------------------------------------
-// the C ABI of include/lsq_hip_group_multi.h
-// ------------------------------------------------------------------------------------------------
-#include <cstdarg>
-#include <cstdio>
-
-namespace {
-
-thread_local char g_multi_error[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_multi_error, sizeof(g_multi_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int io_vec(int dtype) { return dtype == LSQ_F32 ? 4 : dtype == LSQ_F64 ? 2 : 8; }
-uintptr_t elem_bytes(int dtype) { return dtype == LSQ_F64 ? 8 : (dtype == LSQ_F32 ? 4 : 2); }
-uintptr_t param_bytes(int dtype) { return dtype == LSQ_F64 ? 8 : 4; }
-bool aligned_to(const void* a, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(a) & (bytes - 1)) == 0; }
-
-// dtype, count, the items' sizes -- and, for a launch (dir 0 = forward, 1 = backward), their buffers and lsq_params
-int check_items(int dtype, const lsq_group_item* items, int32_t count, const lsq_params* p, int dir, const char* what) {
-    if (dtype < LSQ_F32 || dtype > LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
-    if (count < 0) return fail(LSQ_EINVAL, "%s: negative item count %d", what, count);
-    if (count > 0 && !items) return fail(LSQ_EINVAL, "%s: items is NULL", what);
-    if (dir >= 0) {
-        if (!p) return fail(LSQ_EINVAL, "%s: lsq_params pointer is NULL", what);
-        if (p->quant_min > p->quant_max) return fail(LSQ_EINVAL, "%s: quant_min %d > quant_max %d", what, p->quant_min, p->quant_max);
-        if (p->type_min > p->type_max) return fail(LSQ_EINVAL, "%s: type_min %d > type_max %d", what, p->type_min, p->type_max);
-        if (p->numel_for_scaler != 0)
-            return fail(LSQ_EINVAL, "%s: numel_for_scaler must be 0 (there is no sharded group op), got %lld", what,
-                        static_cast<long long>(p->numel_for_scaler));
-    }
-    const uintptr_t eb = elem_bytes(dtype), pb = param_bytes(dtype);
-    for (int32_t i = 0; i < count; ++i) {
-        const lsq_group_item& it = items[i];
-        const long long n = it.n, G = it.group_size;
-        if (G <= 0) return fail(LSQ_EINVAL, "%s: item %d: group_size must be positive, got %lld", what, i, G);
-        if (n < 0) return fail(LSQ_EINVAL, "%s: item %d: negative element count %lld", what, i, n);
-        if (n % G != 0)
-            return fail(LSQ_EINVAL, "%s: item %d: element count %lld is not a multiple of group_size %lld", what, i, n, G);
-        if (dir < 0 || n == 0) continue;
-        if (dir == 0) {
-            if (!it.x || !it.y || !it.scale || !it.shift) return fail(LSQ_EINVAL, "%s: item %d: NULL buffer", what, i);
-            if (!aligned_to(it.x, eb) || !aligned_to(it.y, eb))
-                return fail(LSQ_EINVAL, "%s: item %d: x and y must be element-aligned", what, i);
-        } else {
-            if (!it.grad || !it.x || !it.dx || !it.ds || !it.db || !it.scale || !it.shift)
-                return fail(LSQ_EINVAL, "%s: item %d: NULL buffer", what, i);
-            if (!aligned_to(it.grad, eb) || !aligned_to(it.x, eb) || !aligned_to(it.dx, eb))
-                return fail(LSQ_EINVAL, "%s: item %d: grad, x and dx must be element-aligned", what, i);
-            if (!aligned_to(it.ds, pb) || !aligned_to(it.db, pb))
-                return fail(LSQ_EINVAL, "%s: item %d: ds and db must be element-aligned", what, i);
-        }
-        if (!aligned_to(it.scale, pb) || !aligned_to(it.shift, pb))
-            return fail(LSQ_EINVAL, "%s: item %d: scale and shift must be element-aligned", what, i);
-    }
-    return LSQ_OK;
-}
-
-int run(bool backward, int dtype, const lsq_group_item* items, int32_t count, const lsq_params* p, void* stream) {
-    const char* what = backward ? "lsq_group_multi_backward" : "lsq_group_multi_forward";
-    if (int rc = check_items(dtype, items, count, p, backward ? 1 : 0, what)) return rc;
-    hipError_t e = hipSuccess;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
+static hipError_t per_group_multi(bool backward, int dtype, const lsq_group_item* items, int32_t count, const lsq_params& p,
+                                  hipStream_t stream) {
     switch (dtype) {
-        case LSQ_F32: e = lsq::per_group_multi<lsq::io_f32>(backward, items, count, *p, s); break;
-        case LSQ_F64: e = lsq::per_group_multi<lsq::io_f64>(backward, items, count, *p, s); break;
-        case LSQ_BF16: e = lsq::per_group_multi<lsq::io_bf16>(backward, items, count, *p, s); break;
-        default: e = lsq::per_group_multi<lsq::io_f16>(backward, items, count, *p, s); break;
+        case LSQ_F32: return per_group_multi<io_f32>(backward, items, count, p, stream);
+        case LSQ_F64: return per_group_multi<io_f64>(backward, items, count, p, stream);
+        case LSQ_BF16: return per_group_multi<io_bf16>(backward, items, count, p, stream);
+        default: return per_group_multi<io_f16>(backward, items, count, p, stream);
     }
-    if (e == hipSuccess) return LSQ_OK;
-    return fail(static_cast<int>(e), "%s: %s (%s)", what, hipGetErrorName(e), hipGetErrorString(e));
 }
 
-}  // namespace
-
-extern "C" {
-
-int lsq_group_multi_abi_version(void) { return LSQ_GROUP_MULTI_ABI_VERSION; }
-
-const char* lsq_group_multi_last_error(void) { return g_multi_error; }
-
-int lsq_group_multi_forward(int dtype, const lsq_group_item* items, int32_t count, const lsq_params* p, void* stream) {
-    return run(false, dtype, items, count, p, stream);
+hipError_t forward_per_group_multi(int dtype, const lsq_group_item* items, int32_t count, const lsq_params& p,
+                                   hipStream_t stream) {
+    return per_group_multi(false, dtype, items, count, p, stream);
 }
 
-int lsq_group_multi_backward(int dtype, const lsq_group_item* items, int32_t count, const lsq_params* p, void* stream) {
-    return run(true, dtype, items, count, p, stream);
+hipError_t backward_per_group_multi(int dtype, const lsq_group_item* items, int32_t count, const lsq_params& p,
+                                    hipStream_t stream) {
+    return per_group_multi(true, dtype, items, count, p, stream);
 }
 
-int lsq_group_multi_plan(int dtype, const lsq_group_item* items, int32_t count, int32_t* per_item3, int32_t* launches) {
-    const char* what = "lsq_group_multi_plan";
-    if (int rc = check_items(dtype, items, count, nullptr, -1, what)) return rc;
-    if ((count > 0 && !per_item3) || !launches) return fail(LSQ_EINVAL, "%s: NULL output", what);
-    for (int32_t i = 0; i < count; ++i) {
-        per_item3[3 * i] = -1;
-        per_item3[3 * i + 1] = 0;
-        per_item3[3 * i + 2] = 0;
-    }
+int32_t plan_group_multi(int vec, const lsq_group_item* items, int32_t count, int32_t* per_item3) {
     int32_t n_launch = 0;
-    lsq::for_each_launch(io_vec(dtype), items, count, [&](const lsq::GrpLaunch& l) {
+    for_each_launch(vec, items, count, [&](const GrpLaunch& l) {
         for (int k = 0; k < l.count; ++k) {
             int32_t* o = per_item3 + 3 * l.index[k];
             o[0] = n_launch;
@@ -372,8 +235,7 @@ int lsq_group_multi_plan(int dtype, const lsq_group_item* items, int32_t count, 
         }
         ++n_launch;
     });
-    *launches = n_launch;
-    return LSQ_OK;
+    return n_launch;
 }
 
-}  // extern "C"
+}  // namespace lsq

@@ -1,5 +1,5 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
-(include/lsq_cpu.h, ctypes) and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
+(include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes) and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
 The module holds the loader STATE (`_LIB`, `_HAS_OPS`, `_CPU_LIB`, `_NATIVE_LSQ`); the host layers (_hip_host.py,
@@ -138,10 +138,24 @@ except (ImportError, OSError, AttributeError) as e:  # surfaced by _assert_has_o
     error_str = str(e)
 
 
+def _load_companion(name, table, version_fn, abi_version):
+    """dlopen the companion library `name` next to liblsq_hip.so, type the entry points of `table` and check its ABI
+    version (`version_fn`): (handle, "") or, when it cannot be used, (None, why).  The package works without it; its ops then raise."""
+    try:
+        lib = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), name))
+        for fname, (res, args) in table.items():
+            fn = getattr(lib, fname)
+            fn.restype = res
+            fn.argtypes = args
+        abi = getattr(lib, version_fn)()
+        if abi != abi_version:
+            raise OSError("%s has ABI version %d, this package needs %d" % (name, abi, abi_version))
+        return lib, ""
+    except (OSError, AttributeError) as e:
+        return None, str(e)
+
+
 # The kernels for tensors in host memory (include/lsq_cpu.h): the counterpart of the reference's CPU dispatch.
-_CPU_LIB = None
-_CPU_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblsq_cpu.so")
-cpu_error_str = ""
 C_ABI_CPU = {
     "lsq_cpu_abi_version": (_int, []),
     "lsq_cpu_last_error": (ctypes.c_char_p, []),
@@ -152,59 +166,33 @@ C_ABI_CPU = {
     "lsq_cpu_backward_per_channel": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _PP]),
     "lsq_cpu_sharded_finish": (_int, [_int, _vp, _i64, ctypes.c_int32, _PP, _vp, _vp]),
 }
+_CPU_LIB, cpu_error_str = _load_companion("liblsq_cpu.so", C_ABI_CPU, "lsq_cpu_abi_version", ABI_VERSION)
 
 
-def _load_cpu_library():
-    global _CPU_LIB, cpu_error_str
-    try:
-        lib = ctypes.CDLL(_CPU_LIB_PATH)
-        for name, (res, args) in C_ABI_CPU.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.lsq_cpu_abi_version() != ABI_VERSION:
-            raise OSError("liblsq_cpu.so was built for another ABI version")
-        _CPU_LIB = lib
-    except (OSError, AttributeError) as e:
-        cpu_error_str = str(e)
+# The group-wise ops, one tensor per call or many in one launch each way (include/lsq_hip_group.h): a companion library
+# next to liblsq_hip.so, whose ABI (C_ABI above, pinned against include/lsq_hip.h) it leaves as it is.
+class LsqGroupItem(ctypes.Structure):
+    """lsq_group_item (include/lsq_hip_group.h): one tensor of a fused group-wise call."""
+    _fields_ = [("x", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("y", ctypes.c_void_p), ("dx", ctypes.c_void_p),
+                ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("ds", ctypes.c_void_p), ("db", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("group_size", ctypes.c_int64)]
 
 
-_load_cpu_library()
-
-
-# The group-wise ops (include/lsq_hip_group.h): a companion library next to liblsq_hip.so, whose ABI (C_ABI above, pinned
-# against include/lsq_hip.h) it leaves as it is.  Loaded like the CPU kernels: the package works without it, the group ops
-# then raise with `group_error_str`.
-_GROUP_LIB = None
-_GROUP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblsq_hip_group.so")
-group_error_str = ""
-GROUP_ABI_VERSION = 1
+GROUP_ABI_VERSION = 2
+GROUP_MULTI_ITEMS = 28          # LSQ_GROUP_MULTI_ITEMS: items per fused launch
+_GIP = ctypes.POINTER(LsqGroupItem)
 C_ABI_GROUP = {
     "lsq_group_abi_version": (_int, []),
     "lsq_group_last_error": (ctypes.c_char_p, []),
     "lsq_group_forward": (_int, [_int, _vp, _vp, _i64, _i64, _vp, _vp, _PP, _EP, _vp]),
     "lsq_group_backward": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _PP, _vp]),
     "lsq_group_plan": (_int, [_int, _i64, _i64, ctypes.POINTER(ctypes.c_int32 * 8)]),
+    "lsq_group_multi_forward": (_int, [_int, _GIP, ctypes.c_int32, _PP, _vp]),
+    "lsq_group_multi_backward": (_int, [_int, _GIP, ctypes.c_int32, _PP, _vp]),
+    "lsq_group_multi_plan": (_int, [_int, _GIP, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
 }
-
-
-def _load_group_library():
-    global _GROUP_LIB, group_error_str
-    try:
-        lib = ctypes.CDLL(_GROUP_LIB_PATH)
-        for name, (res, args) in C_ABI_GROUP.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.lsq_group_abi_version() != GROUP_ABI_VERSION:
-            raise OSError("liblsq_hip_group.so has ABI version %d, this package needs %d" %
-                          (lib.lsq_group_abi_version(), GROUP_ABI_VERSION))
-        _GROUP_LIB = lib
-    except (OSError, AttributeError) as e:
-        group_error_str = str(e)
-
-
-_load_group_library()
+_GROUP_LIB, group_error_str = _load_companion("liblsq_hip_group.so", C_ABI_GROUP, "lsq_group_abi_version",
+                                                GROUP_ABI_VERSION)
 
 
 def group_library():
@@ -214,59 +202,6 @@ def group_library():
         raise RuntimeError("torchlsq: the group-wise ops need liblsq_hip_group.so, which could not be loaded (build it with "
                            "`python __graft_entry__.py`): %s" % group_error_str)
     return _GROUP_LIB
-
-
-# Many group-wise tensors in one launch each way (include/lsq_hip_group_multi.h): a third library, so that the pinned
-# exports of liblsq_hip_group.so (C_ABI_GROUP above) stay as they are.  Loaded like the group library: the package works
-# without it, the fused group-wise calls then raise with `group_multi_error_str`.
-class LsqGroupItem(ctypes.Structure):
-    """lsq_group_item (include/lsq_hip_group_multi.h): one tensor of a multi-tensor group-wise launch."""
-    _fields_ = [("x", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("y", ctypes.c_void_p), ("dx", ctypes.c_void_p),
-                ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("ds", ctypes.c_void_p), ("db", ctypes.c_void_p),
-                ("n", ctypes.c_int64), ("group_size", ctypes.c_int64)]
-
-
-_GROUP_MULTI_LIB = None
-_GROUP_MULTI_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblsq_hip_group_multi.so")
-group_multi_error_str = ""
-GROUP_MULTI_ABI_VERSION = 1
-GROUP_MULTI_ITEMS = 28          # LSQ_GROUP_MULTI_ITEMS: items per launch
-_GIP = ctypes.POINTER(LsqGroupItem)
-C_ABI_GROUP_MULTI = {
-    "lsq_group_multi_abi_version": (_int, []),
-    "lsq_group_multi_last_error": (ctypes.c_char_p, []),
-    "lsq_group_multi_forward": (_int, [_int, _GIP, ctypes.c_int32, _PP, _vp]),
-    "lsq_group_multi_backward": (_int, [_int, _GIP, ctypes.c_int32, _PP, _vp]),
-    "lsq_group_multi_plan": (_int, [_int, _GIP, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
-}
-
-
-def _load_group_multi_library():
-    global _GROUP_MULTI_LIB, group_multi_error_str
-    try:
-        lib = ctypes.CDLL(_GROUP_MULTI_LIB_PATH)
-        for name, (res, args) in C_ABI_GROUP_MULTI.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.lsq_group_multi_abi_version() != GROUP_MULTI_ABI_VERSION:
-            raise OSError("liblsq_hip_group_multi.so has ABI version %d, this package needs %d" %
-                          (lib.lsq_group_multi_abi_version(), GROUP_MULTI_ABI_VERSION))
-        _GROUP_MULTI_LIB = lib
-    except (OSError, AttributeError) as e:
-        group_multi_error_str = str(e)
-
-
-_load_group_multi_library()
-
-
-def group_multi_library():
-    """The ctypes handle of liblsq_hip_group_multi.so (raises if it is missing)."""
-    _assert_has_ops()
-    if _GROUP_MULTI_LIB is None:
-        raise RuntimeError("torchlsq: the fused group-wise calls need liblsq_hip_group_multi.so, which could not be loaded "
-                           "(build it with `python __graft_entry__.py`): %s" % group_multi_error_str)
-    return _GROUP_MULTI_LIB
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

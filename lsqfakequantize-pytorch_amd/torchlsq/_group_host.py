@@ -2,8 +2,8 @@
 
 GPU tensors go to liblsq_hip_group.so (include/lsq_hip_group.h) with one ctypes call per op; CPU tensors go to the
 per-channel kernels of liblsq_cpu.so on the [n / G, G] view (axis 0), which is what a group IS, value for value.
-`group_forward_multi` / `group_backward_multi`: many GPU tensors of one dtype in one ctypes call each way
-(liblsq_hip_group_multi.so, include/lsq_hip_group_multi.h), with the same checks and layout rules.
+`group_forward_multi` / `group_backward_multi`: many GPU tensors of one dtype in one ctypes call each way (the fused calls
+of the same library), with the same checks and layout rules.
 Checks and layout rules as in _hip_host.py: the flat stream needs x in row-major order (a non-contiguous x is made
 contiguous first, like a non-dense per-channel input); element-aligned views (x[1:]) run in place.
 """
@@ -12,7 +12,7 @@ import ctypes
 import torch
 
 from . import _abi
-from ._abi import _DTYPE_CODE, LsqGroupItem, _assert_has_ops, group_library, group_multi_library
+from ._abi import _DTYPE_CODE, LsqGroupItem, _assert_has_ops, group_library
 from ._hip_host import (_aux_output, _check, _on_device, _param_dtype, _params, _require_gpu, _stream_of,
                         check_backward_dtypes, check_forward_dtypes)
 from ._cpu_host import cpu_backward, cpu_forward, cpu_levels
@@ -35,6 +35,22 @@ def _group_status(rc, what):
         raise RuntimeError("%s failed (%d): %s" % (what, rc, _abi._GROUP_LIB.lsq_group_last_error().decode("utf-8", "replace")))
 
 
+def _fwd_buffers(x, scale, shift):
+    """the inputs as the flat stream reads them: contiguous x, scale and shift"""
+    return x.contiguous(), scale.contiguous(), shift.contiguous()
+
+
+def _bwd_buffers(grad, x, scale, shift):
+    """(grad, x, scale, shift) as the flat stream reads them -- contiguous, grad in x's shape -- and the outputs (dx,
+    d_scale, d_shift), the parameter gradients in the parameters' shapes"""
+    xd, sc, sh = _fwd_buffers(x, scale, shift)
+    gd = grad.contiguous() if grad.shape == x.shape else grad.reshape(x.shape).contiguous()
+    pd = _param_dtype(x)
+    outs = (torch.empty_like(xd), torch.empty(scale.shape, dtype=pd, device=x.device),
+            torch.empty(shift.shape, dtype=pd, device=x.device))
+    return (gd, xd, sc, sh), outs
+
+
 def group_forward(x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode,
                   levels_bias=None, want_mask=False, levels_only=False):
     """y (contiguous, x's shape); with levels_bias / want_mask also the one byte per element; levels_only: the bytes alone"""
@@ -46,7 +62,7 @@ def group_forward(x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, g
                             levels_bias, want_mask, levels_only)
     lib = group_library()
     _require_gpu("lsq_forward_per_group", x, scale, shift)
-    xd = x.contiguous()
+    xd, sc, sh = _fwd_buffers(x, scale, shift)
     y = None if levels_only else torch.empty_like(xd)
     has_aux = levels_bias is not None or want_mask
     if xd.numel() == 0:
@@ -54,7 +70,6 @@ def group_forward(x, scale, shift, group_size, qmin, qmax, tmin, tmax, use_gs, g
         return lv if levels_only else ((y, lv) if has_aux else y)
     lv, ex = _aux_output(xd, levels_bias, want_mask)
     _, pref = _params(qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
-    sc, sh = scale.contiguous(), shift.contiguous()
     idx = x.device.index
     rc = _on_device(idx, lib.lsq_group_forward, _DTYPE_CODE[x.dtype], xd.data_ptr(), None if levels_only else y.data_ptr(),
                     xd.numel(), group_size, sc.data_ptr(), sh.data_ptr(), pref, ex, _stream_of(idx))
@@ -80,14 +95,8 @@ def group_backward(grad, x, scale, shift, group_size, qmin, qmax, tmin, tmax, us
         return dx.reshape(x.shape), ds.reshape(scale.shape), db.reshape(shift.shape)
     lib = group_library()
     _require_gpu("lsq_backward_per_group", x, grad, scale, shift)
-    xd = x.contiguous()
-    gd = grad.contiguous() if grad.shape == x.shape else grad.reshape(x.shape).contiguous()
-    dx = torch.empty_like(xd)
-    pd = _param_dtype(x)
-    ds = torch.empty(scale.shape, dtype=pd, device=x.device)
-    db = torch.empty(shift.shape, dtype=pd, device=x.device)
+    (gd, xd, sc, sh), (dx, ds, db) = _bwd_buffers(grad, x, scale, shift)
     _, pref = _params(qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
-    sc, sh = scale.contiguous(), shift.contiguous()
     idx = x.device.index
     rc = _on_device(idx, lib.lsq_group_backward, _DTYPE_CODE[x.dtype], gd.data_ptr(), xd.data_ptr(), dx.data_ptr(),
                     ds.data_ptr(), db.data_ptr(), xd.numel(), group_size, sc.data_ptr(), sh.data_ptr(), pref, _stream_of(idx))
@@ -117,12 +126,6 @@ def group_plan(dtype, n, group_size):
                 reduction="butterfly" if out[5] == 1 else "scan", vec=out[6])
 
 
-def _multi_status(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc,
-                                                   _abi._GROUP_MULTI_LIB.lsq_group_multi_last_error().decode("utf-8", "replace")))
-
-
 def _multi_common(what, xs, scales, shifts, group_sizes):
     """checks of the single calls for every tensor; (device index, dtype code)"""
     n = len(xs)
@@ -140,13 +143,13 @@ def _multi_common(what, xs, scales, shifts, group_sizes):
 def group_forward_multi(xs, scales, shifts, group_sizes, qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode):
     """[y_i] = [group_forward(x_i, ...)]: one ctypes call, one launch per class of reduction and per 28 tensors"""
     _assert_has_ops()
-    lib = group_multi_library()
+    lib = group_library()
     idx, code = _multi_common("lsq_group_multi_forward", xs, scales, shifts, group_sizes)
     _, pref = _params(qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
     items = (LsqGroupItem * len(xs))()
     keep, ys = [], []
     for k, (x, sc, sh, G) in enumerate(zip(xs, scales, shifts, group_sizes)):
-        xd, scc, shc = x.contiguous(), sc.contiguous(), sh.contiguous()
+        xd, scc, shc = _fwd_buffers(x, sc, sh)
         y = torch.empty_like(xd)
         keep += [xd, scc, shc]
         ys.append(y)
@@ -155,7 +158,7 @@ def group_forward_multi(xs, scales, shifts, group_sizes, qmin, qmax, tmin, tmax,
         it.n, it.group_size = xd.numel(), G
     rc = _on_device(idx, lib.lsq_group_multi_forward, code, items, len(xs), pref, _stream_of(idx))
     if rc:
-        _multi_status(rc, "lsq_group_multi_forward")
+        _group_status(rc, "lsq_group_multi_forward")
     return ys
 
 
@@ -163,7 +166,7 @@ def group_backward_multi(grads, xs, scales, shifts, group_sizes, qmin, qmax, tmi
     """[(dx_i, d_scale_i, d_shift_i)] = [group_backward(grad_i, x_i, ...)]: one ctypes call; the parameter gradients come
     back in the parameters' shapes"""
     _assert_has_ops()
-    lib = group_multi_library()
+    lib = group_library()
     idx, code = _multi_common("lsq_group_multi_backward", xs, scales, shifts, group_sizes)
     _check(len(grads) == len(xs), "lsq_group_multi_backward: one gradient per tensor")
     _, pref = _params(qmin, qmax, tmin, tmax, use_gs, gs, sym, eval_mode, init_mode)
@@ -172,13 +175,7 @@ def group_backward_multi(grads, xs, scales, shifts, group_sizes, qmin, qmax, tmi
     for k, (g, x, sc, sh, G) in enumerate(zip(grads, xs, scales, shifts, group_sizes)):
         check_backward_dtypes(g, x, sc, sh)
         _require_gpu("lsq_group_multi_backward", x, g)
-        xd = x.contiguous()
-        gd = g.contiguous() if g.shape == x.shape else g.reshape(x.shape).contiguous()
-        scc, shc = sc.contiguous(), sh.contiguous()
-        dx = torch.empty_like(xd)
-        pd = _param_dtype(x)
-        ds = torch.empty(sc.shape, dtype=pd, device=x.device)
-        db = torch.empty(sh.shape, dtype=pd, device=x.device)
+        (gd, xd, scc, shc), (dx, ds, db) = _bwd_buffers(g, x, sc, sh)
         keep += [xd, gd, scc, shc]
         outs.append((dx, ds, db))
         it = items[k]
@@ -186,14 +183,14 @@ def group_backward_multi(grads, xs, scales, shifts, group_sizes, qmin, qmax, tmi
         it.ds, it.db, it.n, it.group_size = ds.data_ptr(), db.data_ptr(), xd.numel(), G
     rc = _on_device(idx, lib.lsq_group_multi_backward, code, items, len(xs), pref, _stream_of(idx))
     if rc:
-        _multi_status(rc, "lsq_group_multi_backward")
+        _group_status(rc, "lsq_group_multi_backward")
     return outs
 
 
 def group_multi_plan(dtype, sizes, group_sizes):
-    """How liblsq_hip_group_multi.so launches tensors of `sizes` elements with `group_sizes` -- host only, nothing is
+    """How the fused calls of liblsq_hip_group.so launch tensors of `sizes` elements with `group_sizes` -- host only, nothing is
     launched (lsq_group_multi_plan): (per tensor (launch index, forward workgroups, backward workgroups), launches)"""
-    lib = group_multi_library()
+    lib = group_library()
     n = len(sizes)
     items = (LsqGroupItem * max(n, 1))()
     for k, (m, G) in enumerate(zip(sizes, group_sizes)):
@@ -202,5 +199,5 @@ def group_multi_plan(dtype, sizes, group_sizes):
     launches = ctypes.c_int32(0)
     rc = lib.lsq_group_multi_plan(_DTYPE_CODE[dtype], items, n, out, ctypes.byref(launches))
     if rc:
-        _multi_status(rc, "lsq_group_multi_plan")
+        _group_status(rc, "lsq_group_multi_plan")
     return [(out[3 * k], out[3 * k + 1], out[3 * k + 2]) for k in range(n)], launches.value

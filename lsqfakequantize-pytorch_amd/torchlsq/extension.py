@@ -38,8 +38,8 @@ from ._group_host import (check_group_args, group_backward, group_backward_multi
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_GROUP_MULTI_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str",
-                "group_error_str", "group_multi_error_str", "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str", "group_error_str",
+                "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 

@@ -433,10 +433,10 @@ def lsq_levels_per_group(x: Tensor, scale: Tensor, shift: Tensor, group_size: in
 
 
 class _LSQGroupForeach(torch.autograd.Function):
-    """N group-wise quantizers of one dtype as ONE autograd node over the multi-tensor group kernels
-    (liblsq_hip_group_multi.so): one launch per reduction class and per 28 tensors each way instead of N.  Every tensor is
-    walked by the workgroups of its own single call, so outputs and gradients carry the same bits as N `lsq_per_group`
-    calls.  Saves {x_i, scale_i, shift_i}, as _LSQForeach does."""
+    """N group-wise quantizers of one dtype as ONE autograd node over the multi-tensor group kernels (the fused calls of
+    liblsq_hip_group.so): one launch per reduction class and per 28 tensors each way instead of N.  Every tensor is walked
+    by the workgroups of its own single call, so outputs and gradients carry the same bits as N `lsq_per_group` calls.
+    Saves {x_i, scale_i, shift_i}, as _LSQForeach does."""
 
     @staticmethod
     def forward(ctx, cfg, n, *tensors):

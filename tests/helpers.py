@@ -1,7 +1,11 @@
-"""Shared comparison helpers for the parity tests."""
+"""Shared helpers of the tests: bitwise and reduction comparisons, and the gfx950 kernels of a built library."""
 import hashlib
+import os
+import re
+import subprocess
 
 import numpy as np
+import pytest
 
 TOL = 1e-6   # north_star: dequantized output and gradients within 1e-6 relative of the reference CPU path
 
@@ -37,3 +41,36 @@ def assert_reduction_close(got, want, abs_terms, what, tol=TOL):
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+
+def gfx950_kernels(lib, tmp):
+    """{kernel symbol: (disassembly text, private segment bytes)} for every gfx950 kernel of the shared library `lib`: its
+    code objects are pulled out of the .hip_fatbin section, unbundled and disassembled with the ROCm LLVM tools (no GPU
+    needed) in the directory `tmp`.  Skips the calling test when the tools are missing."""
+    for tool in ("clang-offload-bundler", "llvm-objdump", "llvm-readelf"):
+        if not os.path.isfile(os.path.join(LLVM, tool)):
+            pytest.skip("ROCm LLVM tool %s not found" % tool)
+    fat = os.path.join(tmp, "fat.bin")
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
+    assert starts, "no offload bundle in %s" % os.path.basename(lib)
+    out = {}
+    for i, s in enumerate(starts):
+        part = os.path.join(tmp, "bundle%d.bin" % i)
+        with open(part, "wb") as f:
+            f.write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+        co = os.path.join(tmp, "dev%d.co" % i)
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        asm = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+        meta = {m.group(1): int(m.group(2)) for m in
+                re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, re.S)}
+        for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", asm, re.S | re.M):
+            if m.group(1) in meta:
+                out[m.group(1)] = (m.group(2), meta[m.group(1)])
+    return out

@@ -11,44 +11,19 @@ tools (no GPU needed):
 """
 import os
 import re
-import subprocess
 
 import pytest
 
+from helpers import gfx950_kernels
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "lsqfakequantize-pytorch_amd", "torchlsq", "liblsq_hip.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
     """{kernel symbol: (disassembly text, metadata dict)} for every gfx950 kernel in the library."""
-    for tool in ("clang-offload-bundler", "llvm-objdump", "llvm-readelf"):
-        if not os.path.isfile(os.path.join(LLVM, tool)):
-            pytest.skip("ROCm LLVM tool %s not found" % tool)
-    tmp = tmp_path_factory.mktemp("devcode")
-    fat = str(tmp / "fat.bin")
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", LIB, fat], check=True)
-    blob = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-    assert starts, "no offload bundle in liblsq_hip.so"
-    out = {}
-    for i, s in enumerate(starts):
-        part = str(tmp / ("bundle%d.bin" % i))
-        with open(part, "wb") as f:
-            f.write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-        co = str(tmp / ("dev%d.co" % i))
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-        asm = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-        meta = {}
-        for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, re.S):
-            meta[m.group(1)] = int(m.group(2))
-        for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", asm, re.S | re.M):
-            if m.group(1) in meta:
-                out[m.group(1)] = (m.group(2), meta[m.group(1)])
+    out = gfx950_kernels(LIB, str(tmp_path_factory.mktemp("devcode")))
     assert len(out) > 100, "expected the whole kernel table, found %d kernels" % len(out)
     return out
 

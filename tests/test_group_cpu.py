@@ -1,6 +1,7 @@
 """CPU: the group-wise ops (include/lsq_hip_group.h, liblsq_hip_group.so, torchlsq.functional.lsq_per_group) without a GPU.
 
-  * the group library exports exactly what its header declares, nothing named lsq_hip_*, and reads no environment;
+  * the group library exports exactly what its header declares (the single and the fused calls), ABI 2, nothing named
+    lsq_hip_*, and reads no environment;
   * its gfx950 code objects follow the main library's device-code rules (tests/test_device_code.py);
   * argument validation and the launch plan, host only;
   * the CPU op is, bit for bit, the oracle's per-channel op on the [numel // G, G] view;
@@ -15,13 +16,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_bits_equal, assert_reduction_close
+from helpers import assert_bits_equal, assert_reduction_close, gfx950_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lsq_hip_group.h")
 LIB = os.path.join(ROOT, "lsqfakequantize-pytorch_amd", "torchlsq", "liblsq_hip_group.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
 def _declared():
@@ -29,50 +28,31 @@ def _declared():
     return sorted(set(re.findall(r"\b(lsq_\w+)\s*\(", text)))
 
 
-def test_group_library_exports_its_header_only():
+def test_group_library_exports_its_eight_entry_points():
     from torchlsq import extension as E
     names = _declared()
     assert names == sorted(["lsq_group_abi_version", "lsq_group_last_error", "lsq_group_forward", "lsq_group_backward",
-                            "lsq_group_plan"])
+                            "lsq_group_plan", "lsq_group_multi_forward", "lsq_group_multi_backward", "lsq_group_multi_plan"])
     assert sorted(E.C_ABI_GROUP) == names
     nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
     exported = sorted(set(l.split()[-1] for l in nm.splitlines() if " T " in l and l.split()[-1].startswith("lsq_")))
     assert exported == names
     assert "lsq_hip_" not in nm and "debug" not in nm
     und = subprocess.run(["nm", "-D", "--undefined-only", LIB], capture_output=True, text=True, check=True).stdout
-    assert "getenv" not in und and "lsq_hip_" not in und
+    assert "getenv" not in und and "lsq_hip_" not in und and "lsq_group_" not in und
     lib = E.group_library()
-    assert lib.lsq_group_abi_version() == E.GROUP_ABI_VERSION == 1
+    assert lib.lsq_group_abi_version() == E.GROUP_ABI_VERSION == 2
+    assert re.search(r"#define LSQ_GROUP_MULTI_ITEMS (\d+)", open(HEADER).read()).group(1) == str(E.GROUP_MULTI_ITEMS)
     # the main library's ABI is untouched: its ctypes table has no group symbol
     assert not [n for n in E.C_ABI if "group" in n]
 
 
 @pytest.fixture(scope="module")
 def group_kernels(tmp_path_factory):
-    for tool in ("clang-offload-bundler", "llvm-objdump", "llvm-readelf"):
-        if not os.path.isfile(os.path.join(LLVM, tool)):
-            pytest.skip("ROCm LLVM tool %s not found" % tool)
-    tmp = tmp_path_factory.mktemp("grpcode")
-    fat = str(tmp / "fat.bin")
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", LIB, fat], check=True)
-    blob = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-    assert starts
-    out = {}
-    for i, s in enumerate(starts):
-        part = str(tmp / ("bundle%d.bin" % i))
-        with open(part, "wb") as f:
-            f.write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-        co = str(tmp / ("dev%d.co" % i))
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-        asm = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-        meta = {m.group(1): int(m.group(2)) for m in
-                re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)", notes, re.S)}
-        for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", asm, re.S | re.M):
-            if m.group(1) in meta:
-                out[m.group(1)] = (m.group(2), meta[m.group(1)])
+    every = gfx950_kernels(LIB, str(tmp_path_factory.mktemp("grpcode")))
+    # the library holds the single-tensor kernels and the fused calls' (tests/test_group_foreach_cpu.py), nothing else
+    assert all(re.search(r"(fwd|bwd)_grp_(multi_)?kernel", n) for n in every), sorted(every)
+    out = {n: v for n, v in every.items() if "_grp_kernel" in n}
     # 4 storage types x (forward: init x levels x form = 8; backward: 6 mode combinations x 3 reductions = 18)
     assert len([n for n in out if "fwd_grp_kernel" in n]) == 32 and len([n for n in out if "bwd_grp_kernel" in n]) == 72, sorted(out)
     return out

@@ -1,4 +1,4 @@
-"""GPU: the fused group-wise calls (liblsq_hip_group_multi.so -> torchlsq.functional.lsq_foreach_per_group,
+"""GPU: the fused group-wise calls (lsq_group_multi_* -> torchlsq.functional.lsq_foreach_per_group,
 LSQWeightGroup(group_wise=True)).
 
 The contract: lsq_foreach_per_group(xs, ss, bs, Gs, ...) == [lsq_per_group(x, s, b, G, ...) for ...] bit for bit -- y, dx,
