@@ -262,7 +262,7 @@ int lsq_hip_backward_per_channel_multi(int dtype, const lsq_pc_item* items, int3
  *           instantiation (0: not asked), kernel family -- 1 = 256-lane windows, 2 = row-group windows, 3 = segment walk,
  *           4 = owner windows (one launch, no workspace) --, LDS-DMA ring depth (0 = register loops), workgroup size,
  *           ring copies issued with the streaming hint]
- * It is the plan the launch itself is made from (lsq_per_channel.hip, plan_backward; the sizes of
+ * It is the plan the launch itself is made from (lsq_pc_plan.hpp, plan_backward; the sizes of
  * lsq_hip_backward_per_channel_workspace come from the same plans), so a test on the SHIPPED library can tell which kernel
  * family a shape runs without a debug build (tests/test_shipped_binary_gpu.py).
  * Depends on the current device (CU count, the instantiation's register count): needs a GPU. */

@@ -200,7 +200,7 @@ inline int resident_blocks_per_cu(const void* kernel, size_t lds_bytes) {
     return n;
 }
 
-// what a per-channel launch looks like: part of its plan (lsq_per_channel.hip, plan_forward / plan_backward), reported by
+// what a per-channel launch looks like: part of its plan (lsq_pc_plan.hpp, plan_forward / plan_backward), reported by
 // lsq_hip_plan_backward_per_channel (production and tools build alike) and -- tools build only -- kept per thread for the
 // last real launch (lsq_hip_debug_last_launch)
 struct LaunchNote {

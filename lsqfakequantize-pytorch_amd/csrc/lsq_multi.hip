@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void bwd_multi_kernel(const MultiArgs<typen
                                                                    it.shift, r, it.gs, nullptr, 0, direct);
 }
 
-// packets in flight per lane: as the single-tensor segment kernels (lsq_per_channel.hip kSegUnroll)
+// packets in flight per lane: as the single-tensor segment kernels (lsq_pc_plan.hpp kSegUnroll)
 template <typename IO>
 constexpr int kMultiUnroll = sizeof(typename IO::elem) < 4 ? 1 : 4;
 

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(kBlock) void minmax_pc_kernel(const void* __restric
             if (valid) r[j].push(v);
         }
     };
-    // rows = full groups of UNROLL + one group of UNROLL/2 + ... + one single row (no padded slots, see lsq_per_channel.hip)
+    // rows = full groups of UNROLL + one group of UNROLL/2 + ... + one single row (no padded slots, see lsq_pc_fwd.hpp)
     auto group = [&](int64_t i0, auto width) {
         constexpr int H = decltype(width)::value;
         E in[H][V];
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(kBlock) void moments_pc_kernel(const void* __restri
         for (int j = 0; j < V; ++j)
             if (valid) r[j].push(static_cast<double>(static_cast<T>(in[j])), pivot[j]);
     };
-    // rows = full groups of UNROLL + one group of UNROLL/2 + ... + one single row (no padded slots, see lsq_per_channel.hip)
+    // rows = full groups of UNROLL + one group of UNROLL/2 + ... + one single row (no padded slots, see lsq_pc_fwd.hpp)
     auto group = [&](int64_t i0, auto width) {
         constexpr int H = decltype(width)::value;
         E in[H][V];

@@ -297,7 +297,7 @@ struct OwnPlan {
 // min_run_bytes: the shortest run an owner may have (a run is what a workgroup reads of ONE row); the plan grows the channel
 // group until the run is that long.  The default is no minimum: short runs are fine on small tensors ([64,1024,5,5] fp32,
 // 400-byte runs: 11.3 -> 8.1 us; [256,2048,7] fp32, 112-byte runs: 16.7 -> 14.1 us) and it is the launch policy that keeps
-// them off larger ones (lsq_per_channel.hip, kOwnMaxElemsShortRun; profiles/r04_owner_min_run.txt).  Tools builds can set one.
+// them off larger ones (lsq_pc_plan.hpp, kOwnMaxElemsShortRun; profiles/r04_owner_min_run.txt).  Tools builds can set one.
 constexpr int kOwnMinRunBytes = 1;
 constexpr int kOwnFatDefault = 1;
 // one candidate: owners of k channels

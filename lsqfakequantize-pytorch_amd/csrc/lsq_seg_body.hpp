@@ -1,5 +1,5 @@
 // lsq_seg_body.hpp -- SEGMENT mode of the per-channel kernels: one workgroup walks (a segment of) ONE channel.
-// Shared by the single-tensor kernels (lsq_per_channel.hip: fwd_seg_kernel / bwd_seg_kernel, conv / linear weights on
+// Shared by the single-tensor kernels (lsq_pc_seg.hpp: fwd_seg_kernel / bwd_seg_kernel, conv / linear weights on
 // axis 0) and the multi-tensor kernels (lsq_multi.hip: many weight quantizers in one launch) -- the same walk, the same
 // summation order, hence the same bits.
 #pragma once

@@ -1,4 +1,4 @@
-"""GPU: a regression GATE on the per-channel backward's launch policy.  The thresholds of lsq_per_channel.hip were calibrated on a
+"""GPU: a regression GATE on the per-channel backward's launch policy.  The thresholds of lsq_pc_plan.hpp were calibrated on a
 handful of boxes (profiles/r04_policy_audit.txt); the driver's box is a fresh one every round.  For ~30 seeded (shape, storage
 type) cases -- NCHW activations, token layouts, conv / linear weights, NHWC -- the backward op is timed as the policy launches it
 and with every family-forcing knob of the tools build (tools/exp_policy_audit.py in small: HIP-graph replays over rotated

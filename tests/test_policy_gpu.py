@@ -1,4 +1,4 @@
-"""GPU: every size threshold of the per-channel launch policy (lsq_per_channel.hip: plan_forward, plan_bwd_pc,
+"""GPU: every size threshold of the per-channel launch policy (lsq_pc_plan.hpp: plan_forward, plan_bwd_pc,
 plan_backward; lsq_pc_geom.hpp) pinned from both sides: one shape just below and one just above it, fp32 and bf16
 storage, each held to the CPU oracle (y / dx bit-exact, d_scale / d_shift within 1e-6 of sum|terms|) -- and the launch note of
 the tools build (tools/lsq_tools.py) says which kernel family / loop form / workgroup size actually ran, so a threshold that
