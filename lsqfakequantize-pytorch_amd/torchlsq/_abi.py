@@ -1,5 +1,6 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
-(include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes) and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
+(include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
+ctypes) and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
 The module holds the loader STATE (`_LIB`, `_HAS_OPS`, `_CPU_LIB`, `_NATIVE_LSQ`); the host layers (_hip_host.py,
@@ -202,6 +203,29 @@ def group_library():
         raise RuntimeError("torchlsq: the group-wise ops need liblsq_hip_group.so, which could not be loaded (build it with "
                            "`python __graft_entry__.py`): %s" % group_error_str)
     return _GROUP_LIB
+
+
+# Packed 4- / 2-bit export of group-wise weights, and the way back (include/lsq_hip_pack.h): a third companion library; the
+# ABIs above stay as they are.
+PACK_ABI_VERSION = 1
+C_ABI_PACK = {
+    "lsq_pack_abi_version": (_int, []),
+    "lsq_pack_last_error": (ctypes.c_char_p, []),
+    "lsq_pack_quantize": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _PP, _int, _vp, _vp, _vp, _vp]),
+    "lsq_pack_dequantize": (_int, [_int, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "lsq_pack_unpack": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp]),
+    "lsq_pack_plan": (_int, [_int, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_PACK_LIB, pack_error_str = _load_companion("liblsq_hip_pack.so", C_ABI_PACK, "lsq_pack_abi_version", PACK_ABI_VERSION)
+
+
+def pack_library():
+    """The ctypes handle of liblsq_hip_pack.so (raises if it is missing)."""
+    _assert_has_ops()
+    if _PACK_LIB is None:
+        raise RuntimeError("torchlsq: the packed export ops need liblsq_hip_pack.so, which could not be loaded (build it with "
+                           "`python __graft_entry__.py`): %s" % pack_error_str)
+    return _PACK_LIB
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

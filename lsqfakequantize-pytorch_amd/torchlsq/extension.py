@@ -34,12 +34,13 @@ from ._hip_host import (_SINGLE_LAUNCH_BWD, _TICKET_SLABS, _TICKETS, _WS_BYTES_P
 from ._cpu_host import _cpu_meanstd, _cpu_minmax, cpu_backward, cpu_forward, cpu_levels, cpu_sharded_finish  # noqa: F401
 from ._group_host import (check_group_args, group_backward, group_backward_multi, group_forward,  # noqa: F401
                           group_forward_multi, group_multi_plan, group_plan)
+from ._pack_host import pack_dequantize, pack_plan, pack_quantize, pack_unpack  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str", "group_error_str",
-                "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str",
+                "group_error_str", "pack_error_str", "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
@@ -95,7 +96,14 @@ _lib_def.define("lsq_backward_per_group(Tensor grad, Tensor x, Tensor scale, Ten
                 ") -> (Tensor, Tensor, Tensor)")
 _lib_def.define("lsq_levels_per_group(Tensor x, Tensor scale, Tensor shift, int group_size, int quant_min, int quant_max, "
                 "int type_min, int type_max, int level_bias) -> Tensor")
-
+#  * packed export of group-wise weights (liblsq_hip_pack.so, include/lsq_hip_pack.h, which defines the format): the 4- / 2-bit
+#    codes of `lsq_forward_per_group`'s levels with one (scale, zero point) per group, and the two ways back -- the
+#    fake-quantized values, bit for bit those of the forward, and the one-byte levels of `lsq_levels_per_group`.
+_lib_def.define("lsq_pack_per_group(Tensor x, Tensor scale, Tensor shift, int group_size, int bits, int quant_min, "
+                "int quant_max, int type_min, int type_max) -> (Tensor, Tensor, Tensor)")
+_lib_def.define("lsq_unpack_per_group(Tensor codes, int bits, int quant_min, int level_bias) -> Tensor")
+_lib_def.define("lsq_dequantize_per_group(Tensor codes, Tensor scale, Tensor zero_point, int group_size, int bits, "
+                "ScalarType dtype) -> Tensor")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -383,6 +391,34 @@ def _backward_grp(ctx, grad_out):
 
 torch.library.register_autograd("torchlsq::lsq_forward_per_group", _backward_grp, setup_context=_setup_grp, lib=_lib_def)
 torch.library.register_autograd("torchlsq::lsq_backward_per_group", _no_double_backward("lsq_per_group"), lib=_lib_def)
+
+
+# -------------------------------------------------------------------------------------------------
+# the packed export ops (_pack_host.py): GPU tensors -> liblsq_hip_pack.so, CPU tensors -> cpu_levels + torch integer ops;
+# shape-only kernels.  Conversion-time ops on detached values: no autograd.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_pack_per_group", pack_quantize)
+    _lib_key.impl("lsq_unpack_per_group", pack_unpack)
+    _lib_key.impl("lsq_dequantize_per_group", pack_dequantize)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_pack_per_group", lib=_lib_def)
+def _fake_pack_grp(x, scale, shift, group_size, bits, *a):
+    return (torch.empty(x.shape[:-1] + (x.shape[-1] * bits // 8,), dtype=torch.uint8, device=x.device),
+            torch.empty(scale.shape, dtype=_param_dtype(x), device=x.device),
+            torch.empty(scale.shape, dtype=torch.int32, device=x.device))
+
+
+@torch.library.register_fake("torchlsq::lsq_unpack_per_group", lib=_lib_def)
+def _fake_unpack_grp(codes, bits, *a):
+    return torch.empty(codes.shape[:-1] + (codes.shape[-1] * (8 // bits),), dtype=torch.int8, device=codes.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_dequantize_per_group", lib=_lib_def)
+def _fake_dequantize_grp(codes, scale, zero_point, group_size, bits, dtype):
+    return torch.empty(codes.shape[:-1] + (codes.shape[-1] * (8 // bits),), dtype=dtype, device=codes.device)
 
 
 # -------------------------------------------------------------------------------------------------

@@ -526,3 +526,88 @@ def lsq_foreach_per_group(xs, scales, shifts, group_size,
         for i, y in zip(idx, ys):
             out[i] = y
     return out
+
+
+class PackedGroupTensor:
+    """A group-wise quantized weight in its deployment format (torch has no per-group quantized tensor; the layout is the
+    contract of include/lsq_hip_pack.h):
+
+        codes       uint8, shape[:-1] + (shape[-1] * bits / 8,): `bits`-bit codes (level - quant_min), little-endian inside
+                    the byte -- for 4 bits, element 0 is the low nibble
+        scale       max(|scale|, eps) per group (float32; float64 for a float64 weight)
+        zero_point  int32 per group, in code units (the forward's zero point minus quant_min)
+        bits, group_size, quant_min, shape
+
+    `dequantize(dtype)` is `(code - zero_point) * scale`: for the storage type the weight was packed from, the output of
+    `lsq_per_group` bit for bit, except that codes do not carry the sign of a zero (see `lsq_pack_per_group`).  `levels()` are the bytes of `lsq_levels_per_group`."""
+
+    def __init__(self, codes, scale, zero_point, bits, group_size, quant_min, shape):
+        self.codes, self.scale, self.zero_point = codes, scale, zero_point
+        self.bits, self.group_size, self.quant_min = int(bits), int(group_size), int(quant_min)
+        self.shape = torch.Size(shape)
+
+    def dequantize(self, dtype=None) -> Tensor:
+        """the fake-quantized weight in `dtype` (default: the scale's dtype), in the original shape"""
+        dtype = self.scale.dtype if dtype is None else dtype
+        return lsq_dequantize_per_group(self.codes, self.scale, self.zero_point, self.group_size, self.bits, dtype).reshape(self.shape)
+
+    def levels(self, dtype=torch.qint8) -> Tensor:
+        """the integer levels, one byte per element in the original shape: torch.int8 for torch.qint8, torch.uint8 for
+        torch.quint8 (as `lsq_levels_per_group`)"""
+        return lsq_unpack_per_group(self.codes, self.bits, self.quant_min, dtype).reshape(self.shape)
+
+    def state(self):
+        """a plain dict of tensors and ints, for torch.save / a checkpoint; `from_state` is the way back"""
+        return dict(codes=self.codes, scale=self.scale, zero_point=self.zero_point, bits=self.bits, group_size=self.group_size,
+                    quant_min=self.quant_min, shape=list(self.shape))
+
+    @classmethod
+    def from_state(cls, state):
+        return cls(state["codes"], state["scale"], state["zero_point"], state["bits"], state["group_size"], state["quant_min"],
+                   state["shape"])
+
+    def __repr__(self):
+        return "PackedGroupTensor(shape=%s, bits=%d, group_size=%d, quant_min=%d, device=%s)" % (
+            tuple(self.shape), self.bits, self.group_size, self.quant_min, self.codes.device)
+
+
+def lsq_pack_per_group(x: Tensor, scale: Tensor, shift: Tensor, group_size: int, bits: int,
+                       quant_min: int, quant_max: int,
+                       type_min: int = None,
+                       type_max: int = None) -> PackedGroupTensor:
+    """`x` under the group-wise quantizer (`scale`, `shift`, G = `group_size`: the arguments of `lsq_per_group`) as packed
+    `bits`-bit codes (4 or 2; quant_max - quant_min must fit, and G must be a multiple of 8 / bits): one pass over x that
+    writes bits / 8 bytes per element and the per-group constants.  The codes are the levels of `lsq_per_group`'s forward,
+    so `lsq_pack_per_group(...).dequantize(x.dtype)` equals `lsq_per_group(...)` as numbers, and bit for bit iff quant_min >= 0
+    or no group's zero point is +0.0.  Codes cannot carry the sign of a zero: with quant_min < 0 and a zero point of +0.0 --
+    -shift / scale in [+0.0, 0.5], which includes shift = -0.0 -- the forward gives -0.0 for positions in [-0.5, 0) and
+    dequantize gives +0.0.  A shift of +0.0 (zero point -0.0) or a non-zero integer zero point is bit-safe
+    (include/lsq_hip_pack.h)."""
+    _assert_has_ops()
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    group_size = int(group_size)
+    x, scale, shift = x.detach(), scale.detach(), shift.detach()
+    scale, shift = _group_params(x, scale, shift, group_size)
+    codes, qscale, qzero = torch.ops.torchlsq.lsq_pack_per_group(x, scale, shift, group_size, int(bits), quant_min, quant_max,
+                                                                 type_min, type_max)
+    return PackedGroupTensor(codes, qscale, qzero, bits, group_size, quant_min, x.shape)
+
+
+def lsq_dequantize_per_group(codes: Tensor, scale: Tensor, zero_point: Tensor, group_size: int, bits: int,
+                             dtype=torch.float32) -> Tensor:
+    """The fake-quantized values behind packed codes (`PackedGroupTensor.dequantize`): (code - zero_point) * scale per
+    group of `group_size` elements, as `dtype`, in the shape codes.shape[:-1] + (codes.shape[-1] * 8 / bits,)."""
+    _assert_has_ops()
+    return torch.ops.torchlsq.lsq_dequantize_per_group(codes, scale, zero_point, int(group_size), int(bits), dtype)
+
+
+def lsq_unpack_per_group(codes: Tensor, bits: int, quant_min: int, dtype=torch.qint8) -> Tensor:
+    """The integer levels behind packed codes, one byte per element (`PackedGroupTensor.levels`): torch.int8 for
+    dtype=torch.qint8, torch.uint8 for torch.quint8 -- the bytes of `lsq_levels_per_group`."""
+    _assert_has_ops()
+    assert dtype in (torch.quint8, torch.qint8), "dtype must be torch.quint8 or torch.qint8"
+    lo, hi = (0, 255) if dtype == torch.quint8 else (-128, 127)
+    assert lo <= quant_min and quant_min + 2 ** int(bits) - 1 <= hi, "the quantized range must fit the quantized type"
+    levels = torch.ops.torchlsq.lsq_unpack_per_group(codes, int(bits), int(quant_min), 0)
+    return levels.view(torch.uint8) if dtype == torch.quint8 else levels

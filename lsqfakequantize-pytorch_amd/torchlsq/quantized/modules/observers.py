@@ -585,6 +585,32 @@ class LSQFakeQuantizer(ObserverBase):
             zp = torch.fmin(torch.full_like(s, tmax), torch.fmax(torch.full_like(s, tmin), -self.shift.detach() * (1.0 / s))).round()
         return levels.reshape(x.shape), s, zp.to(torch.int64)
 
+    def export_packed(self, x, bits=None):
+        """`x` under this trained group-wise quantizer in its deployment format: a `PackedGroupTensor` of 4- or 2-bit codes
+        with one (scale, zero point) per group (`torchlsq.functional.lsq_pack_per_group`), whose `.dequantize(x.dtype)` equals the
+        module's steady-state output `m(x)` as numbers, and bit for bit except the sign of a zero, which codes cannot carry:
+        this module gives a symmetric range with quant_min + quant_max of 0 or 1 (-7..7, -1..1) the shift -0.0, hence the zero point
+        +0.0, and `m(x)` is then -0.0 where x / scale lies in [-0.5, 0) while the dequantized value is +0.0; the ranges
+        -8..7 and -2..1 (shift +0.0) agree in every bit.  bits=None picks the smallest of {2, 4} that holds
+        quant_max - quant_min.  Only for `group_size` quantizers; wider ranges stay with `quantize()` (one byte per level)."""
+        from torchlsq.functional import lsq_pack_per_group
+        if self.group_size is None:
+            raise ValueError("export_packed() is for group-wise quantizers (group_size=...); use quantize() for a per-tensor or "
+                             "per-channel one")
+        assert self._initialized and self.scale is not None, "run the module on at least one batch before export_packed()"
+        span = self.quant_max - self.quant_min
+        if bits is None:
+            bits = 2 if span <= 3 else 4
+        if bits not in (2, 4) or span > 2 ** bits - 1:
+            raise ValueError("export_packed(): the range [%d, %d] does not fit %s-bit codes (packed export holds at most 4 "
+                             "bits); use quantize() for one byte per level" % (self.quant_min, self.quant_max, bits))
+        tmin, tmax = TYPES_RANGE_MAPPING[self.dtype]['range']
+        out, row = self._group_rows(x)
+        packed = lsq_pack_per_group(x.reshape(out, row), self.scale, self.shift, self.group_size, bits, self.quant_min,
+                                    self.quant_max, type_min=tmin, type_max=tmax)
+        packed.shape = torch.Size(x.shape)
+        return packed
+
     def _forward_groups(self, x, full_lsq, tmin, tmax):
         """the LSQ call of a group-wise weight quantizer: `lsq_per_group` on the [out, numel / out] view"""
         from torchlsq.functional import lsq_per_group

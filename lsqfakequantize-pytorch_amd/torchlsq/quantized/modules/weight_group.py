@@ -26,19 +26,20 @@ from .observers import LSQFakeQuantizer, TYPES_RANGE_MAPPING
 
 
 def _qat_weight_layers(model):
-    """(layer, quantizer) pairs whose forward calls `layer.weight_fake_quant(layer.weight)` with the plain weight"""
+    """(qualified name, layer, quantizer) triples whose forward calls `layer.weight_fake_quant(layer.weight)` with the plain weight"""
     import torch.ao.nn.qat as nnqat
     plain = tuple(getattr(nnqat, n) for n in ("Conv1d", "Conv2d", "Conv3d", "Linear", "Embedding", "EmbeddingBag") if hasattr(nnqat, n))
     out = []
-    for m in model.modules():
+    for name, m in model.named_modules():
         if type(m) in plain and isinstance(getattr(m, "weight_fake_quant", None), LSQFakeQuantizer):
-            out.append((m, m.weight_fake_quant))
+            out.append((name, m, m.weight_fake_quant))
     return out
 
 
 class LSQWeightGroup:
     def __init__(self, model, register_hook=True, group_wise=False):
-        self.pairs = _qat_weight_layers(model)
+        self.named_pairs = _qat_weight_layers(model)
+        self.pairs = [(layer, q) for _, layer, q in self.named_pairs]
         self.group_wise = bool(group_wise)      # also fuse the group-wise (group_size) quantizers
         self.handle = model.register_forward_pre_hook(self._pre_hook) if register_hook else None
         # results a layer did not pick up (a branch that did not run, an exception mid-forward) are dropped when the model's
@@ -47,6 +48,11 @@ class LSQWeightGroup:
         self.post_handle = model.register_forward_hook(self._post_hook, always_call=True) if register_hook else None
         self.last_fused = 0          # per-channel / per-tensor weights that went through the fused call at the last prequantize()
         self.last_fused_groups = 0   # group-wise weights that did (group_wise=True)
+
+    def export_packed(self, bits=None):
+        """{qualified module name: PackedGroupTensor} for every group-wise weight quantizer of the model
+        (`LSQFakeQuantizer.export_packed` of each layer's weight; export is a one-off, so one call per layer)"""
+        return {name: q.export_packed(layer.weight, bits) for name, layer, q in self.named_pairs if q.group_size is not None}
 
     def clear(self):
         for _, q in self.pairs:
