@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <unordered_map>
 
 #include <hip/hip_version.h>
@@ -372,6 +373,30 @@ void lsq_hip_debug_last_launch(int* out8) {
     const lsq::LaunchNote& n = lsq::last_launch_note();
     out8[0] = n.grid_x; out8[1] = n.grid_y; out8[2] = n.resident_per_cu; out8[3] = n.vgprs_hint;
     out8[4] = n.kind; out8[5] = n.dma_depth; out8[6] = n.block; out8[7] = n.ring_nt;
+}
+
+void lsq_hip_debug_launched_reset(void) {
+    lsq::LaunchedRecord& r = lsq::launched_record();
+    std::lock_guard<std::mutex> hold(r.lock);
+    r.kernels.clear();
+}
+
+int lsq_hip_debug_launched_names(char* buf, int cap) {
+    std::vector<const void*> kernels;
+    {
+        lsq::LaunchedRecord& r = lsq::launched_record();
+        std::lock_guard<std::mutex> hold(r.lock);
+        kernels = r.kernels;
+    }
+    std::string all;
+    for (const void* k : kernels) {
+        const char* name = hipKernelNameRefByPtr(k, nullptr);
+        if (!all.empty()) all += '\n';
+        all += name ? name : "?";
+    }
+    const int need = static_cast<int>(all.size()) + 1;
+    if (buf && cap >= need) std::memcpy(buf, all.c_str(), static_cast<size_t>(need));
+    return need;
 }
 #endif
 

@@ -51,6 +51,12 @@ void lsq_hip_debug_set_own(int v);
 void lsq_hip_debug_set_own_min_run(int v);
 /* owner windows: channel group of the plan -- 0 = the policy, 1 = the smallest that works, 2 = the largest that still gives every CU an owner */
 void lsq_hip_debug_set_own_fat(int v);
+/* Which per-channel kernels ran: a process-wide record (every thread's launches) of the forward / backward window and segment
+ * kernels and the finalizes (finalize_pc / finalize_ww / finalize_seg, two launch sites) since the last reset, each kernel once.  launched_names writes their mangled names, separated by
+ * newlines and NUL-terminated, into buf and returns the bytes that takes; when cap is smaller (or buf NULL) nothing is written
+ * and the return value is the size to ask again with. */
+void lsq_hip_debug_launched_reset(void);
+int lsq_hip_debug_launched_names(char* buf, int cap);
 /* tuning only: override the workgroups-per-CU of the observer-statistics kernels (0 = defaults) */
 void lsq_hip_debug_set_observe_wg_per_cu(int v);
 #ifdef __cplusplus

@@ -10,6 +10,9 @@
 #include <type_traits>
 #include <utility>
 #include <vector>
+#ifdef LSQ_TOOLS
+#include <mutex>
+#endif
 
 #include "../../include/lsq_hip.h"
 #include "lsq_math.hpp"
@@ -215,6 +218,26 @@ inline LaunchNote& last_launch_note() {
     thread_local LaunchNote note = {0, 0, 0, 0, 0, 0, 0, 0};
     return note;
 }
+// Which kernels ran: the host function pointers of the launches since the last reset, each once, in launch order.  One
+// record for the whole process behind a mutex (not per thread like the note above: a test reads it after calls that another
+// thread may have made); any launch site of any translation unit may join with LSQ_NOTE_LAUNCH.  lsq_hip_debug_launched_names
+// turns the pointers into kernel names.
+struct LaunchedRecord {
+    std::mutex lock;
+    std::vector<const void*> kernels;
+};
+inline LaunchedRecord& launched_record() {
+    static LaunchedRecord r;
+    return r;
+}
+inline void note_launched(const void* kernel) {
+    LaunchedRecord& r = launched_record();
+    std::lock_guard<std::mutex> hold(r.lock);
+    if (std::find(r.kernels.begin(), r.kernels.end(), kernel) == r.kernels.end()) r.kernels.push_back(kernel);
+}
+#define LSQ_NOTE_LAUNCH(kernel) ::lsq::note_launched(reinterpret_cast<const void*>(kernel))
+#else
+#define LSQ_NOTE_LAUNCH(kernel) ((void)0)
 #endif
 
 inline bool is_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -59,8 +59,13 @@ hipError_t forward_per_channel(const void* x, void* y, int64_t outer, int64_t ch
     const Range<T> r = make_range<T>(p);
     const T* sc = static_cast<const T*>(scale);
     const T* sh = static_cast<const T*>(shift);
-    if (pl.seg) hipLaunchKernelGGL(pl.seg, pl.grid, dim3(kBlock), 0, stream, x, y, levels, bias, aux_kind, pl.sg, sc, sh, r);
-    else hipLaunchKernelGGL(pl.win, pl.grid, dim3(kBlock), pl.lds, stream, x, y, levels, bias, aux_kind, pl.g, sc, sh, r);
+    if (pl.seg) {
+        LSQ_NOTE_LAUNCH(pl.seg);
+        hipLaunchKernelGGL(pl.seg, pl.grid, dim3(kBlock), 0, stream, x, y, levels, bias, aux_kind, pl.sg, sc, sh, r);
+    } else {
+        LSQ_NOTE_LAUNCH(pl.win);
+        hipLaunchKernelGGL(pl.win, pl.grid, dim3(kBlock), pl.lds, stream, x, y, levels, bias, aux_kind, pl.g, sc, sh, r);
+    }
     return hipGetLastError();
 }
 
@@ -94,16 +99,23 @@ hipError_t backward_per_channel(const void* grad, const void* x, void* dx, void*
     const bool direct = !pl.fin_win && !pl.fin_seg;     // no finalize follows: the kernel stores d_scale / d_shift
     if (pl.seg) {
         const SegDirect<T> sd{direct ? dsT : nullptr, dbT, wide, sym_term};
+        LSQ_NOTE_LAUNCH(pl.seg);
         hipLaunchKernelGGL(pl.seg, pl.grid, dim3(kBlock), 0, stream, grad, x, dx, pl.sg, sc, sh, r, gs, partials, sd);
     } else {
         const PcDirect<T> pd = direct ? PcDirect<T>{dsT, dbT, wide, sym_term, p.sym ? 1 : 0} : PcDirect<T>{nullptr, nullptr, nullptr, sym_term, 0};
+        LSQ_NOTE_LAUNCH(pl.win);
         hipLaunchKernelGGL(pl.win, pl.grid, dim3(pl.g.block_threads), pl.lds, stream, grad, x, dx, pl.g, sc, sh, r, gs, partials, pd);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || direct) return e;
     const int eval = p.eval_mode ? 1 : 0, sym = p.sym ? 1 : 0;
-    if (pl.seg) hipLaunchKernelGGL(pl.fin_seg, pl.fin_grid, dim3(kBlock), 0, stream, partials, pl.sg, pl.fin_ch, eval, sym, sym_term, dsT, dbT, wide);
-    else hipLaunchKernelGGL(pl.fin_win, pl.fin_grid, dim3(kBlock), 0, stream, partials, pl.g, pl.fin_ch, eval, sym, sym_term, dsT, dbT, wide);
+    if (pl.seg) {
+        LSQ_NOTE_LAUNCH(pl.fin_seg);
+        hipLaunchKernelGGL(pl.fin_seg, pl.fin_grid, dim3(kBlock), 0, stream, partials, pl.sg, pl.fin_ch, eval, sym, sym_term, dsT, dbT, wide);
+    } else {
+        LSQ_NOTE_LAUNCH(pl.fin_win);
+        hipLaunchKernelGGL(pl.fin_win, pl.fin_grid, dim3(kBlock), 0, stream, partials, pl.g, pl.fin_ch, eval, sym, sym_term, dsT, dbT, wide);
+    }
     return hipGetLastError();
 }
 

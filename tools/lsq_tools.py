@@ -36,6 +36,8 @@ def internal_abi():
               "set_observe_wg_per_cu", "set_ww_max_log2", "set_seg_min_div", "set_fwd_direct", "set_seg_no_up_front", "set_own", "set_own_min_run", "set_own_fat"):
         tab["lsq_hip_debug_" + n] = (None, [_int])
     tab["lsq_hip_debug_last_launch"] = (None, [ctypes.POINTER(ctypes.c_int * 8)])
+    tab["lsq_hip_debug_launched_reset"] = (None, [])
+    tab["lsq_hip_debug_launched_names"] = (_int, [ctypes.c_char_p, _int])
     return tab
 
 
@@ -108,3 +110,21 @@ def last_launch():
     _state["lib"].lsq_hip_debug_last_launch(ctypes.byref(out))
     return dict(grid_x=out[0], grid_y=out[1], resident_per_cu=out[2], vgprs=out[3], kind=KINDS.get(out[4], "?"),
                 ring_depth=out[5], block=out[6], ring_nt=out[7])
+
+
+def launched_reset():
+    """Forget which per-channel kernels the tools library has launched so far (a process-wide record, every thread's)."""
+    _state["lib"].lsq_hip_debug_launched_reset()
+
+
+def launched():
+    """The mangled names of the per-channel kernels (forward / backward window and segment kernels, the three finalize kernels) that the
+    tools library launched since the last launched_reset(), as a set."""
+    lib = _state["lib"]
+    cap = lib.lsq_hip_debug_launched_names(None, 0)
+    while True:
+        buf = ctypes.create_string_buffer(cap)
+        need = lib.lsq_hip_debug_launched_names(buf, cap)
+        if need <= cap:
+            return set(n for n in buf.value.decode().split("\n") if n)
+        cap = need
