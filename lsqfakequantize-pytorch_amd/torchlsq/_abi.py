@@ -228,6 +228,29 @@ def pack_library():
     return _PACK_LIB
 
 
+# The linear layer that reads packed weights in place (include/lsq_hip_qlinear.h): a fourth companion library; the ABIs above
+# stay as they are.
+QLINEAR_ABI_VERSION = 1
+QLINEAR_MAX_ROWS = 16           # LSQ_QLINEAR_MAX_ROWS: rows of x one launch serves
+C_ABI_QLINEAR = {
+    "lsq_qlinear_abi_version": (_int, []),
+    "lsq_qlinear_last_error": (ctypes.c_char_p, []),
+    "lsq_qlinear_forward": (_int, [_int, _vp, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp]),
+    "lsq_qlinear_plan": (_int, [_int, _i64, _i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_QLINEAR_LIB, qlinear_error_str = _load_companion("liblsq_hip_qlinear.so", C_ABI_QLINEAR, "lsq_qlinear_abi_version",
+                                                    QLINEAR_ABI_VERSION)
+
+
+def qlinear_library():
+    """The ctypes handle of liblsq_hip_qlinear.so (raises if it is missing)."""
+    _assert_has_ops()
+    if _QLINEAR_LIB is None:
+        raise RuntimeError("torchlsq: the packed linear op needs liblsq_hip_qlinear.so, which could not be loaded (build it "
+                           "with `python __graft_entry__.py`): %s" % qlinear_error_str)
+    return _QLINEAR_LIB
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -35,12 +35,13 @@ from ._cpu_host import _cpu_meanstd, _cpu_minmax, cpu_backward, cpu_forward, cpu
 from ._group_host import (check_group_args, group_backward, group_backward_multi, group_forward,  # noqa: F401
                           group_forward_multi, group_multi_plan, group_plan)
 from ._pack_host import pack_dequantize, pack_plan, pack_quantize, pack_unpack  # noqa: F401
+from ._qlinear_host import qlinear_forward, qlinear_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str",
-                "group_error_str", "pack_error_str", "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str",
+                "group_error_str", "pack_error_str", "qlinear_error_str", "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
@@ -104,6 +105,10 @@ _lib_def.define("lsq_pack_per_group(Tensor x, Tensor scale, Tensor shift, int gr
 _lib_def.define("lsq_unpack_per_group(Tensor codes, int bits, int quant_min, int level_bias) -> Tensor")
 _lib_def.define("lsq_dequantize_per_group(Tensor codes, Tensor scale, Tensor zero_point, int group_size, int bits, "
                 "ScalarType dtype) -> Tensor")
+#  * a linear layer on the packed weight (liblsq_hip_qlinear.so, include/lsq_hip_qlinear.h): y = x @ w^T (+ bias) read from the
+#    codes, for x of [..., K] and codes of [N, K * bits / 8].  Inference only.
+_lib_def.define("lsq_linear_packed(Tensor x, Tensor codes, Tensor scale, Tensor zero_point, Tensor? bias, int group_size, "
+                "int bits) -> Tensor")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -419,6 +424,32 @@ def _fake_unpack_grp(codes, bits, *a):
 @torch.library.register_fake("torchlsq::lsq_dequantize_per_group", lib=_lib_def)
 def _fake_dequantize_grp(codes, scale, zero_point, group_size, bits, dtype):
     return torch.empty(codes.shape[:-1] + (codes.shape[-1] * (8 // bits),), dtype=dtype, device=codes.device)
+
+
+# -------------------------------------------------------------------------------------------------
+# the linear op on packed weights (_qlinear_host.py): GPU tensors -> liblsq_hip_qlinear.so (up to 16 rows of x; more rows
+# dequantize and call F.linear), CPU tensors -> torch; a shape-only kernel.  Inference only: the autograd key refuses an x
+# (or bias) that wants a gradient instead of cutting the graph without a word.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_packed", qlinear_forward)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed", lib=_lib_def)
+def _fake_linear_packed(x, codes, scale, zero_point, bias, group_size, bits):
+    return torch.empty(x.shape[:-1] + (codes.shape[0],), dtype=x.dtype, device=x.device)
+
+
+def _linear_packed_no_grad(x, codes, scale, zero_point, bias, group_size, bits):
+    if torch.is_grad_enabled() and (x.requires_grad or (bias is not None and bias.requires_grad)):
+        raise RuntimeError("lsq_linear_packed is inference-only: x (or the bias) requires grad.  Run it under torch.no_grad() "
+                           "or detach the input; train with the fake-quantized layer (lsq_per_group), not with packed codes")
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_linear_packed(x, codes, scale, zero_point, bias, group_size, bits)
+
+
+_lib_def.impl("lsq_linear_packed", _linear_packed_no_grad, "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

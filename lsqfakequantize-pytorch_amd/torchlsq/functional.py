@@ -556,6 +556,10 @@ class PackedGroupTensor:
         torch.quint8 (as `lsq_levels_per_group`)"""
         return lsq_unpack_per_group(self.codes, self.bits, self.quant_min, dtype).reshape(self.shape)
 
+    def linear(self, x: Tensor, bias: Tensor = None) -> Tensor:
+        """`x @ dequantize().T (+ bias)` computed from the codes (`lsq_linear_packed`): no dequantized weight is written"""
+        return lsq_linear_packed(x, self, bias)
+
     def state(self):
         """a plain dict of tensors and ints, for torch.save / a checkpoint; `from_state` is the way back"""
         return dict(codes=self.codes, scale=self.scale, zero_point=self.zero_point, bits=self.bits, group_size=self.group_size,
@@ -611,3 +615,19 @@ def lsq_unpack_per_group(codes: Tensor, bits: int, quant_min: int, dtype=torch.q
     assert lo <= quant_min and quant_min + 2 ** int(bits) - 1 <= hi, "the quantized range must fit the quantized type"
     levels = torch.ops.torchlsq.lsq_unpack_per_group(codes, int(bits), int(quant_min), 0)
     return levels.view(torch.uint8) if dtype == torch.quint8 else levels
+
+
+def lsq_linear_packed(x: Tensor, packed: PackedGroupTensor, bias: Tensor = None) -> Tensor:
+    """A linear layer on a packed group-wise weight: `y[..., n] = sum_k x[..., k] * w[n, k] (+ bias[n])` with
+    `w = (code - zero_point) * scale` read straight from the 4- / 2-bit codes of `packed` (a 2-D weight [N, K], or any shape
+    viewed as [shape[0], numel / shape[0]] like the group-wise quantizer does).  x is bfloat16, float16 or float32; y has its
+    dtype.  Accumulation in float32, the bias (float32 or x's dtype) added in float32 before the one rounding; no atomics,
+    repeated calls are bit-identical.  On the GPU up to 16 rows of x (the product of its leading dims) run the native kernel
+    of liblsq_hip_qlinear.so -- the weight is streamed once, and row m of the result is bit for bit the 1-row call on x[m];
+    more rows (prefill) dequantize into a float32 temporary and call `torch.nn.functional.linear` in float32, which meets the same
+    accuracy bound but not that invariance.  Inference only: an x that requires grad under enabled grad mode raises."""
+    _assert_has_ops()
+    codes = packed.codes.reshape(packed.shape[0], -1) if packed.codes.dim() != 2 else packed.codes
+    groups = codes.size(0) * codes.size(1) * (8 // packed.bits) // packed.group_size
+    return torch.ops.torchlsq.lsq_linear_packed(x, codes, packed.scale.reshape(groups), packed.zero_point.reshape(groups), bias,
+                                                packed.group_size, packed.bits)
