@@ -251,6 +251,33 @@ def qlinear_library():
     return _QLINEAR_LIB
 
 
+# 8-bit activation levels on the packed codes (include/lsq_hip_qlinear_a8.h): a fifth companion library; the ABIs above stay as
+# they are.
+QLINEAR_A8_ABI_VERSION = 1
+QLINEAR_A8_MAX_ROWS = 16        # LSQ_QLINEAR_A8_MAX_ROWS: rows of x one launch serves
+LSQ_A8_U8, LSQ_A8_I8 = 0, 1     # level_dtype of lsq_qlinear_a8_forward_levels
+C_ABI_QLINEAR_A8 = {
+    "lsq_qlinear_a8_abi_version": (_int, []),
+    "lsq_qlinear_a8_last_error": (ctypes.c_char_p, []),
+    "lsq_qlinear_a8_forward_levels": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _int,
+                                             _vp]),
+    "lsq_qlinear_a8_forward": (_int, [_int, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp,
+                                      _int, _vp, _vp]),
+    "lsq_qlinear_a8_plan": (_int, [_i64, _i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_QLINEAR_A8_LIB, qlinear_a8_error_str = _load_companion("liblsq_hip_qlinear_a8.so", C_ABI_QLINEAR_A8, "lsq_qlinear_a8_abi_version",
+                                                          QLINEAR_A8_ABI_VERSION)
+
+
+def qlinear_a8_library():
+    """The ctypes handle of liblsq_hip_qlinear_a8.so (raises if it is missing)."""
+    _assert_has_ops()
+    if _QLINEAR_A8_LIB is None:
+        raise RuntimeError("torchlsq: the 8-bit-activation packed linear op needs liblsq_hip_qlinear_a8.so, which could not be "
+                           "loaded (build it with `python __graft_entry__.py`): %s" % qlinear_a8_error_str)
+    return _QLINEAR_A8_LIB
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -36,12 +36,13 @@ from ._group_host import (check_group_args, group_backward, group_backward_multi
                           group_forward_multi, group_multi_plan, group_plan)
 from ._pack_host import pack_dequantize, pack_plan, pack_quantize, pack_unpack  # noqa: F401
 from ._qlinear_host import qlinear_forward, qlinear_plan  # noqa: F401
+from ._qlinear_a8_host import qlinear_a8_forward, qlinear_a8_forward_levels, qlinear_a8_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_NATIVE_LSQ", "error_str", "cpu_error_str",
-                "group_error_str", "pack_error_str", "qlinear_error_str", "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
@@ -109,6 +110,13 @@ _lib_def.define("lsq_dequantize_per_group(Tensor codes, Tensor scale, Tensor zer
 #    codes, for x of [..., K] and codes of [N, K * bits / 8].  Inference only.
 _lib_def.define("lsq_linear_packed(Tensor x, Tensor codes, Tensor scale, Tensor zero_point, Tensor? bias, int group_size, "
                 "int bits) -> Tensor")
+#  * the same layer on 8-bit activation LEVELS, summed in integers (liblsq_hip_qlinear_a8.so, include/lsq_hip_qlinear_a8.h):
+#    _q8 takes the levels as uint8 / int8 bytes with s_x (float32) and zx (int32) as one-element tensors; _a8 takes a floating
+#    x and a per-tensor quantizer's scale, shift and range and forms the levels on the way.  Inference only.
+_lib_def.define("lsq_linear_packed_q8(Tensor x_levels, Tensor s_x, Tensor zx, Tensor codes, Tensor scale, Tensor zero_point, "
+                "Tensor? bias, int group_size, int bits, ScalarType out_dtype) -> Tensor")
+_lib_def.define("lsq_linear_packed_a8(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
+                "int type_max, Tensor codes, Tensor scale, Tensor zero_point, Tensor? bias, int group_size, int bits) -> Tensor")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -450,6 +458,52 @@ def _linear_packed_no_grad(x, codes, scale, zero_point, bias, group_size, bits):
 
 
 _lib_def.impl("lsq_linear_packed", _linear_packed_no_grad, "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the 8-bit-activation linear ops on packed weights (_qlinear_a8_host.py): GPU tensors -> liblsq_hip_qlinear_a8.so (16 rows
+# a launch; more rows are one launch per block of 16), CPU tensors -> torch int64 products; a
+# shape-only kernel each.  Inference only, like lsq_linear_packed.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_packed_q8", qlinear_a8_forward_levels)
+    _lib_key.impl("lsq_linear_packed_a8", qlinear_a8_forward)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed_q8", lib=_lib_def)
+def _fake_linear_packed_q8(x_levels, s_x, zx, codes, scale, zero_point, bias, group_size, bits, out_dtype):
+    return torch.empty(x_levels.shape[:-1] + (codes.shape[0],), dtype=out_dtype, device=x_levels.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed_a8", lib=_lib_def)
+def _fake_linear_packed_a8(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, codes, scale, zero_point, bias,
+                           group_size, bits):
+    return torch.empty(x.shape[:-1] + (codes.shape[0],), dtype=x.dtype, device=x.device)
+
+
+def _refuse_grad(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("%s is inference-only: an input requires grad.  Run it under torch.no_grad() or detach the input; "
+                           "train with the fake-quantized layers, not with packed codes and integer levels" % what)
+
+
+def _linear_packed_q8_no_grad(x_levels, s_x, zx, codes, scale, zero_point, bias, group_size, bits, out_dtype):
+    _refuse_grad("lsq_linear_packed_q8", s_x, bias)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_linear_packed_q8(x_levels, s_x, zx, codes, scale, zero_point, bias, group_size, bits, out_dtype)
+
+
+def _linear_packed_a8_no_grad(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, codes, scale, zero_point, bias,
+                              group_size, bits):
+    _refuse_grad("lsq_linear_packed_a8", x, act_scale, act_shift, bias)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_linear_packed_a8(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, codes,
+                                                       scale, zero_point, bias, group_size, bits)
+
+
+_lib_def.impl("lsq_linear_packed_q8", _linear_packed_q8_no_grad, "Autograd")
+_lib_def.impl("lsq_linear_packed_a8", _linear_packed_a8_no_grad, "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

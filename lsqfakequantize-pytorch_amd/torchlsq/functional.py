@@ -560,6 +560,11 @@ class PackedGroupTensor:
         """`x @ dequantize().T (+ bias)` computed from the codes (`lsq_linear_packed`): no dequantized weight is written"""
         return lsq_linear_packed(x, self, bias)
 
+    def linear_a8(self, x: Tensor, bias: Tensor = None, scale: Tensor = None, shift: Tensor = None, quant_min: int = None,
+                  quant_max: int = None, type_min: int = None, type_max: int = None, out_dtype=None) -> Tensor:
+        """the same layer on the 8-bit levels of a per-tensor activation quantizer, summed in integers (`lsq_linear_packed_a8`)"""
+        return lsq_linear_packed_a8(x, self, bias, scale, shift, quant_min, quant_max, type_min, type_max, out_dtype)
+
     def state(self):
         """a plain dict of tensors and ints, for torch.save / a checkpoint; `from_state` is the way back"""
         return dict(codes=self.codes, scale=self.scale, zero_point=self.zero_point, bits=self.bits, group_size=self.group_size,
@@ -631,3 +636,38 @@ def lsq_linear_packed(x: Tensor, packed: PackedGroupTensor, bias: Tensor = None)
     groups = codes.size(0) * codes.size(1) * (8 // packed.bits) // packed.group_size
     return torch.ops.torchlsq.lsq_linear_packed(x, codes, packed.scale.reshape(groups), packed.zero_point.reshape(groups), bias,
                                                 packed.group_size, packed.bits)
+
+
+def lsq_linear_packed_a8(x: Tensor, packed: PackedGroupTensor, bias: Tensor = None, scale: Tensor = None, shift: Tensor = None,
+                         quant_min: int = None, quant_max: int = None, type_min: int = None, type_max: int = None,
+                         out_dtype=None) -> Tensor:
+    """`lsq_linear_packed` on QUANTIZED activations (W4A8 / W2A8): with lx the 8-bit level of an activation, zx its zero point
+    and s_x its scale, `y[..., n] = s_x * sum_g scale[n, g] * I[..., n, g] (+ bias[n])` where
+    `I = sum_{k in g} (lx[k] - zx) * (code[n, k] - zero_point[n, g])` is an exact integer, converted to float32 once per group.
+
+    * floating x (bfloat16, float16 or float32) with the per-tensor quantizer's `scale` and `shift` (float32 tensors of one
+      value), `quant_min`, `quant_max` and optionally the type's range: the levels are those of
+      `lsq(x, scale, shift, ...)` -- formed inside the kernel on the GPU, no quantized copy of x is written -- and y has x's
+      dtype.  Equal, bit for bit, to the second form on `lsq_levels_per_tensor`'s bytes.
+    * a per-tensor `torch.quint8` / `torch.qint8` tensor as x (e.g. `m.quantize(x)`) with `out_dtype` (default float32): its
+      `int_repr()`, `q_scale()` and `q_zero_point()` are used; scale, shift and the range arguments are ignored.
+
+    No atomics; repeated calls are bit-identical; on the GPU up to 16 rows run the native kernel of
+    liblsq_hip_qlinear_a8.so and row m of the result is bit for bit the 1-row call.  More rows take the same kernel 16 at
+    a time, one launch per block of rows: the same bits, the weight streamed once per block.  Inference only."""
+    _assert_has_ops()
+    codes = packed.codes.reshape(packed.shape[0], -1) if packed.codes.dim() != 2 else packed.codes
+    groups = codes.size(0) * codes.size(1) * (8 // packed.bits) // packed.group_size
+    w = (codes, packed.scale.reshape(groups), packed.zero_point.reshape(groups), bias, packed.group_size, packed.bits)
+    if x.is_quantized:
+        assert x.qscheme() in (torch.per_tensor_affine, torch.per_tensor_symmetric) and x.dtype in (torch.quint8, torch.qint8), \
+            "lsq_linear_packed_a8 needs a per-tensor torch.quint8 / torch.qint8 tensor"
+        s_x = torch.tensor([x.q_scale()], dtype=torch.float32, device=x.device)
+        zx = torch.tensor([x.q_zero_point()], dtype=torch.int32, device=x.device)
+        return torch.ops.torchlsq.lsq_linear_packed_q8(x.int_repr(), s_x, zx, *w, torch.float32 if out_dtype is None else out_dtype)
+    assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
+        "lsq_linear_packed_a8 on a floating x needs the activation quantizer's scale, shift, quant_min and quant_max"
+    assert out_dtype is None or out_dtype == x.dtype, "a floating x gives y of x's dtype"
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    return torch.ops.torchlsq.lsq_linear_packed_a8(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w)

@@ -11,6 +11,7 @@ from torch.ao.quantization import FakeQuantize as _FakeQuantize
 from .modules.observers import LSQFakeQuantizer
 from .modules.weight_group import LSQWeightGroup  # noqa: F401
 from .modules.packed_linear import PackedLinear, convert_packed  # noqa: F401
+from .modules.packed_linear_a8 import PackedLinearA8, convert_packed_a8  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
@@ -107,4 +108,5 @@ def prepare_ddp(model, process_group=None, grads="mean"):
     return model
 
 
-__all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "convert_packed", "enable_rank_sync", "prepare_ddp"] + [row[0] for row in _TABLE]
+__all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "PackedLinearA8", "convert_packed", "convert_packed_a8",
+           "enable_rank_sync", "prepare_ddp"] + [row[0] for row in _TABLE]
