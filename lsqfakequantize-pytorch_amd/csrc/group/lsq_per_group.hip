@@ -19,6 +19,7 @@
 //    item's lane, and the part of a group that continues into the next pass is carried in a wave-uniform register.
 // All indexing is 64-bit (tensors and group counts beyond 2^31).
 #include "lsq_grp_body.hpp"
+#include "../lsq_companion_abi.hpp"
 
 namespace lsq {
 
@@ -128,20 +129,7 @@ static hipError_t backward_per_group(const lsq_group_item& item, const lsq_param
 // ------------------------------------------------------------------------------------------------
 // the C ABI of include/lsq_hip_group.h, all eight entry points: validation, dtype dispatch, error bookkeeping
 // ------------------------------------------------------------------------------------------------
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
-
-thread_local char g_group_error[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_group_error, sizeof(g_group_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 // LSQ_EINVAL, "what: message" for a single call (item < 0), "what: item <i>: message" for an item of a fused call
 int fail_item(const char* what, int item, const char* fmt, ...) {
@@ -153,16 +141,6 @@ int fail_item(const char* what, int item, const char* fmt, ...) {
     if (item < 0) return fail(LSQ_EINVAL, "%s: %s", what, msg);
     return fail(LSQ_EINVAL, "%s: item %d: %s", what, item, msg);
 }
-
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return LSQ_OK;
-    return fail(static_cast<int>(e), "%s: %s (%s)", what, hipGetErrorName(e), hipGetErrorString(e));
-}
-
-int io_vec(int dtype) { return dtype == LSQ_F32 ? 4 : dtype == LSQ_F64 ? 2 : 8; }
-uintptr_t elem_bytes(int dtype) { return dtype == LSQ_F64 ? 8 : (dtype == LSQ_F32 ? 4 : 2); }
-uintptr_t param_bytes(int dtype) { return dtype == LSQ_F64 ? 8 : 4; }
-bool aligned_to(const void* a, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(a) & (bytes - 1)) == 0; }
 
 int check_dtype(int dtype, const char* what) {
     if (dtype < LSQ_F32 || dtype > LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
@@ -233,7 +211,7 @@ extern "C" {
 
 int lsq_group_abi_version(void) { return LSQ_GROUP_ABI_VERSION; }
 
-const char* lsq_group_last_error(void) { return g_group_error; }
+const char* lsq_group_last_error(void) { return g_last_error; }
 
 int lsq_group_forward(int dtype, const void* x, void* y, int64_t n, int64_t group_size, const void* scale, const void* shift,
                       const lsq_params* p, const lsq_fwd_extras* extras, void* stream) {

@@ -19,6 +19,7 @@
 // The arithmetic is lsq_math.hpp's: level() for the codes, make_qparams for the constants, and (c - qzero) * qscale rounded
 // by out_elem like the forward's dequant() -- compiled with -ffp-contract=off like everything else.
 #include "../group/lsq_grp_body.hpp"
+#include "../lsq_companion_abi.hpp"
 #include "../../../include/lsq_hip_pack.h"
 
 namespace lsq {
@@ -254,8 +255,6 @@ inline PackPlan plan_pack(int vec, int64_t n, int64_t G, int bits) {
     return pl;
 }
 
-inline bool aligned_to(const void* a, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(a) & (bytes - 1)) == 0; }
-
 template <typename IO, int BITS>
 static hipError_t quantize_packed(const void* x, int64_t n, int64_t G, const void* scale, const void* shift, const lsq_params& p,
                                   void* codes, void* qscale, void* qzero, hipStream_t stream) {
@@ -319,29 +318,7 @@ static hipError_t unpack_packed(const void* codes, int64_t n, int offset, void* 
 // ------------------------------------------------------------------------------------------------
 // the C ABI of include/lsq_hip_pack.h: validation, dtype dispatch, error bookkeeping
 // ------------------------------------------------------------------------------------------------
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
-
-thread_local char g_pack_error[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_pack_error, sizeof(g_pack_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return LSQ_OK;
-    return fail(static_cast<int>(e), "%s: %s (%s)", what, hipGetErrorName(e), hipGetErrorString(e));
-}
-
-int io_vec(int dtype) { return dtype == LSQ_F32 ? 4 : dtype == LSQ_F64 ? 2 : 8; }
-uintptr_t elem_bytes(int dtype) { return dtype == LSQ_F64 ? 8 : (dtype == LSQ_F32 ? 4 : 2); }
-uintptr_t param_bytes(int dtype) { return dtype == LSQ_F64 ? 8 : 4; }
 
 constexpr int32_t kTypeLimit = 1 << 23;
 
@@ -377,7 +354,7 @@ extern "C" {
 
 int lsq_pack_abi_version(void) { return LSQ_PACK_ABI_VERSION; }
 
-const char* lsq_pack_last_error(void) { return g_pack_error; }
+const char* lsq_pack_last_error(void) { return g_last_error; }
 
 int lsq_pack_quantize(int dtype, const void* x, int64_t n, int64_t group_size, const void* scale, const void* shift,
                       const lsq_params* p, int bits, void* codes, void* qscale, void* qzero, void* stream) {
@@ -397,9 +374,9 @@ int lsq_pack_quantize(int dtype, const void* x, int64_t n, int64_t group_size, c
         return fail(LSQ_EINVAL, "%s: numel_for_scaler must be 0 (there is no sharded group op), got %lld", what,
                     static_cast<long long>(p->numel_for_scaler));
     if (!x || !scale || !shift || !codes || !qscale || !qzero) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
-    if (!lsq::aligned_to(x, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: x must be element-aligned", what);
-    if (!lsq::aligned_to(scale, param_bytes(dtype)) || !lsq::aligned_to(shift, param_bytes(dtype)) ||
-        !lsq::aligned_to(qscale, param_bytes(dtype)) || !lsq::aligned_to(qzero, 4))
+    if (!aligned_to(x, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: x must be element-aligned", what);
+    if (!aligned_to(scale, param_bytes(dtype)) || !aligned_to(shift, param_bytes(dtype)) ||
+        !aligned_to(qscale, param_bytes(dtype)) || !aligned_to(qzero, 4))
         return fail(LSQ_EINVAL, "%s: scale, shift, qscale and qzero must be element-aligned", what);
     if (n == 0) return LSQ_OK;
     hipError_t e = hipSuccess;
@@ -413,8 +390,8 @@ int lsq_pack_dequantize(int dtype, const void* codes, int64_t n, int64_t group_s
     const char* what = "lsq_pack_dequantize";
     if (int rc = check_layout(dtype, n, group_size, bits, what)) return rc;
     if (!codes || !qscale || !qzero || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
-    if (!lsq::aligned_to(y, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: y must be element-aligned", what);
-    if (!lsq::aligned_to(qscale, param_bytes(dtype)) || !lsq::aligned_to(qzero, 4))
+    if (!aligned_to(y, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: y must be element-aligned", what);
+    if (!aligned_to(qscale, param_bytes(dtype)) || !aligned_to(qzero, 4))
         return fail(LSQ_EINVAL, "%s: qscale and qzero must be element-aligned", what);
     if (n == 0) return LSQ_OK;
     hipError_t e = hipSuccess;

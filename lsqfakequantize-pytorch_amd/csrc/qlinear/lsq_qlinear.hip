@@ -1,40 +1,23 @@
 // lsq_qlinear.hip -- y = x @ w^T (+ bias) on packed 4- / 2-bit group-wise weights for up to 16 rows of x on gfx950
 // (include/lsq_hip_qlinear.h, which states the arithmetic contract; the weight format is include/lsq_hip_pack.h's): the
-// kernels and the C ABI of liblsq_hip_qlinear.so.
-//
-// The op is a stream over the codes -- N * K * bits / 8 bytes, the only large traffic -- with x (at most 16 x K) kept close.
+// kernels and the C ABI of liblsq_hip_qlinear.so.  lsq_qdecode.hpp has the design both decode linears share -- tile
+// ownership, K split by wave, the transpose, the order of the sum -- and its pieces; particular to float x:
 //  * MATRIX-CORE form (bf16 / fp16 x, G a multiple of the BE = 128 / bits elements of one 16-byte code packet, codes 16-byte
-//    aligned).  A workgroup of 16 waves owns a tile of 16 output columns (rows of w) and walks the tiles in a persistent grid;
-//    its waves split K: step s -- 4 packets = 4 * BE consecutive k of each of the 16 rows -- belongs to wave s % 16, so the
-//    order of the sum never depends on M.  Per step a lane (row n = lane & 15, q = lane >> 4) loads packet 4 s + q of its
-//    row with one non-temporal global_load_dwordx4 (2 steps per wave in flight at 4 bits, 1 at 2 bits, issued before x is
-//    staged), and four v_permlane{32,16}_swap transpose the 4 x 4 dwords of the lanes (n, 0..3): afterwards dword t of lane
-//    (n, q) is dword q of packet 4 s + t, so the 32 k of one mfma_f32_16x16x32 lie in ONE packet and with it in one group.
-//    x is the A operand (row m = lane & 15), read from LDS as 16 bytes per lane and MFMA: x is staged there in chunks of
-//    4096 k, rows padded by 16 bytes against bank conflicts; rows m >= M are zero registers.  The B operand is the integer
-//    code - qzero as bf16 / fp16 -- exact for -128 <= qzero <= 128; a packet where any of the wave's 16 rows has a qzero
-//    beyond that splits |code - qzero| into three exact 8-bit pieces and runs three MFMAs (the format allows +-2^23).  The
-//    packet's fp32 partial tile is folded into the accumulator with one multiply by the column's qscale.  The 16 waves'
-//    tiles are summed through LDS in wave order, the bias is added in fp32, and the result is rounded once.
-//  * GENERIC form (fp32 x, any other G, misaligned codes): one wave per output column, one code byte per lane and step,
-//    w = float(code - qzero) * qscale and one fp32 multiply-add per (row of x, element), a butterfly over the wave.
-//    Rows of x go four at a time.  Correct for every legal format; not tuned.
-#include "../group/lsq_grp_body.hpp"
-#include "../../../include/lsq_hip_qlinear.h"
+//    aligned).  Load step s of a chunk belongs to wave s % 16: 2 steps per wave in flight at 4 bits, 1 at 2 bits, issued
+//    before x is staged.  x is the A operand of mfma_f32_16x16x32 (row m = lane & 15), 16 bytes per lane and MFMA read
+//    from LDS, where it is staged as it is in chunks of 4096 k; rows m >= M are zero registers.  The B operand is the
+//    integer code - qzero as bf16 / fp16 -- exact for -128 <= qzero <= 128; a packet where any of the wave's 16 rows has a
+//    qzero beyond that splits |code - qzero| into three exact 8-bit pieces and runs three MFMAs (the format allows
+//    +-2^23).  The packet's fp32 partial tile is folded into the accumulator with one multiply by the column's qscale.
+//    After the sum over the waves the bias is added in fp32, and the result is rounded once.
+//  * GENERIC form (fp32 x, any other G, misaligned codes): one code byte per lane and step, w = float(code - qzero) * qscale
+//    and one fp32 multiply-add per (row of x, element), a butterfly over the wave.
+#include "lsq_qdecode.hpp"
 
 namespace lsq {
 
-constexpr int kQWaves = 16;                         // waves that share one output tile (matrix-core form)
-constexpr int kQBlock = kQWaves * 64;
-constexpr int kQTile = 16;                          // output columns per tile
-constexpr int kQChunk = 4096;                       // elements of K per LDS chunk of x
-constexpr int kQRowStride = kQChunk * 2 + 16;       // bytes between rows of x in LDS: 4 banks further per row
-constexpr int kQRedBytes = kQWaves * 64 * 16;       // one fp32 x 4 accumulator per lane and wave
-constexpr int kQGenericRowsAtOnce = 4;
+constexpr int kQRowStride = kQChunk * 2 + kQRowPad; // bytes between rows of x in LDS
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
@@ -48,25 +31,10 @@ template <> struct MatOp<io_f16> {
     __device__ static __forceinline__ f32x4 mfma(vec a, vec b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 };
 
-// the 4 x 4 transpose of r[t] over the lanes (n, q = 0..3) = lane n + 16 q: afterwards r[t] of lane q is what r[q] of lane t was
-__device__ __forceinline__ void transpose_over_rows(uint32_t (&r)[4]) {
-    u32x2 p;
-    p = __builtin_amdgcn_permlane32_swap(r[0], r[2], false, false); r[0] = p.x; r[2] = p.y;    // lanes 32..63 of r[0] <-> 0..31 of r[2]
-    p = __builtin_amdgcn_permlane32_swap(r[1], r[3], false, false); r[1] = p.x; r[3] = p.y;
-    p = __builtin_amdgcn_permlane16_swap(r[0], r[1], false, false); r[0] = p.x; r[1] = p.y;    // odd rows of r[0] <-> even rows of r[1]
-    p = __builtin_amdgcn_permlane16_swap(r[2], r[3], false, false); r[2] = p.x; r[3] = p.y;
-}
-
 // the j-th of the 8 codes of MFMA h of one dword
 template <int BITS>
 __device__ __forceinline__ int code_at(uint32_t w, int h, int j) {
     return static_cast<int>((w >> (h * 8 * BITS + j * BITS)) & ((1u << BITS) - 1u));
-}
-
-template <typename IO>
-__device__ __forceinline__ float bias_at(const void* bias, int bias_f32, int64_t n) {
-    if (!bias) return 0.0f;
-    return bias_f32 ? static_cast<const float*>(bias)[n] : IO::load1(bias, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -113,17 +81,9 @@ __global__ __launch_bounds__(kQBlock) void qlinear_mfma_kernel(const void* __res
             for (int u = 0; u < U; ++u) {
                 const int64_t p0 = (c * kSteps + u * kQWaves + wave) * 4;
                 raw[u] = u32x4{0u, 0u, 0u, 0u};
-                if (p0 + q < n_packets) raw[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow + (p0 + q) * 16));
+                if (p0 + q < n_packets) raw[u] = load_code_packet(wrow, p0 + q);
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    qsv[u][t] = 0.0f;
-                    qzv[u][t] = 0;
-                    if (p0 + t < n_packets) {
-                        const int64_t g = bpg_shift >= 0 ? ((p0 + t) >> bpg_shift) : bpg.div(p0 + t);
-                        qsv[u][t] = qs_row[g];
-                        qzv[u][t] = qz_row[g];
-                    }
-                }
+                for (int t = 0; t < 4; ++t) load_packet_scale(qs_row, qz_row, p0 + t, n_packets, bpg_shift, bpg, qsv[u][t], qzv[u][t]);
             }
             if (n_chunks > 1 || tile == first_tile) {       // x stays in LDS across tiles when one chunk holds it
                 __syncthreads();
@@ -275,8 +235,7 @@ inline QLinearPlan plan_qlinear(int dtype, int64_t M, int64_t N, int64_t K, int6
         pl.waves = kQWaves;
         pl.cols = kQTile;
         pl.packets_per_group = G / packet_elems;
-        // one workgroup of 16 waves per compute unit: the kernel's registers leave room for 4 waves per SIMD
-        pl.grid = static_cast<int>(std::min(std::max<int64_t>(1, (N + kQTile - 1) / kQTile), cus));
+        pl.grid = mfma_grid(N, cus);
     } else {
         pl.block = kBlock;
         pl.lds = 0;
@@ -284,31 +243,18 @@ inline QLinearPlan plan_qlinear(int dtype, int64_t M, int64_t N, int64_t K, int6
         pl.waves = 1;
         pl.cols = 1;
         pl.packets_per_group = 0;
-        const int64_t per_block = kBlock / 64;
-        pl.grid = static_cast<int>(std::min(std::max<int64_t>(1, (N + per_block - 1) / per_block), cus * 8));
+        pl.grid = generic_grid(N, cus);
     }
     return pl;
-}
-
-inline bool q_aligned_to(const void* a, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(a) & (bytes - 1)) == 0; }
-
-// the matrix-core kernel may use more LDS than the 64 KiB a kernel gets unasked: said once per kernel and device
-template <typename IO, int BITS>
-static hipError_t allow_lds() {
-    static std::atomic<int> ready[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (ready[dev].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qlinear_mfma_kernel<IO, BITS>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kQRedBytes + LSQ_QLINEAR_MAX_ROWS * kQRowStride);
-    if (e == hipSuccess) ready[dev].store(1, std::memory_order_release);
-    return e;
 }
 
 template <typename IO, int BITS>
 static hipError_t qlinear_mfma(const QLinearPlan& pl, const void* x, int64_t M, const void* codes, int64_t N, int64_t K, int64_t G,
                                const void* qscale, const void* qzero, const void* bias, int bias_f32, void* y, hipStream_t stream) {
-    if (const hipError_t e = allow_lds<IO, BITS>()) return e;
+    static LdsOnce once;
+    if (const hipError_t e = allow_lds(once, reinterpret_cast<const void*>(&qlinear_mfma_kernel<IO, BITS>),
+                                       kQRedBytes + LSQ_QLINEAR_MAX_ROWS * kQRowStride))
+        return e;
     hipLaunchKernelGGL((qlinear_mfma_kernel<IO, BITS>), dim3(pl.grid), dim3(pl.block), pl.lds, stream, x, static_cast<int>(M),
                        static_cast<const uint8_t*>(codes), N, K, K / G, log2_exact(pl.packets_per_group), make_div(pl.packets_per_group),
                        static_cast<const float*>(qscale), static_cast<const int32_t*>(qzero), bias, bias_f32, y);
@@ -329,44 +275,11 @@ static hipError_t qlinear_generic(const QLinearPlan& pl, const void* x, int64_t 
 // ------------------------------------------------------------------------------------------------
 // the C ABI of include/lsq_hip_qlinear.h: validation, dtype dispatch, error bookkeeping
 // ------------------------------------------------------------------------------------------------
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
 
-thread_local char g_qlinear_error[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_qlinear_error, sizeof(g_qlinear_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return LSQ_OK;
-    return fail(static_cast<int>(e), "%s: %s (%s)", what, hipGetErrorName(e), hipGetErrorString(e));
-}
-
-uintptr_t elem_bytes(int dtype) { return dtype == LSQ_F32 ? 4 : 2; }
-
 int check_shape(int dtype, int64_t M, int64_t N, int64_t K, int64_t G, int bits, const char* what) {
-    if (dtype == LSQ_F64)
-        return fail(LSQ_EINVAL, "%s: float64 is not supported (a packed weight with a float64 scale has no GPU linear)", what);
-    if (dtype != LSQ_F32 && dtype != LSQ_BF16 && dtype != LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
-    if (bits != 4 && bits != 2) return fail(LSQ_EINVAL, "%s: bits must be 4 or 2, got %d", what, bits);
-    const long long m = M, n = N, k = K, g = G;
-    if (G <= 0) return fail(LSQ_EINVAL, "%s: group_size must be positive, got %lld", what, g);
-    if (N < 0 || K < 0) return fail(LSQ_EINVAL, "%s: negative weight shape [%lld, %lld]", what, n, k);
-    if (K % G != 0) return fail(LSQ_EINVAL, "%s: K = %lld is not a multiple of group_size %lld", what, k, g);
-    if (G % (8 / bits) != 0)
-        return fail(LSQ_EINVAL, "%s: group_size %lld is not a multiple of %d, the elements of one byte of %d-bit codes", what, g,
-                    8 / bits, bits);
-    if (M < 1 || M > LSQ_QLINEAR_MAX_ROWS)
-        return fail(LSQ_EINVAL, "%s: M = %lld rows of x, the kernel serves 1 to %d (dequantize and call a GEMM beyond that)", what, m,
-                    LSQ_QLINEAR_MAX_ROWS);
-    return LSQ_OK;
+    return check_shape(dtype, M, N, K, G, bits, what, "a packed weight with a float64 scale has no GPU linear",
+                       "dequantize and call a GEMM beyond that");
 }
 
 }  // namespace
@@ -382,7 +295,7 @@ extern "C" {
 
 int lsq_qlinear_abi_version(void) { return LSQ_QLINEAR_ABI_VERSION; }
 
-const char* lsq_qlinear_last_error(void) { return g_qlinear_error; }
+const char* lsq_qlinear_last_error(void) { return g_last_error; }
 
 int lsq_qlinear_forward(int dtype, const void* x, int64_t M, const void* codes, int64_t N, int64_t K, int64_t group_size, int bits,
                         const void* qscale, const void* qzero, const void* bias, int bias_dtype, void* y, void* stream) {
@@ -391,13 +304,13 @@ int lsq_qlinear_forward(int dtype, const void* x, int64_t M, const void* codes, 
     if (!x || !codes || !qscale || !qzero || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (bias && bias_dtype != LSQ_F32 && bias_dtype != dtype)
         return fail(LSQ_EINVAL, "%s: the bias must be float32 or of x's type, got dtype code %d", what, bias_dtype);
-    if (!lsq::q_aligned_to(x, elem_bytes(dtype)) || !lsq::q_aligned_to(y, elem_bytes(dtype)))
+    if (!aligned_to(x, elem_bytes(dtype)) || !aligned_to(y, elem_bytes(dtype)))
         return fail(LSQ_EINVAL, "%s: x and y must be element-aligned", what);
-    if (!lsq::q_aligned_to(qscale, 4) || !lsq::q_aligned_to(qzero, 4) || (bias && !lsq::q_aligned_to(bias, elem_bytes(bias_dtype))))
+    if (!aligned_to(qscale, 4) || !aligned_to(qzero, 4) || (bias && !aligned_to(bias, elem_bytes(bias_dtype))))
         return fail(LSQ_EINVAL, "%s: qscale, qzero and bias must be element-aligned", what);
     if (N == 0) return LSQ_OK;
     lsq::QLinearPlan pl = lsq::plan_qlinear(dtype, M, N, K, group_size, bits);
-    if (pl.mfma && !lsq::q_aligned_to(codes, 16)) pl = lsq::plan_qlinear(LSQ_F32, M, N, K, group_size, bits);   // the generic form
+    if (pl.mfma && !aligned_to(codes, 16)) pl = lsq::plan_qlinear(LSQ_F32, M, N, K, group_size, bits);   // the generic form
     const int bias_f32 = bias_dtype == LSQ_F32 ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipSuccess;
@@ -418,14 +331,7 @@ int lsq_qlinear_plan(int dtype, int64_t M, int64_t N, int64_t K, int64_t group_s
     if (int rc = check_shape(dtype, M, N, K, group_size, bits, what)) return rc;
     if (!out8) return fail(LSQ_EINVAL, "%s: NULL output", what);
     const lsq::QLinearPlan pl = lsq::plan_qlinear(dtype, M, N, K, group_size, bits);
-    out8[0] = pl.mfma ? 1 : 0;
-    out8[1] = pl.grid;
-    out8[2] = pl.block;
-    out8[3] = LSQ_QLINEAR_MAX_ROWS;
-    out8[4] = pl.lds;
-    out8[5] = pl.chunk;
-    out8[6] = pl.waves;
-    out8[7] = pl.cols;
+    lsq::write_plan8(out8, pl.mfma, pl.grid, pl.block, pl.lds, pl.chunk, pl.waves, pl.cols);
     return LSQ_OK;
 }
 

@@ -10,42 +10,28 @@
 // in integers: nothing cancels, and no property of the quantizer decides anything -- zx is read in the kernel.  The levels
 // come from memory (XLevels) or are formed from a floating x with lsq_math.hpp's make_qparams / level() while x is read
 // (XFloat): everything after that is the same code, so the two entry forms agree bit for bit.
+//
+// lsq_qdecode.hpp has the design both decode linears share -- tile ownership, K split by wave, the transpose, the order of
+// the sum -- and its pieces; particular to 8-bit levels:
 //  * MATRIX-CORE form (G a multiple of the BE = 128 / bits elements of one 16-byte code packet, lcm(G, 4 packets) <= 4096
-//    elements, codes 16-byte aligned).  A workgroup of 16 waves owns a tile of 16 output columns and walks the tiles in a
-//    persistent grid.  K is cut into SPANS of lcm(G, 4 BE) elements -- whole groups and whole load steps -- and span s of a
-//    chunk belongs to wave s % 16, so a group's integer sum stays in one wave and the order of the fp32 sum never depends on
-//    M.  Per load step a lane (row n = lane & 15, q = lane >> 4) loads packet 4 s + q of its row with one non-temporal
-//    global_load_dwordx4 (two steps in flight, the first two issued before x is staged), and four v_permlane{32,16}_swap
-//    transpose the 4 x 4 dwords of the lanes (n, 0..3) so that one MFMA reads one packet (or two adjacent ones of one group).
-//    The B operand of v_mfma_i32_16x16x64_i8 is the codes as the unsigned nibbles (crumbs) they are: a mask and a shift per
-//    dword.  An integer sum has no order, so x is laid out in LDS in that de-interleaved order and the A operand is one
-//    ds_read of 8 or 16 bytes.  A second MFMA with an all-ones A operand gives sum c.  x is staged once per workgroup and
-//    chunk (at most 4096 k) as the bytes a[m, k]; sum a - G z per (row, group) is formed from the staged bytes.  When a
+//    elements, codes 16-byte aligned).  K is cut into SPANS of lcm(G, 4 BE) elements -- whole groups and whole load steps --
+//    and span s of a chunk belongs to wave s % 16, so a group's integer sum stays in one wave.  Two load steps are in flight,
+//    the first two issued before x is staged; after the transpose one MFMA reads one packet (or two adjacent ones of one
+//    group).  The B operand of v_mfma_i32_16x16x64_i8 is the codes as the unsigned nibbles (crumbs) they are: a mask and a
+//    shift per dword.  An integer sum has no order, so x is laid out in LDS in that de-interleaved order and the A operand
+//    is one ds_read of 8 or 16 bytes.  A second MFMA with an all-ones A operand gives sum c.  x is staged once per workgroup
+//    and chunk (at most 4096 k) as the bytes a[m, k]; sum a - G z per (row, group) is formed from the staged bytes.  When a
 //    group ends, I is formed (32-bit when every |qzero| of the wave's columns is at most 256, else 64-bit), converted with
-//    one rounding and multiplied by qscale.  The 16 waves' tiles are summed through LDS in wave order, multiplied by s_x,
-//    the bias is added in fp32, and the result is rounded once.
-//  * GENERIC form (every other legal format): one wave per output column; the lanes of a segment of the wave share one
-//    group, multiply-add in 64-bit integers and sum with a butterfly; the segments' fp32 sums meet in a second butterfly.
-//    Rows of x go four at a time.  Correct for every legal format; not tuned.
-#include "../group/lsq_grp_body.hpp"
-#include "../../../include/lsq_hip_qlinear_a8.h"
+//    one rounding and multiplied by qscale.  After the sum over the waves the result is multiplied by s_x, the bias is
+//    added in fp32, and it is rounded once.
+//  * GENERIC form (every other legal format): the lanes of a segment of the wave share one group, multiply-add in 64-bit
+//    integers and sum with a butterfly; the segments' fp32 sums meet in a second butterfly.
+#include "../qlinear/lsq_qdecode.hpp"
 
 namespace lsq {
 
-constexpr int kAWaves = 16;                         // waves that share one output tile (matrix-core form)
-constexpr int kABlock = kAWaves * 64;
-constexpr int kATile = 16;                          // output columns per tile
-constexpr int kAChunkMax = 4096;                    // most elements of K per LDS chunk of x
-constexpr int kARowPad = 16;                        // bytes between rows of x in LDS beyond the chunk: 4 banks further per row
-constexpr int kARedBytes = kAWaves * 64 * 16;       // one fp32 x 4 accumulator per lane and wave
-constexpr int kAMaxLds = kARedBytes + LSQ_QLINEAR_A8_MAX_ROWS * (kAChunkMax + kARowPad) + LSQ_QLINEAR_A8_MAX_ROWS * (kAChunkMax / 32) * 4;
-constexpr int kAGenericRowsAtOnce = 4;
+constexpr int kAMaxLds = kQRedBytes + LSQ_QLINEAR_A8_MAX_ROWS * (kQChunk + kQRowPad) + LSQ_QLINEAR_A8_MAX_ROWS * (kQChunk / 32) * 4;
 constexpr int kAFastZero = 256;                     // |qzero| up to here: I fits 32 bits for every G of the matrix-core form
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // ------------------------------------------------------------------------------------------------
 // the activation: where a[m, k] comes from
@@ -98,12 +84,6 @@ struct XFloat {
     }
 };
 
-template <typename IO>
-__device__ __forceinline__ float a8_bias_at(const void* bias, int bias_f32, int64_t n) {
-    if (!bias) return 0.0f;
-    return bias_f32 ? static_cast<const float*>(bias)[n] : IO::load1(bias, n);
-}
-
 // ------------------------------------------------------------------------------------------------
 // matrix-core form
 // ------------------------------------------------------------------------------------------------
@@ -121,15 +101,6 @@ struct A8Geom {             // kernel argument: the cut of K (host: plan_a8)
     int row_stride;         // bytes between rows of x in LDS
     int gstride;            // groups per row of the LDS table of sum a - G z
 };
-
-// the 4 x 4 transpose of r[t] over the lanes (n, q = 0..3) = lane n + 16 q: afterwards r[t] of lane q is what r[q] of lane t was
-__device__ __forceinline__ void a8_transpose_over_rows(uint32_t (&r)[4]) {
-    u32x2 p;
-    p = __builtin_amdgcn_permlane32_swap(r[0], r[2], false, false); r[0] = p.x; r[2] = p.y;    // lanes 32..63 of r[0] <-> 0..31 of r[2]
-    p = __builtin_amdgcn_permlane32_swap(r[1], r[3], false, false); r[1] = p.x; r[3] = p.y;
-    p = __builtin_amdgcn_permlane16_swap(r[0], r[1], false, false); r[0] = p.x; r[1] = p.y;    // odd rows of r[0] <-> even rows of r[1]
-    p = __builtin_amdgcn_permlane16_swap(r[2], r[3], false, false); r[2] = p.x; r[3] = p.y;
-}
 
 // where element j of a block of 16 consecutive k lies in LDS: the order in which the masks and shifts below hand the codes
 // of a dword to the MFMA.  4 bits (8 codes per dword): the even codes, then the odd ones; 2 bits (16 codes per dword): codes
@@ -157,7 +128,7 @@ __device__ __forceinline__ int a8_sum_bytes(uint32_t w) {
 }
 
 template <typename XS, typename OUT, int BITS, bool PAIR>
-__global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int M, const uint8_t* __restrict__ codes, A8Geom geo,
+__global__ __launch_bounds__(kQBlock) void qlinear_a8_mfma_kernel(A8Act act, int M, const uint8_t* __restrict__ codes, A8Geom geo,
                                                                  const float* __restrict__ qscale, const int32_t* __restrict__ qzero,
                                                                  const void* __restrict__ bias, int bias_f32, void* __restrict__ y) {
     constexpr int D = 32 / BITS;                    // elements per dword
@@ -165,7 +136,7 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
     static_assert(!PAIR || BITS == 4, "two packets per MFMA only at 4 bits: a 2-bit packet is 64 elements already");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* red = reinterpret_cast<float*>(smem);
-    unsigned char* xs = smem + kARedBytes;
+    unsigned char* xs = smem + kQRedBytes;
     int32_t* aeff = reinterpret_cast<int32_t*>(xs + M * geo.row_stride);       // [M][gstride]: sum a - G z
 
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
@@ -175,12 +146,12 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
     const int64_t row_bytes = n_packets * 16;
     const int64_t n_chunks = (K + geo.chunk_k - 1) / geo.chunk_k;
     const int64_t chunk_p = static_cast<int64_t>(geo.chunk_spans) * geo.span_p;
-    const int64_t tiles = (N + kATile - 1) / kATile;
+    const int64_t tiles = (N + kQTile - 1) / kQTile;
     const int64_t first_tile = static_cast<int64_t>(blockIdx.x);
     const i32x4 ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
 
     for (int64_t tile = first_tile; tile < tiles; tile += static_cast<int64_t>(gridDim.x)) {
-        const int64_t row = std::min<int64_t>(tile * kATile + nl, N - 1);          // a clamped row computes a value nobody stores
+        const int64_t row = std::min<int64_t>(tile * kQTile + nl, N - 1);          // a clamped row computes a value nobody stores
         const uint8_t* __restrict__ wrow = codes + row * row_bytes;
         const float* __restrict__ qs_row = qscale + row * geo.n_groups;
         const int32_t* __restrict__ qz_row = qzero + row * geo.n_groups;
@@ -191,21 +162,14 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
             s.valid = cur.span < geo.chunk_spans && s.p0 < n_packets;
             s.raw = u32x4{0u, 0u, 0u, 0u};
             if (s.valid) {
-                if (s.p0 + q < n_packets) s.raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow + (s.p0 + q) * 16));
+                if (s.p0 + q < n_packets) s.raw = load_code_packet(wrow, s.p0 + q);
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    s.qs[t] = 0.0f;
-                    s.qz[t] = 0;
-                    if (s.p0 + t < n_packets) {
-                        const int64_t g = geo.ppg_shift >= 0 ? ((s.p0 + t) >> geo.ppg_shift) : geo.ppg_div.div(s.p0 + t);
-                        s.qs[t] = qs_row[g];
-                        s.qz[t] = qz_row[g];
-                    }
-                }
+                for (int t = 0; t < 4; ++t)
+                    load_packet_scale(qs_row, qz_row, s.p0 + t, n_packets, geo.ppg_shift, geo.ppg_div, s.qs[t], s.qz[t]);
             }
             if (++cur.l == geo.steps_per_span) {
                 cur.l = 0;
-                cur.span += kAWaves;
+                cur.span += kQWaves;
             }
         };
 
@@ -221,7 +185,7 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
                 __syncthreads();
                 const int kc_len = static_cast<int>(std::min<int64_t>(geo.chunk_k, K - kc0));
                 const int bpr = kc_len / 16;                // blocks of 16 k per row; exact, BE % 16 == 0
-                for (int it = tid; it < M * bpr; it += kABlock) {
+                for (int it = tid; it < M * bpr; it += kQBlock) {
                     const int m = it / bpr, b = it - m * bpr;
                     uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -234,7 +198,7 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
                 }
                 __syncthreads();
                 const int ng = kc_len / geo.G;              // groups of this chunk; exact
-                for (int it = tid; it < M * ng; it += kABlock) {
+                for (int it = tid; it < M * ng; it += kQBlock) {
                     const int m = it / ng, g = it - m * ng;
                     const unsigned char* src = xs + m * geo.row_stride + g * geo.G;
                     int sum = 0;
@@ -258,7 +222,7 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
                     pig = 0;
                 }
                 uint32_t r[4] = {s.raw.x, s.raw.y, s.raw.z, s.raw.w};
-                a8_transpose_over_rows(r);
+                transpose_over_rows(r);
                 constexpr int PER = PAIR ? 2 : 1;           // packets per MFMA
 #pragma unroll
                 for (int t = 0; t < 4; t += PER) {
@@ -315,7 +279,7 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
                 }
                 if (++cp.l == geo.steps_per_span) {
                     cp.l = 0;
-                    cp.span += kAWaves;
+                    cp.span += kQWaves;
                 }
             };
             while (s0.valid) {                              // the same for the whole wave
@@ -333,10 +297,10 @@ __global__ __launch_bounds__(kABlock) void qlinear_a8_mfma_kernel(A8Act act, int
             const int l = tid & 63, reg = tid >> 6;
             float sum = 0.0f;
 #pragma unroll
-            for (int w = 0; w < kAWaves; ++w) sum = sum + red[(w * 64 + l) * 4 + reg];
-            const int64_t n = tile * kATile + (l & 15);
+            for (int w = 0; w < kQWaves; ++w) sum = sum + red[(w * 64 + l) * 4 + reg];
+            const int64_t n = tile * kQTile + (l & 15);
             const int m = (l >> 4) * 4 + reg;
-            if (m < M && n < N) store_out<OUT, false>(y, static_cast<int64_t>(m) * N + n, sum * ac.s_x + a8_bias_at<OUT>(bias, bias_f32, n));
+            if (m < M && n < N) store_out<OUT, false>(y, static_cast<int64_t>(m) * N + n, sum * ac.s_x + bias_at<OUT>(bias, bias_f32, n));
         }
         __syncthreads();
     }
@@ -360,7 +324,7 @@ __global__ __launch_bounds__(kBlock) void qlinear_a8_generic_kernel(A8Act act, i
                                                                    const float* __restrict__ qscale, const int32_t* __restrict__ qzero,
                                                                    const void* __restrict__ bias, int bias_f32, void* __restrict__ y) {
     constexpr int PB = 8 / BITS;
-    constexpr int R = kAGenericRowsAtOnce;
+    constexpr int R = kQGenericRowsAtOnce;
     constexpr uint32_t kMask = (1u << BITS) - 1u;
     const int lane = static_cast<int>(threadIdx.x) & 63;
     const int seg_lanes = 1 << seg_shift, seg = lane >> seg_shift, sl = lane & (seg_lanes - 1);
@@ -408,7 +372,7 @@ __global__ __launch_bounds__(kBlock) void qlinear_a8_generic_kernel(A8Act act, i
             for (int i = 0; i < R; ++i) {
                 for (int s = seg_lanes; s <= 32; s <<= 1) acc[i] = acc[i] + __shfl_xor(acc[i], s, 64);     // the segments' sums
                 if (lane == 0 && m0 + i < M)
-                    store_out<OUT, false>(y, static_cast<int64_t>(m0 + i) * N + n, acc[i] * ac.s_x + a8_bias_at<OUT>(bias, bias_f32, n));
+                    store_out<OUT, false>(y, static_cast<int64_t>(m0 + i) * N + n, acc[i] * ac.s_x + bias_at<OUT>(bias, bias_f32, n));
             }
         }
     }
@@ -434,7 +398,7 @@ inline A8Plan plan_a8(int64_t M, int64_t N, int64_t K, int64_t G, int bits, bool
         const int64_t ppg = G / BE;
         span_p = ppg % 4 == 0 ? ppg : (ppg % 2 == 0 ? ppg * 2 : ppg * 4);      // lcm(ppg, 4)
     }
-    pl.mfma = aligned && span_p > 0 && span_p * BE <= kAChunkMax;
+    pl.mfma = aligned && span_p > 0 && span_p * BE <= kQChunk;
     if (pl.mfma) {
         A8Geom& g = pl.geo;
         g.N = N;
@@ -448,18 +412,17 @@ inline A8Plan plan_a8(int64_t M, int64_t N, int64_t K, int64_t G, int bits, bool
         g.span_p = static_cast<int>(span_p);
         g.steps_per_span = g.span_p / 4;
         g.groups_per_span = g.span_p / g.ppg;
-        g.chunk_spans = static_cast<int>(kAChunkMax / (span_p * BE));
+        g.chunk_spans = static_cast<int>(kQChunk / (span_p * BE));
         g.chunk_k = static_cast<int>(g.chunk_spans * span_p * BE);
         const int64_t held = std::max<int64_t>(BE, std::min<int64_t>(g.chunk_k, K));       // elements of one row in LDS
-        g.row_stride = static_cast<int>(held) + kARowPad;
+        g.row_stride = static_cast<int>(held) + kQRowPad;
         g.gstride = static_cast<int>(std::max<int64_t>(1, held / G));
         pl.pair = bits == 4 && g.ppg % 2 == 0;
-        pl.block = kABlock;
-        pl.lds = kARedBytes + static_cast<int>(M) * g.row_stride + static_cast<int>(M) * g.gstride * 4;
-        pl.waves = kAWaves;
-        pl.cols = kATile;
-        // one workgroup of 16 waves per compute unit
-        pl.grid = static_cast<int>(std::min(std::max<int64_t>(1, (N + kATile - 1) / kATile), cus));
+        pl.block = kQBlock;
+        pl.lds = kQRedBytes + static_cast<int>(M) * g.row_stride + static_cast<int>(M) * g.gstride * 4;
+        pl.waves = kQWaves;
+        pl.cols = kQTile;
+        pl.grid = mfma_grid(N, cus);
     } else {
         pl.block = kBlock;
         pl.lds = 0;
@@ -468,25 +431,9 @@ inline A8Plan plan_a8(int64_t M, int64_t N, int64_t K, int64_t G, int bits, bool
         pl.bytes_per_group = G / (8 / bits);
         pl.seg_shift = 0;
         while (pl.seg_shift < 6 && (int64_t{1} << pl.seg_shift) < pl.bytes_per_group) ++pl.seg_shift;
-        const int64_t per_block = kBlock / 64;
-        pl.grid = static_cast<int>(std::min(std::max<int64_t>(1, (N + per_block - 1) / per_block), cus * 8));
+        pl.grid = generic_grid(N, cus);
     }
     return pl;
-}
-
-inline bool a8_aligned_to(const void* a, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(a) & (bytes - 1)) == 0; }
-
-// the matrix-core kernel may use more LDS than the 64 KiB a kernel gets unasked: said once per kernel and device
-template <typename XS, typename OUT, int BITS, bool PAIR>
-static hipError_t a8_allow_lds() {
-    static std::atomic<int> ready[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (ready[dev].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qlinear_a8_mfma_kernel<XS, OUT, BITS, PAIR>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kAMaxLds);
-    if (e == hipSuccess) ready[dev].store(1, std::memory_order_release);
-    return e;
 }
 
 struct A8Weights {
@@ -499,7 +446,9 @@ struct A8Weights {
 
 template <typename XS, typename OUT, int BITS, bool PAIR>
 static hipError_t a8_launch_mfma(const A8Plan& pl, const A8Act& act, int64_t M, const A8Weights& w, void* y, hipStream_t stream) {
-    if (const hipError_t e = a8_allow_lds<XS, OUT, BITS, PAIR>()) return e;
+    static LdsOnce once;
+    if (const hipError_t e = allow_lds(once, reinterpret_cast<const void*>(&qlinear_a8_mfma_kernel<XS, OUT, BITS, PAIR>), kAMaxLds))
+        return e;
     hipLaunchKernelGGL((qlinear_a8_mfma_kernel<XS, OUT, BITS, PAIR>), dim3(pl.grid), dim3(pl.block), pl.lds, stream, act,
                        static_cast<int>(M), static_cast<const uint8_t*>(w.codes), pl.geo, static_cast<const float*>(w.qscale),
                        static_cast<const int32_t*>(w.qzero), w.bias, w.bias_f32, y);
@@ -531,43 +480,11 @@ static hipError_t a8_launch(const A8Plan& pl, const A8Act& act, int64_t M, const
 // ------------------------------------------------------------------------------------------------
 // the C ABI of include/lsq_hip_qlinear_a8.h: validation, dtype dispatch, error bookkeeping
 // ------------------------------------------------------------------------------------------------
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
 
-thread_local char g_a8_error[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_a8_error, sizeof(g_a8_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return LSQ_OK;
-    return fail(static_cast<int>(e), "%s: %s (%s)", what, hipGetErrorName(e), hipGetErrorString(e));
-}
-
-uintptr_t elem_bytes(int dtype) { return dtype == LSQ_F32 ? 4 : 2; }
-
 int check_shape(int dtype, int64_t M, int64_t N, int64_t K, int64_t G, int bits, const char* what) {
-    if (dtype == LSQ_F64) return fail(LSQ_EINVAL, "%s: float64 is not supported (the kernel computes in integers and float32)", what);
-    if (dtype != LSQ_F32 && dtype != LSQ_BF16 && dtype != LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
-    if (bits != 4 && bits != 2) return fail(LSQ_EINVAL, "%s: bits must be 4 or 2, got %d", what, bits);
-    const long long m = M, n = N, k = K, g = G;
-    if (G <= 0) return fail(LSQ_EINVAL, "%s: group_size must be positive, got %lld", what, g);
-    if (N < 0 || K < 0) return fail(LSQ_EINVAL, "%s: negative weight shape [%lld, %lld]", what, n, k);
-    if (K % G != 0) return fail(LSQ_EINVAL, "%s: K = %lld is not a multiple of group_size %lld", what, k, g);
-    if (G % (8 / bits) != 0)
-        return fail(LSQ_EINVAL, "%s: group_size %lld is not a multiple of %d, the elements of one byte of %d-bit codes", what, g,
-                    8 / bits, bits);
-    if (M < 1 || M > LSQ_QLINEAR_A8_MAX_ROWS)
-        return fail(LSQ_EINVAL, "%s: M = %lld rows of x, the kernel serves 1 to %d (dequantize the levels and call the prefill route "
-                    "beyond that)", what, m, LSQ_QLINEAR_A8_MAX_ROWS);
-    return LSQ_OK;
+    return check_shape(dtype, M, N, K, G, bits, what, "the kernel computes in integers and float32",
+                       "dequantize the levels and call the prefill route beyond that");
 }
 
 int check_weights(const char* what, int y_dtype, const void* codes, const void* qscale, const void* qzero, const void* bias,
@@ -575,8 +492,8 @@ int check_weights(const char* what, int y_dtype, const void* codes, const void* 
     if (!codes || !qscale || !qzero || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (bias && bias_dtype != LSQ_F32 && bias_dtype != y_dtype)
         return fail(LSQ_EINVAL, "%s: the bias must be float32 or of y's type, got dtype code %d", what, bias_dtype);
-    if (!lsq::a8_aligned_to(y, elem_bytes(y_dtype))) return fail(LSQ_EINVAL, "%s: x and y must be element-aligned", what);
-    if (!lsq::a8_aligned_to(qscale, 4) || !lsq::a8_aligned_to(qzero, 4) || (bias && !lsq::a8_aligned_to(bias, elem_bytes(bias_dtype))))
+    if (!aligned_to(y, elem_bytes(y_dtype))) return fail(LSQ_EINVAL, "%s: x and y must be element-aligned", what);
+    if (!aligned_to(qscale, 4) || !aligned_to(qzero, 4) || (bias && !aligned_to(bias, elem_bytes(bias_dtype))))
         return fail(LSQ_EINVAL, "%s: qscale, qzero and bias must be element-aligned", what);
     return LSQ_OK;
 }
@@ -597,7 +514,7 @@ extern "C" {
 
 int lsq_qlinear_a8_abi_version(void) { return LSQ_QLINEAR_A8_ABI_VERSION; }
 
-const char* lsq_qlinear_a8_last_error(void) { return g_a8_error; }
+const char* lsq_qlinear_a8_last_error(void) { return g_last_error; }
 
 int lsq_qlinear_a8_forward_levels(int level_dtype, const void* x_levels, int64_t M, const void* s_x, const void* zx, const void* codes,
                                   int64_t N, int64_t K, int64_t group_size, int bits, const void* qscale, const void* qzero,
@@ -608,9 +525,9 @@ int lsq_qlinear_a8_forward_levels(int level_dtype, const void* x_levels, int64_t
         return fail(LSQ_EINVAL, "%s: level_dtype must be LSQ_A8_U8 (0) or LSQ_A8_I8 (1), got %d", what, level_dtype);
     if (!x_levels || !s_x || !zx) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (int rc = check_weights(what, y_dtype, codes, qscale, qzero, bias, bias_dtype, y)) return rc;
-    if (!lsq::a8_aligned_to(s_x, 4) || !lsq::a8_aligned_to(zx, 4)) return fail(LSQ_EINVAL, "%s: s_x and zx must be element-aligned", what);
+    if (!aligned_to(s_x, 4) || !aligned_to(zx, 4)) return fail(LSQ_EINVAL, "%s: s_x and zx must be element-aligned", what);
     if (N == 0) return LSQ_OK;
-    const lsq::A8Plan pl = lsq::plan_a8(M, N, K, group_size, bits, lsq::a8_aligned_to(codes, 16));
+    const lsq::A8Plan pl = lsq::plan_a8(M, N, K, group_size, bits, aligned_to(codes, 16));
     lsq::A8Act act{};
     act.x = x_levels;
     act.scale = static_cast<const float*>(s_x);
@@ -634,11 +551,11 @@ int lsq_qlinear_a8_forward(int dtype, const void* x, int64_t M, const void* scal
                     static_cast<long long>(type_min), static_cast<long long>(type_max));
     if (!x || !scale || !shift) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (int rc = check_weights(what, dtype, codes, qscale, qzero, bias, bias_dtype, y)) return rc;
-    if (!lsq::a8_aligned_to(x, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: x and y must be element-aligned", what);
-    if (!lsq::a8_aligned_to(scale, 4) || !lsq::a8_aligned_to(shift, 4))
+    if (!aligned_to(x, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: x and y must be element-aligned", what);
+    if (!aligned_to(scale, 4) || !aligned_to(shift, 4))
         return fail(LSQ_EINVAL, "%s: scale and shift must be element-aligned", what);
     if (N == 0) return LSQ_OK;
-    const lsq::A8Plan pl = lsq::plan_a8(M, N, K, group_size, bits, lsq::a8_aligned_to(codes, 16));
+    const lsq::A8Plan pl = lsq::plan_a8(M, N, K, group_size, bits, aligned_to(codes, 16));
     lsq::A8Act act{};
     act.x = x;
     act.scale = static_cast<const float*>(scale);
@@ -664,14 +581,7 @@ int lsq_qlinear_a8_plan(int64_t M, int64_t N, int64_t K, int64_t group_size, int
     if (int rc = check_shape(LSQ_F32, M, N, K, group_size, bits, what)) return rc;
     if (!out8) return fail(LSQ_EINVAL, "%s: NULL output", what);
     const lsq::A8Plan pl = lsq::plan_a8(M, N, K, group_size, bits, true);
-    out8[0] = pl.mfma ? 1 : 0;
-    out8[1] = pl.grid;
-    out8[2] = pl.block;
-    out8[3] = LSQ_QLINEAR_A8_MAX_ROWS;
-    out8[4] = pl.lds;
-    out8[5] = pl.mfma ? pl.geo.chunk_k : 0;
-    out8[6] = pl.waves;
-    out8[7] = pl.cols;
+    lsq::write_plan8(out8, pl.mfma, pl.grid, pl.block, pl.lds, pl.mfma ? pl.geo.chunk_k : 0, pl.waves, pl.cols);
     return LSQ_OK;
 }
 

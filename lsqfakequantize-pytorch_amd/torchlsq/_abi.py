@@ -156,6 +156,15 @@ def _load_companion(name, table, version_fn, abi_version):
         return None, str(e)
 
 
+def _require_companion(lib, name, what, err):
+    """`lib`, the ctypes handle of the companion library `name`; raises when it is missing (`err`: why)"""
+    _assert_has_ops()
+    if lib is None:
+        raise RuntimeError("torchlsq: %s liblsq_hip_%s.so, which could not be loaded (build it with "
+                           "`python __graft_entry__.py`): %s" % (what, name, err))
+    return lib
+
+
 # The kernels for tensors in host memory (include/lsq_cpu.h): the counterpart of the reference's CPU dispatch.
 C_ABI_CPU = {
     "lsq_cpu_abi_version": (_int, []),
@@ -198,11 +207,7 @@ _GROUP_LIB, group_error_str = _load_companion("liblsq_hip_group.so", C_ABI_GROUP
 
 def group_library():
     """The ctypes handle of liblsq_hip_group.so (raises if it is missing)."""
-    _assert_has_ops()
-    if _GROUP_LIB is None:
-        raise RuntimeError("torchlsq: the group-wise ops need liblsq_hip_group.so, which could not be loaded (build it with "
-                           "`python __graft_entry__.py`): %s" % group_error_str)
-    return _GROUP_LIB
+    return _require_companion(_GROUP_LIB, "group", "the group-wise ops need", group_error_str)
 
 
 # Packed 4- / 2-bit export of group-wise weights, and the way back (include/lsq_hip_pack.h): a third companion library; the
@@ -221,11 +226,7 @@ _PACK_LIB, pack_error_str = _load_companion("liblsq_hip_pack.so", C_ABI_PACK, "l
 
 def pack_library():
     """The ctypes handle of liblsq_hip_pack.so (raises if it is missing)."""
-    _assert_has_ops()
-    if _PACK_LIB is None:
-        raise RuntimeError("torchlsq: the packed export ops need liblsq_hip_pack.so, which could not be loaded (build it with "
-                           "`python __graft_entry__.py`): %s" % pack_error_str)
-    return _PACK_LIB
+    return _require_companion(_PACK_LIB, "pack", "the packed export ops need", pack_error_str)
 
 
 # The linear layer that reads packed weights in place (include/lsq_hip_qlinear.h): a fourth companion library; the ABIs above
@@ -244,11 +245,7 @@ _QLINEAR_LIB, qlinear_error_str = _load_companion("liblsq_hip_qlinear.so", C_ABI
 
 def qlinear_library():
     """The ctypes handle of liblsq_hip_qlinear.so (raises if it is missing)."""
-    _assert_has_ops()
-    if _QLINEAR_LIB is None:
-        raise RuntimeError("torchlsq: the packed linear op needs liblsq_hip_qlinear.so, which could not be loaded (build it "
-                           "with `python __graft_entry__.py`): %s" % qlinear_error_str)
-    return _QLINEAR_LIB
+    return _require_companion(_QLINEAR_LIB, "qlinear", "the packed linear op needs", qlinear_error_str)
 
 
 # 8-bit activation levels on the packed codes (include/lsq_hip_qlinear_a8.h): a fifth companion library; the ABIs above stay as
@@ -271,11 +268,7 @@ _QLINEAR_A8_LIB, qlinear_a8_error_str = _load_companion("liblsq_hip_qlinear_a8.s
 
 def qlinear_a8_library():
     """The ctypes handle of liblsq_hip_qlinear_a8.so (raises if it is missing)."""
-    _assert_has_ops()
-    if _QLINEAR_A8_LIB is None:
-        raise RuntimeError("torchlsq: the 8-bit-activation packed linear op needs liblsq_hip_qlinear_a8.so, which could not be "
-                           "loaded (build it with `python __graft_entry__.py`): %s" % qlinear_a8_error_str)
-    return _QLINEAR_A8_LIB
+    return _require_companion(_QLINEAR_A8_LIB, "qlinear_a8", "the 8-bit-activation packed linear op needs", qlinear_a8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

@@ -21,34 +21,22 @@ import ctypes
 
 import torch
 
-from . import _abi
 from ._abi import _DTYPE_CODE, LSQ_A8_I8, LSQ_A8_U8, QLINEAR_A8_MAX_ROWS, _assert_has_ops, qlinear_a8_library
 from ._cpu_host import _require_cpu, cpu_levels
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._pack_host import _check_packed, _unpack_bytes
+from ._pack_host import _unpack_bytes
+from ._qlinear_host import _plan_dict, _status, check_packed_linear_args
 
 _Y_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _LEVEL_CODE = {torch.uint8: LSQ_A8_U8, torch.int8: LSQ_A8_I8}
 
 
-def _a8_status(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, _abi._QLINEAR_A8_LIB.lsq_qlinear_a8_last_error().decode("utf-8", "replace")))
-
-
 def _check_a8_args(what, x, codes, qscale, qzero, bias, group_size, bits, y_dtype):
     """(N, K) of the packed weight, after the checks both ops and both devices share"""
-    _check_packed(what, codes, qscale, qzero, group_size, bits)
-    _check(codes.dim() == 2, "%s: codes must be the [N, K * bits / 8] bytes of a 2-D weight, got %d dims" % (what, codes.dim()))
-    N, K = codes.size(0), codes.size(1) * (8 // bits)
-    _check(x.dim() >= 1 and x.size(-1) == K,
-           "%s: the last dimension of x is %s, the packed weight has K = %d" % (what, x.size(-1) if x.dim() else "missing", K))
+    N, K = check_packed_linear_args(what, x, codes, qscale, qzero, bias, group_size, bits, y_dtype)
     _check(y_dtype in _Y_DTYPES, "%s: the output must be float32, bfloat16 or float16, got '%s'" % (what, str(y_dtype).replace("torch.", "")))
     _check(qscale.dtype == torch.float32,
            "%s: a packed weight with a float64 scale has no 8-bit-activation linear (the op computes in integers and float32)" % what)
-    if bias is not None:
-        _check(bias.dim() == 1 and bias.numel() == N, "%s: the bias needs %d values, got shape %s" % (what, N, tuple(bias.shape)))
-        _check(bias.dtype in (torch.float32, y_dtype), "%s: the bias must be float32 or of the output's dtype" % what)
     return N, K
 
 
@@ -91,6 +79,28 @@ def _row_blocks(M):
     return [(m0, min(QLINEAR_A8_MAX_ROWS, M - m0)) for m0 in range(0, M, QLINEAR_A8_MAX_ROWS)]
 
 
+def _launch_row_blocks(entry, x_code, xd, act_args, codes, qscale, qzero, bias, group_size, bits, y_dtype, y_args=()):
+    """The GPU side of both ops: y [M, N] of y_dtype for the rows xd [M, K], QLINEAR_A8_MAX_ROWS rows per launch of the C
+    entry point `entry`.  The two entry points differ in `x_code` (the dtype code of x), in `act_args` (what follows the rows
+    of x: the activation's constants) and in `y_args` (what follows y)."""
+    lib = qlinear_a8_library()
+    fn = getattr(lib, entry)
+    if not xd.is_contiguous():
+        xd = xd.contiguous()
+    cd, qs, qz = codes.contiguous(), qscale.contiguous(), qzero.contiguous()
+    bd = None if bias is None else bias.contiguous()
+    M, K, N = xd.size(0), xd.size(1), cd.size(0)
+    y = torch.empty((M, N), dtype=y_dtype, device=xd.device)
+    idx = xd.device.index
+    x_row, y_row = K * xd.element_size(), N * y.element_size()
+    for m0, rows in _row_blocks(M):
+        rc = _on_device(idx, fn, x_code, xd.data_ptr() + m0 * x_row, rows, *act_args, cd.data_ptr(), N, K, group_size, bits,
+                        qs.data_ptr(), qz.data_ptr(), None if bd is None else bd.data_ptr(), 0 if bd is None else _DTYPE_CODE[bd.dtype],
+                        y.data_ptr() + m0 * y_row, *y_args, _stream_of(idx))
+        _status(rc, entry, lib, "lsq_qlinear_a8_last_error")
+    return y
+
+
 def qlinear_a8_forward_levels(x_levels, s_x, zx, codes, qscale, qzero, bias, group_size, bits, out_dtype):
     """x_levels [..., K] bytes -> y [..., N] of out_dtype.  Inference only."""
     what = "lsq_linear_packed_q8"
@@ -112,20 +122,8 @@ def qlinear_a8_forward_levels(x_levels, s_x, zx, codes, qscale, qzero, bias, gro
     _require_gpu(what, *tensors)
     if M == 0 or N == 0:
         return torch.empty(out_shape, dtype=out_dtype, device=x_levels.device)
-    cd, qs, qz = codes.contiguous(), qscale.contiguous(), qzero.contiguous()
-    lib = qlinear_a8_library()
-    if not lx.is_contiguous():
-        lx = lx.contiguous()
-    bd = None if bias is None else bias.contiguous()
-    y = torch.empty((M, N), dtype=out_dtype, device=x_levels.device)
-    idx = x_levels.device.index
-    for m0, rows in _row_blocks(M):
-        rc = _on_device(idx, lib.lsq_qlinear_a8_forward_levels, _LEVEL_CODE[x_levels.dtype], lx.data_ptr() + m0 * K, rows,
-                        s_x.data_ptr(), zx.data_ptr(), cd.data_ptr(), N, K, group_size, bits, qs.data_ptr(), qz.data_ptr(),
-                        None if bd is None else bd.data_ptr(), 0 if bd is None else _DTYPE_CODE[bd.dtype],
-                        y.data_ptr() + m0 * N * y.element_size(), _DTYPE_CODE[out_dtype], _stream_of(idx))
-        if rc:
-            _a8_status(rc, "lsq_qlinear_a8_forward_levels")
+    y = _launch_row_blocks("lsq_qlinear_a8_forward_levels", _LEVEL_CODE[x_levels.dtype], lx, (s_x.data_ptr(), zx.data_ptr()), codes,
+                           qscale, qzero, bias, group_size, bits, out_dtype, (_DTYPE_CODE[out_dtype],))
     return y.reshape(out_shape)
 
 
@@ -157,22 +155,9 @@ def qlinear_a8_forward(x, act_scale, act_shift, qmin, qmax, tmin, tmax, codes, q
         lv = lv.view(torch.uint8) if unsigned else lv
         s_x, zx = _act_constants(sc, sh, tmin, tmax)
         return _cpu_levels_linear(lv, s_x, zx, codes, qscale, qzero, bias, group_size, bits, x.dtype, N, K).reshape(out_shape)
-    lib = qlinear_a8_library()
-    if not xd.is_contiguous():
-        xd = xd.contiguous()
-    cd, qs, qz = codes.contiguous(), qscale.contiguous(), qzero.contiguous()
     sc, sh = act_scale.detach().contiguous(), act_shift.detach().contiguous()
-    bd = None if bias is None else bias.contiguous()
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    idx = x.device.index
-    row = K * xd.element_size()
-    for m0, rows in _row_blocks(M):
-        rc = _on_device(idx, lib.lsq_qlinear_a8_forward, _DTYPE_CODE[x.dtype], xd.data_ptr() + m0 * row, rows, sc.data_ptr(),
-                        sh.data_ptr(), qmin, qmax, tmin, tmax, cd.data_ptr(), N, K, group_size, bits, qs.data_ptr(), qz.data_ptr(),
-                        None if bd is None else bd.data_ptr(), 0 if bd is None else _DTYPE_CODE[bd.dtype],
-                        y.data_ptr() + m0 * N * y.element_size(), _stream_of(idx))
-        if rc:
-            _a8_status(rc, "lsq_qlinear_a8_forward")
+    y = _launch_row_blocks("lsq_qlinear_a8_forward", _DTYPE_CODE[x.dtype], xd, (sc.data_ptr(), sh.data_ptr(), qmin, qmax, tmin, tmax),
+                           codes, qscale, qzero, bias, group_size, bits, x.dtype)
     return y.reshape(out_shape)
 
 
@@ -181,7 +166,5 @@ def qlinear_a8_plan(M, N, K, group_size, bits):
     lib = qlinear_a8_library()
     out = (ctypes.c_int32 * 8)()
     rc = lib.lsq_qlinear_a8_plan(int(M), int(N), int(K), int(group_size), int(bits), ctypes.byref(out))
-    if rc:
-        _a8_status(rc, "lsq_qlinear_a8_plan")
-    return dict(form="mfma" if out[0] else "generic", grid=out[1], block=out[2], native_rows=out[3], lds_bytes=out[4],
-                chunk=out[5], waves_per_tile=out[6], cols_per_tile=out[7])
+    _status(rc, "lsq_qlinear_a8_plan", lib, "lsq_qlinear_a8_last_error")
+    return _plan_dict(out)

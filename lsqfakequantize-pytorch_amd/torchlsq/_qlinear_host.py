@@ -11,7 +11,6 @@ import ctypes
 
 import torch
 
-from . import _abi
 from ._abi import _DTYPE_CODE, QLINEAR_MAX_ROWS, _assert_has_ops, qlinear_library
 from ._cpu_host import _require_cpu
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
@@ -20,23 +19,33 @@ from ._pack_host import _check_packed, pack_dequantize
 _X_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
-def _qlinear_status(rc, what):
+def _status(rc, what, lib, last_error):
+    """raise for the non-zero status `rc` of the call `what` into `lib`, with the message its `last_error` entry point holds"""
     if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, _abi._QLINEAR_LIB.lsq_qlinear_last_error().decode("utf-8", "replace")))
+        raise RuntimeError("%s failed (%d): %s" % (what, rc, getattr(lib, last_error)().decode("utf-8", "replace")))
 
 
-def check_qlinear_args(what, x, codes, qscale, qzero, bias, group_size, bits):
-    """(N, K) of the packed weight, after the checks both devices share"""
+def check_packed_linear_args(what, x, codes, qscale, qzero, bias, group_size, bits, y_dtype=None):
+    """(N, K) of the packed weight, after the checks every linear op on it shares, on both devices.  y_dtype: the output's
+    dtype; None when it is x's, which must then be a floating-point one.  The bias is float32 or of that dtype."""
     _check_packed(what, codes, qscale, qzero, group_size, bits)
     _check(codes.dim() == 2, "%s: codes must be the [N, K * bits / 8] bytes of a 2-D weight, got %d dims" % (what, codes.dim()))
     N, K = codes.size(0), codes.size(1) * (8 // bits)
     _check(x.dim() >= 1 and x.size(-1) == K,
            "%s: the last dimension of x is %s, the packed weight has K = %d" % (what, x.size(-1) if x.dim() else "missing", K))
-    _check(x.is_floating_point(), "%s: x must be a floating-point tensor" % what)
+    if y_dtype is None:
+        _check(x.is_floating_point(), "%s: x must be a floating-point tensor" % what)
     if bias is not None:
         _check(bias.dim() == 1 and bias.numel() == N, "%s: the bias needs %d values, got shape %s" % (what, N, tuple(bias.shape)))
-        _check(bias.dtype in (torch.float32, x.dtype), "%s: the bias must be float32 or of x's dtype" % what)
+        _check(bias.dtype in (torch.float32, x.dtype if y_dtype is None else y_dtype),
+               "%s: the bias must be float32 or of %s dtype" % (what, "x's" if y_dtype is None else "the output's"))
     return N, K
+
+
+def _plan_dict(out8):
+    """out8[] of lsq_qlinear_plan / lsq_qlinear_a8_plan"""
+    return dict(form="mfma" if out8[0] else "generic", grid=out8[1], block=out8[2], native_rows=out8[3], lds_bytes=out8[4],
+                chunk=out8[5], waves_per_tile=out8[6], cols_per_tile=out8[7])
 
 
 def qlinear_forward(x, codes, qscale, qzero, bias, group_size, bits):
@@ -44,7 +53,7 @@ def qlinear_forward(x, codes, qscale, qzero, bias, group_size, bits):
     wants a gradient."""
     what = "lsq_linear_packed"
     _assert_has_ops()
-    N, K = check_qlinear_args(what, x, codes, qscale, qzero, bias, group_size, bits)
+    N, K = check_packed_linear_args(what, x, codes, qscale, qzero, bias, group_size, bits)
     out_shape = x.shape[:-1] + (N,)
     tensors = (x, codes, qscale, qzero) + ((bias,) if bias is not None else ())
     if not any(t.is_cuda for t in tensors):
@@ -82,8 +91,7 @@ def qlinear_forward(x, codes, qscale, qzero, bias, group_size, bits):
     rc = _on_device(idx, lib.lsq_qlinear_forward, _DTYPE_CODE[x.dtype], xd.data_ptr(), M, cd.data_ptr(), N, K, group_size, bits,
                     qs.data_ptr(), qz.data_ptr(), None if bd is None else bd.data_ptr(),
                     0 if bd is None else _DTYPE_CODE[bd.dtype], y.data_ptr(), _stream_of(idx))
-    if rc:
-        _qlinear_status(rc, "lsq_qlinear_forward")
+    _status(rc, "lsq_qlinear_forward", lib, "lsq_qlinear_last_error")
     return y.reshape(out_shape)
 
 
@@ -92,7 +100,5 @@ def qlinear_plan(dtype, M, N, K, group_size, bits):
     lib = qlinear_library()
     out = (ctypes.c_int32 * 8)()
     rc = lib.lsq_qlinear_plan(_DTYPE_CODE[dtype], int(M), int(N), int(K), int(group_size), int(bits), ctypes.byref(out))
-    if rc:
-        _qlinear_status(rc, "lsq_qlinear_plan")
-    return dict(form="mfma" if out[0] else "generic", grid=out[1], block=out[2], native_rows=out[3], lds_bytes=out[4],
-                chunk=out[5], waves_per_tile=out[6], cols_per_tile=out[7])
+    _status(rc, "lsq_qlinear_plan", lib, "lsq_qlinear_last_error")
+    return _plan_dict(out)
