@@ -1,6 +1,7 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
-ctypes) and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
+ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so and liblsq_hip_qgemm.so (ctypes)
+and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
 The module holds the loader STATE (`_LIB`, `_HAS_OPS`, `_CPU_LIB`, `_NATIVE_LSQ`); the host layers (_hip_host.py,
@@ -269,6 +270,23 @@ _QLINEAR_A8_LIB, qlinear_a8_error_str = _load_companion("liblsq_hip_qlinear_a8.s
 def qlinear_a8_library():
     """The ctypes handle of liblsq_hip_qlinear_a8.so (raises if it is missing)."""
     return _require_companion(_QLINEAR_A8_LIB, "qlinear_a8", "the 8-bit-activation packed linear op needs", qlinear_a8_error_str)
+
+
+# The same linear layer for more rows of x than the decode kernel serves: a matrix-core GEMM on the codes
+# (include/lsq_hip_qgemm.h): a sixth companion library; the ABIs above stay as they are.
+QGEMM_ABI_VERSION = 1
+C_ABI_QGEMM = {
+    "lsq_qgemm_abi_version": (_int, []),
+    "lsq_qgemm_last_error": (ctypes.c_char_p, []),
+    "lsq_qgemm_forward": (_int, [_int, _vp, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp]),
+    "lsq_qgemm_plan": (_int, [_int, _i64, _i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_QGEMM_LIB, qgemm_error_str = _load_companion("liblsq_hip_qgemm.so", C_ABI_QGEMM, "lsq_qgemm_abi_version", QGEMM_ABI_VERSION)
+
+
+def qgemm_library():
+    """The ctypes handle of liblsq_hip_qgemm.so (raises if it is missing)."""
+    return _require_companion(_QGEMM_LIB, "qgemm", "the packed linear op on more than %d rows needs" % QLINEAR_MAX_ROWS, qgemm_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

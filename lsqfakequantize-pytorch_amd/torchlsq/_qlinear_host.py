@@ -2,9 +2,13 @@
 straight from the 4- / 2-bit codes (include/lsq_hip_qlinear.h states the arithmetic; include/lsq_hip_pack.h the format).
 
 GPU tensors: up to QLINEAR_MAX_ROWS rows of x (the product of its leading dims) go to liblsq_hip_qlinear.so with one ctypes
-call -- the weight is streamed once and no dequantized copy exists.  More rows are the PREFILL route: the weight is
-dequantized into a float32 temporary (liblsq_hip_pack.so) and handed to torch.nn.functional.linear in float32; that route
-meets the accuracy contract, not the batch invariance of the native kernel.  CPU tensors: x @ dequantize().T in float32 (float64
+call -- the weight is streamed once and no dequantized copy exists.  More rows (prefill, batches of sequences) of
+bfloat16 / float16 x go to the matrix-core GEMM of liblsq_hip_qgemm.so (_qgemm_host.py), which reads the codes in place
+too and is invariant to the batch among its own calls -- its bits are not the decode kernel's, whose sum has another order.
+What that library does not serve -- float32 x, a group that is no whole number of 16-byte code packets, codes that are not
+16-byte aligned -- takes the DEQUANTIZE route: the weight is dequantized into a float32 temporary (liblsq_hip_pack.so) and
+handed to torch.nn.functional.linear in float32; that route meets the accuracy contract, not the batch invariance of the
+native kernels.  CPU tensors: x @ dequantize().T in float32 (float64
 for a float64 scale) with torch -- as in _pack_host.py, not a hot path.
 """
 import ctypes
@@ -15,6 +19,7 @@ from ._abi import _DTYPE_CODE, QLINEAR_MAX_ROWS, _assert_has_ops, qlinear_librar
 from ._cpu_host import _require_cpu
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
 from ._pack_host import _check_packed, pack_dequantize
+from ._qgemm_host import qgemm_forward, qgemm_serves
 
 _X_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -78,7 +83,9 @@ def qlinear_forward(x, codes, qscale, qzero, bias, group_size, bits):
     if M == 0 or N == 0:
         return torch.empty(out_shape, dtype=x.dtype, device=x.device)
     if M > QLINEAR_MAX_ROWS:
-        # the prefill route.  The temporary is float32 whatever x is: a weight rounded to bfloat16 / float16 carries a
+        if qgemm_serves(xd, cd, group_size, bits):
+            return qgemm_forward(xd, cd, qs, qz, None if bias is None else bias.contiguous(), group_size, bits).reshape(out_shape)
+        # the dequantize route, for what the GEMM does not serve.  The temporary is float32 whatever x is: a weight rounded to bfloat16 / float16 carries a
         # relative error of 2^-9 / 2^-12 per term, far outside the fp32-accumulation bound of the op, so the product runs in
         # float32 and is rounded once
         w = pack_dequantize(cd, qs, qz, group_size, bits, torch.float32)

@@ -37,12 +37,14 @@ from ._group_host import (check_group_args, group_backward, group_backward_multi
 from ._pack_host import pack_dequantize, pack_plan, pack_quantize, pack_unpack  # noqa: F401
 from ._qlinear_host import qlinear_forward, qlinear_plan  # noqa: F401
 from ._qlinear_a8_host import qlinear_a8_forward, qlinear_a8_forward_levels, qlinear_a8_plan  # noqa: F401
+from ._qgemm_host import qgemm_forward, qgemm_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "native_error_str"):
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str",
+                "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
@@ -435,8 +437,8 @@ def _fake_dequantize_grp(codes, scale, zero_point, group_size, bits, dtype):
 
 
 # -------------------------------------------------------------------------------------------------
-# the linear op on packed weights (_qlinear_host.py): GPU tensors -> liblsq_hip_qlinear.so (up to 16 rows of x; more rows
-# dequantize and call F.linear), CPU tensors -> torch; a shape-only kernel.  Inference only: the autograd key refuses an x
+# the linear op on packed weights (_qlinear_host.py): GPU tensors -> liblsq_hip_qlinear.so (up to 16 rows of x), more rows ->
+# liblsq_hip_qgemm.so (16-bit x on the formats it serves; else dequantize and call F.linear), CPU tensors -> torch; a shape-only kernel.  Inference only: the autograd key refuses an x
 # (or bias) that wants a gradient instead of cutting the graph without a word.
 # -------------------------------------------------------------------------------------------------
 for _lib_key in (_lib_hip, _lib_cpu):

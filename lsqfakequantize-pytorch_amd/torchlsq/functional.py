@@ -629,8 +629,11 @@ def lsq_linear_packed(x: Tensor, packed: PackedGroupTensor, bias: Tensor = None)
     dtype.  Accumulation in float32, the bias (float32 or x's dtype) added in float32 before the one rounding; no atomics,
     repeated calls are bit-identical.  On the GPU up to 16 rows of x (the product of its leading dims) run the native kernel
     of liblsq_hip_qlinear.so -- the weight is streamed once, and row m of the result is bit for bit the 1-row call on x[m];
-    more rows (prefill) dequantize into a float32 temporary and call `torch.nn.functional.linear` in float32, which meets the same
-    accuracy bound but not that invariance.  Inference only: an x that requires grad under enabled grad mode raises."""
+    more rows (prefill) of bfloat16 / float16 x run the matrix-core GEMM of liblsq_hip_qgemm.so on the codes -- no dequantized
+    copy of the weight, and a row's bits do not depend on the other rows or on its place among them, though they are not the
+    16-row kernel's bits (another order of the same sum).  Float32 x beyond 16 rows, a group size that is no multiple of
+    128 / bits, and codes that are not 16-byte aligned dequantize into a float32 temporary and call
+    `torch.nn.functional.linear` in float32, which meets the same accuracy bound but not that invariance.  Inference only: an x that requires grad under enabled grad mode raises."""
     _assert_has_ops()
     codes = packed.codes.reshape(packed.shape[0], -1) if packed.codes.dim() != 2 else packed.codes
     groups = codes.size(0) * codes.size(1) * (8 // packed.bits) // packed.group_size
