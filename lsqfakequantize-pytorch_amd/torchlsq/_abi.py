@@ -1,6 +1,6 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
-ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so and liblsq_hip_qgemm.so (ctypes)
+ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -287,6 +287,28 @@ _QGEMM_LIB, qgemm_error_str = _load_companion("liblsq_hip_qgemm.so", C_ABI_QGEMM
 def qgemm_library():
     """The ctypes handle of liblsq_hip_qgemm.so (raises if it is missing)."""
     return _require_companion(_QGEMM_LIB, "qgemm", "the packed linear op on more than %d rows needs" % QLINEAR_MAX_ROWS, qgemm_error_str)
+
+
+# qlinear_a8 for more rows than its decode kernel serves: an int8 matrix-core GEMM on the codes with the decode kernel's
+# bits (include/lsq_hip_qgemm_a8.h): a seventh companion library; the ABIs above stay as they are.
+QGEMM_A8_ABI_VERSION = 1
+C_ABI_QGEMM_A8 = {
+    "lsq_qgemm_a8_abi_version": (_int, []),
+    "lsq_qgemm_a8_last_error": (ctypes.c_char_p, []),
+    "lsq_qgemm_a8_forward_levels": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _int,
+                                           _vp]),
+    "lsq_qgemm_a8_forward": (_int, [_int, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp,
+                                    _int, _vp, _vp, _vp]),
+    "lsq_qgemm_a8_plan": (_int, [_i64, _i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_QGEMM_A8_LIB, qgemm_a8_error_str = _load_companion("liblsq_hip_qgemm_a8.so", C_ABI_QGEMM_A8, "lsq_qgemm_a8_abi_version",
+                                                      QGEMM_A8_ABI_VERSION)
+
+
+def qgemm_a8_library():
+    """The ctypes handle of liblsq_hip_qgemm_a8.so (raises if it is missing)."""
+    return _require_companion(_QGEMM_A8_LIB, "qgemm_a8", "the 8-bit-activation packed linear op on more than %d rows needs"
+                              % QLINEAR_A8_MAX_ROWS, qgemm_a8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

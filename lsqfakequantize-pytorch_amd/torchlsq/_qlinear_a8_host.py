@@ -10,8 +10,12 @@ scale, shift and range and forms the levels itself -- in the kernel on the GPU, 
 is the levels op on `lsq_levels_per_tensor`'s bytes, bit for bit.
 
 GPU tensors: up to QLINEAR_A8_MAX_ROWS rows (the product of the leading dims) go to liblsq_hip_qlinear_a8.so with one ctypes
-call; nothing is read back.  More rows go to the same kernel QLINEAR_A8_MAX_ROWS at a time, one launch per block of rows:
-every row is then the 1-row call bit for bit, whatever M is, and the weight is streamed once per block.  (Dequantizing the
+call; nothing is read back.  From `qgemm_a8_min_rows()` rows on, a call on a format that liblsq_hip_qgemm_a8.so serves (the decode
+kernel's matrix-core form: `qgemm_a8_serves`) is ONE call of its int8 matrix-core GEMM (_qgemm_a8_host.py), which streams the
+codes once per 128-row tile and keeps the decode kernel's order of the fp32 sum; the fused op allocates the M * K bytes of
+levels the GEMM's pre-pass writes.  Every other call with more rows goes to the decode kernel QLINEAR_A8_MAX_ROWS at a time,
+one launch per block of rows (`_launch_row_blocks`), the weight streamed once per block.  On both routes every row is the
+1-row call bit for bit, whatever M is: the threshold is a matter of speed alone.  (Dequantizing the
 levels to float32, (lx - zx) * s_x, for `lsq_linear_packed`'s prefill route -- a float32 weight temporary and F.linear in
 float32 -- does K fp32 multiply-adds per output: its error scales with sum |a| |code - qzero|, before the cancellation inside
 a group, and the bound of this op, which scales with sum |I|, does not cover that.  DESIGN.md 9.4 has the figures.)  CPU
@@ -25,6 +29,7 @@ from ._abi import _DTYPE_CODE, LSQ_A8_I8, LSQ_A8_U8, QLINEAR_A8_MAX_ROWS, _asser
 from ._cpu_host import _require_cpu, cpu_levels
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
 from ._pack_host import _unpack_bytes
+from ._qgemm_a8_host import qgemm_a8_forward, qgemm_a8_forward_levels, qgemm_a8_min_rows, qgemm_a8_serves
 from ._qlinear_host import _plan_dict, _status, check_packed_linear_args
 
 _Y_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
@@ -79,6 +84,16 @@ def _row_blocks(M):
     return [(m0, min(QLINEAR_A8_MAX_ROWS, M - m0)) for m0 in range(0, M, QLINEAR_A8_MAX_ROWS)]
 
 
+def _gemm_operands(M, codes, qscale, qzero, bias, group_size, bits):
+    """(codes, qscale, qzero, bias), contiguous, when an M-row GPU call takes the GEMM of liblsq_hip_qgemm_a8.so; else None"""
+    if M < qgemm_a8_min_rows():
+        return None
+    cd = codes.contiguous()
+    if not qgemm_a8_serves(cd, group_size, bits):
+        return None
+    return cd, qscale.contiguous(), qzero.contiguous(), None if bias is None else bias.contiguous()
+
+
 def _launch_row_blocks(entry, x_code, xd, act_args, codes, qscale, qzero, bias, group_size, bits, y_dtype, y_args=()):
     """The GPU side of both ops: y [M, N] of y_dtype for the rows xd [M, K], QLINEAR_A8_MAX_ROWS rows per launch of the C
     entry point `entry`.  The two entry points differ in `x_code` (the dtype code of x), in `act_args` (what follows the rows
@@ -122,8 +137,12 @@ def qlinear_a8_forward_levels(x_levels, s_x, zx, codes, qscale, qzero, bias, gro
     _require_gpu(what, *tensors)
     if M == 0 or N == 0:
         return torch.empty(out_shape, dtype=out_dtype, device=x_levels.device)
-    y = _launch_row_blocks("lsq_qlinear_a8_forward_levels", _LEVEL_CODE[x_levels.dtype], lx, (s_x.data_ptr(), zx.data_ptr()), codes,
-                           qscale, qzero, bias, group_size, bits, out_dtype, (_DTYPE_CODE[out_dtype],))
+    ops = _gemm_operands(M, codes, qscale, qzero, bias, group_size, bits)
+    if ops is not None:
+        y = qgemm_a8_forward_levels(lx.contiguous(), s_x, zx, *ops, group_size, bits, out_dtype)
+    else:
+        y = _launch_row_blocks("lsq_qlinear_a8_forward_levels", _LEVEL_CODE[x_levels.dtype], lx, (s_x.data_ptr(), zx.data_ptr()), codes,
+                               qscale, qzero, bias, group_size, bits, out_dtype, (_DTYPE_CODE[out_dtype],))
     return y.reshape(out_shape)
 
 
@@ -156,8 +175,12 @@ def qlinear_a8_forward(x, act_scale, act_shift, qmin, qmax, tmin, tmax, codes, q
         s_x, zx = _act_constants(sc, sh, tmin, tmax)
         return _cpu_levels_linear(lv, s_x, zx, codes, qscale, qzero, bias, group_size, bits, x.dtype, N, K).reshape(out_shape)
     sc, sh = act_scale.detach().contiguous(), act_shift.detach().contiguous()
-    y = _launch_row_blocks("lsq_qlinear_a8_forward", _DTYPE_CODE[x.dtype], xd, (sc.data_ptr(), sh.data_ptr(), qmin, qmax, tmin, tmax),
-                           codes, qscale, qzero, bias, group_size, bits, x.dtype)
+    ops = _gemm_operands(M, codes, qscale, qzero, bias, group_size, bits)
+    if ops is not None:
+        y = qgemm_a8_forward(xd.contiguous(), sc, sh, qmin, qmax, tmin, tmax, *ops, group_size, bits)
+    else:
+        y = _launch_row_blocks("lsq_qlinear_a8_forward", _DTYPE_CODE[x.dtype], xd, (sc.data_ptr(), sh.data_ptr(), qmin, qmax, tmin, tmax),
+                               codes, qscale, qzero, bias, group_size, bits, x.dtype)
     return y.reshape(out_shape)
 
 

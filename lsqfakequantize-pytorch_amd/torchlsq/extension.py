@@ -38,12 +38,13 @@ from ._pack_host import pack_dequantize, pack_plan, pack_quantize, pack_unpack  
 from ._qlinear_host import qlinear_forward, qlinear_plan  # noqa: F401
 from ._qlinear_a8_host import qlinear_a8_forward, qlinear_a8_forward_levels, qlinear_a8_plan  # noqa: F401
 from ._qgemm_host import qgemm_forward, qgemm_plan  # noqa: F401
+from ._qgemm_a8_host import qgemm_a8_forward, qgemm_a8_forward_levels, qgemm_a8_min_rows, qgemm_a8_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
