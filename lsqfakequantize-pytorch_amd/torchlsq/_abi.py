@@ -311,6 +311,27 @@ def qgemm_a8_library():
                               % QLINEAR_A8_MAX_ROWS, qgemm_a8_error_str)
 
 
+# W8A8: 8-bit activation levels times 8-bit weight levels with one (scale, zero point) per output row, any number of rows
+# (include/lsq_hip_qlinear_w8.h): an eighth companion library; the ABIs above stay as they are.
+QLINEAR_W8_ABI_VERSION = 1
+LSQ_W8_U8, LSQ_W8_I8 = 0, 1     # level_dtype and w_level_dtype
+C_ABI_QLINEAR_W8 = {
+    "lsq_qlinear_w8_abi_version": (_int, []),
+    "lsq_qlinear_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_qlinear_w8_forward_levels": (_int, [_int, _vp, _i64, _vp, _vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _int, _vp, _int, _vp]),
+    "lsq_qlinear_w8_forward": (_int, [_int, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _int,
+                                      _vp, _vp, _vp]),
+    "lsq_qlinear_w8_plan": (_int, [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_QLINEAR_W8_LIB, qlinear_w8_error_str = _load_companion("liblsq_hip_qlinear_w8.so", C_ABI_QLINEAR_W8, "lsq_qlinear_w8_abi_version",
+                                                          QLINEAR_W8_ABI_VERSION)
+
+
+def qlinear_w8_library():
+    """The ctypes handle of liblsq_hip_qlinear_w8.so (raises if it is missing)."""
+    return _require_companion(_QLINEAR_W8_LIB, "qlinear_w8", "the W8A8 linear op needs", qlinear_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -39,12 +39,13 @@ from ._qlinear_host import qlinear_forward, qlinear_plan  # noqa: F401
 from ._qlinear_a8_host import qlinear_a8_forward, qlinear_a8_forward_levels, qlinear_a8_plan  # noqa: F401
 from ._qgemm_host import qgemm_forward, qgemm_plan  # noqa: F401
 from ._qgemm_a8_host import qgemm_a8_forward, qgemm_a8_forward_levels, qgemm_a8_min_rows, qgemm_a8_plan  # noqa: F401
+from ._qlinear_w8_host import qlinear_w8_forward, qlinear_w8_forward_levels, qlinear_w8_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -120,6 +121,13 @@ _lib_def.define("lsq_linear_packed_q8(Tensor x_levels, Tensor s_x, Tensor zx, Te
                 "Tensor? bias, int group_size, int bits, ScalarType out_dtype) -> Tensor")
 _lib_def.define("lsq_linear_packed_a8(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
                 "int type_max, Tensor codes, Tensor scale, Tensor zero_point, Tensor? bias, int group_size, int bits) -> Tensor")
+#  * W8A8: 8-bit activation levels times 8-bit weight LEVELS [N, K] (int8 / uint8) with one scale (float32) and zero point
+#    (int32) per output row, summed in integers over all of K (liblsq_hip_qlinear_w8.so, include/lsq_hip_qlinear_w8.h): _q8
+#    takes the activation levels, _a8 a floating x and the per-tensor quantizer's constants.  Inference only.
+_lib_def.define("lsq_linear_w8_q8(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, ScalarType out_dtype) -> Tensor")
+_lib_def.define("lsq_linear_w8_a8(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
+                "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias) -> Tensor")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -507,6 +515,43 @@ def _linear_packed_a8_no_grad(x, act_scale, act_shift, quant_min, quant_max, typ
 
 _lib_def.impl("lsq_linear_packed_q8", _linear_packed_q8_no_grad, "Autograd")
 _lib_def.impl("lsq_linear_packed_a8", _linear_packed_a8_no_grad, "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the W8A8 linear ops on per-channel weight levels (_qlinear_w8_host.py): GPU tensors -> liblsq_hip_qlinear_w8.so (one call,
+# any number of rows), CPU tensors -> one torch int64 product; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_w8_q8", qlinear_w8_forward_levels)
+    _lib_key.impl("lsq_linear_w8_a8", qlinear_w8_forward)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_w8_q8", lib=_lib_def)
+def _fake_linear_w8_q8(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, out_dtype):
+    return torch.empty(x_levels.shape[:-1] + (w_levels.shape[0],), dtype=out_dtype, device=x_levels.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_w8_a8", lib=_lib_def)
+def _fake_linear_w8_a8(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels, w_scale, w_zero, bias):
+    return torch.empty(x.shape[:-1] + (w_levels.shape[0],), dtype=x.dtype, device=x.device)
+
+
+def _linear_w8_q8_no_grad(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, out_dtype):
+    _refuse_grad("lsq_linear_w8_q8", s_x, w_scale, bias)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_linear_w8_q8(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, out_dtype)
+
+
+def _linear_w8_a8_no_grad(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels, w_scale, w_zero, bias):
+    _refuse_grad("lsq_linear_w8_a8", x, act_scale, act_shift, w_scale, bias)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_linear_w8_a8(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels,
+                                                   w_scale, w_zero, bias)
+
+
+_lib_def.impl("lsq_linear_w8_q8", _linear_w8_q8_no_grad, "Autograd")
+_lib_def.impl("lsq_linear_w8_a8", _linear_w8_a8_no_grad, "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

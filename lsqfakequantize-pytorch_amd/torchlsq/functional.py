@@ -674,3 +674,59 @@ def lsq_linear_packed_a8(x: Tensor, packed: PackedGroupTensor, bias: Tensor = No
     type_min = quant_min if type_min is None else type_min
     type_max = quant_max if type_max is None else type_max
     return torch.ops.torchlsq.lsq_linear_packed_a8(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w)
+
+
+def w8_weight_operands(weight_q: Tensor):
+    """(levels [N, K] int8 / uint8, scale [N] float32, zero point [N] int32) of a 2-D per-channel (axis 0) or per-tensor
+    `torch.qint8` / `torch.quint8` weight, e.g. `LSQFakeQuantizer.quantize(w)`: what `lsq_linear_w8_q8` / `_a8` take.  A
+    per-tensor quantizer's one pair is repeated N times.  Nothing is read back from the device."""
+    assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 2, \
+        "lsq_linear_w8a8 needs a 2-D torch.qint8 / torch.quint8 weight [out_features, in_features]"
+    levels = weight_q.int_repr()
+    N = levels.size(0)
+    if weight_q.qscheme() in (torch.per_channel_affine, torch.per_channel_symmetric):
+        assert weight_q.q_per_channel_axis() == 0, "lsq_linear_w8a8 needs a weight quantized per output row (axis 0)"
+        scale = weight_q.q_per_channel_scales().to(torch.float32)
+        zero = weight_q.q_per_channel_zero_points().to(torch.int32)
+    else:
+        assert weight_q.qscheme() in (torch.per_tensor_affine, torch.per_tensor_symmetric), \
+            "lsq_linear_w8a8 needs a per-channel or per-tensor quantized weight"
+        scale = torch.full((N,), weight_q.q_scale(), dtype=torch.float32, device=levels.device)
+        zero = torch.full((N,), weight_q.q_zero_point(), dtype=torch.int32, device=levels.device)
+    return levels, scale, zero
+
+
+def lsq_linear_w8a8(x: Tensor, weight_q: Tensor, bias: Tensor = None, scale: Tensor = None, shift: Tensor = None,
+                    quant_min: int = None, quant_max: int = None, type_min: int = None, type_max: int = None,
+                    out_dtype=None) -> Tensor:
+    """A linear layer on 8-bit activations and an 8-bit weight (W8A8), summed in integers: with lx the level of an activation,
+    zx its zero point and s_x its scale, lw the level of a weight and (s_w[n], zw[n]) the scale and zero point of output row n,
+    `y[..., n] = ((s_w[n] * float(I)) * s_x) + bias[n]` where `I = sum_k (lx[k] - zx) * (lw[n, k] - zw[n])` is an exact integer
+    over all of K, converted to float32 once.
+
+    `weight_q` is the 2-D per-channel (axis 0) or per-tensor `torch.qint8` / `torch.quint8` tensor that
+    `LSQFakeQuantizer.quantize(w)` / `lsq_quantize` return.
+
+    * floating x (bfloat16, float16 or float32) with the per-tensor activation quantizer's `scale` and `shift` (float32 tensors
+      of one value), `quant_min`, `quant_max` and optionally the type's range: the levels are those of `lsq(x, scale, shift,
+      ...)` and y has x's dtype.  Equal, bit for bit, to the second form on `lsq_levels_per_tensor`'s bytes.
+    * a per-tensor `torch.quint8` / `torch.qint8` tensor as x (e.g. `m.quantize(x)`) with `out_dtype` (default float32): its
+      `int_repr()`, `q_scale()` and `q_zero_point()` are used; scale, shift and the range arguments are ignored.
+
+    No atomics; repeated calls are bit-identical; a row's bits do not depend on the number of rows or on its position; the
+    GPU result (liblsq_hip_qlinear_w8.so, int8 matrix cores, any number of rows in one call) equals the CPU result bit for
+    bit.  Inference only."""
+    _assert_has_ops()
+    w = w8_weight_operands(weight_q) + (bias,)
+    if x.is_quantized:
+        assert x.qscheme() in (torch.per_tensor_affine, torch.per_tensor_symmetric) and x.dtype in (torch.quint8, torch.qint8), \
+            "lsq_linear_w8a8 needs a per-tensor torch.quint8 / torch.qint8 tensor"
+        s_x = torch.tensor([x.q_scale()], dtype=torch.float32, device=x.device)
+        zx = torch.tensor([x.q_zero_point()], dtype=torch.int32, device=x.device)
+        return torch.ops.torchlsq.lsq_linear_w8_q8(x.int_repr(), s_x, zx, *w, torch.float32 if out_dtype is None else out_dtype)
+    assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
+        "lsq_linear_w8a8 on a floating x needs the activation quantizer's scale, shift, quant_min and quant_max"
+    assert out_dtype is None or out_dtype == x.dtype, "a floating x gives y of x's dtype"
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    return torch.ops.torchlsq.lsq_linear_w8_a8(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w)
