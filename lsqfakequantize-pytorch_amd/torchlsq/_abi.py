@@ -1,6 +1,7 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
-ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes)
+ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes),
+the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -330,6 +331,31 @@ _QLINEAR_W8_LIB, qlinear_w8_error_str = _load_companion("liblsq_hip_qlinear_w8.s
 def qlinear_w8_library():
     """The ctypes handle of liblsq_hip_qlinear_w8.so (raises if it is missing)."""
     return _require_companion(_QLINEAR_W8_LIB, "qlinear_w8", "the W8A8 linear op needs", qlinear_w8_error_str)
+
+
+# W8A8 conv2d: the same arithmetic as an implicit GEMM on channels-last levels (include/lsq_hip_qconv_w8.h): a ninth companion
+# library; the ABIs above stay as they are.
+class LsqQconvW8Geom(ctypes.Structure):
+    """lsq_qconv_w8_geom (include/lsq_hip_qconv_w8.h): x [B, H, W, Cin], weight [Cout, kh, kw, Cin], stride, padding, dilation."""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "Cin", "H", "W", "Cout", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw")]
+
+
+QCONV_W8_ABI_VERSION = 1
+_CGP = ctypes.POINTER(LsqQconvW8Geom)
+C_ABI_QCONV_W8 = {
+    "lsq_qconv_w8_abi_version": (_int, []),
+    "lsq_qconv_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_qconv_w8_forward_levels": (_int, [_int, _vp, _vp, _vp, _CGP, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp]),
+    "lsq_qconv_w8_forward": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _CGP, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "lsq_qconv_w8_plan": (_int, [_CGP, _int, ctypes.POINTER(ctypes.c_int32 * 8)]),
+}
+_QCONV_W8_LIB, qconv_w8_error_str = _load_companion("liblsq_hip_qconv_w8.so", C_ABI_QCONV_W8, "lsq_qconv_w8_abi_version",
+                                                      QCONV_W8_ABI_VERSION)
+
+
+def qconv_w8_library():
+    """The ctypes handle of liblsq_hip_qconv_w8.so (raises if it is missing)."""
+    return _require_companion(_QCONV_W8_LIB, "qconv_w8", "the W8A8 conv2d op needs", qconv_w8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

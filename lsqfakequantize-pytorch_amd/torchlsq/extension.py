@@ -40,12 +40,13 @@ from ._qlinear_a8_host import qlinear_a8_forward, qlinear_a8_forward_levels, qli
 from ._qgemm_host import qgemm_forward, qgemm_plan  # noqa: F401
 from ._qgemm_a8_host import qgemm_a8_forward, qgemm_a8_forward_levels, qgemm_a8_min_rows, qgemm_a8_plan  # noqa: F401
 from ._qlinear_w8_host import qlinear_w8_forward, qlinear_w8_forward_levels, qlinear_w8_plan  # noqa: F401
+from ._qconv_w8_host import qconv_w8_forward, qconv_w8_forward_levels, qconv_w8_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -128,6 +129,14 @@ _lib_def.define("lsq_linear_w8_q8(Tensor x_levels, Tensor s_x, Tensor zx, Tensor
                 "Tensor? bias, ScalarType out_dtype) -> Tensor")
 _lib_def.define("lsq_linear_w8_a8(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
                 "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias) -> Tensor")
+#  * W8A8 conv2d: the same arithmetic over every tap and input channel of a 2-D convolution (groups == 1, zero padding) on
+#    activation levels / a floating x [B, Cin, H, W] and weight LEVELS [Cout, Cin, kh, kw], both read channels-last
+#    (liblsq_hip_qconv_w8.so, include/lsq_hip_qconv_w8.h); y is [B, Cout, OH, OW] in channels-last memory.  Inference only.
+_lib_def.define("lsq_conv2d_w8_q8(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, int[2] stride, int[2] padding, int[2] dilation, ScalarType out_dtype) -> Tensor")
+_lib_def.define("lsq_conv2d_w8_a8(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
+                "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias, int[2] stride, int[2] padding, "
+                "int[2] dilation) -> Tensor")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -552,6 +561,53 @@ def _linear_w8_a8_no_grad(x, act_scale, act_shift, quant_min, quant_max, type_mi
 
 _lib_def.impl("lsq_linear_w8_q8", _linear_w8_q8_no_grad, "Autograd")
 _lib_def.impl("lsq_linear_w8_a8", _linear_w8_a8_no_grad, "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the W8A8 conv2d ops (_qconv_w8_host.py): GPU tensors -> liblsq_hip_qconv_w8.so (one call), CPU tensors -> one torch int64
+# convolution; a shape-only kernel each, which also gives the channels-last memory format.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_conv2d_w8_q8", qconv_w8_forward_levels)
+    _lib_key.impl("lsq_conv2d_w8_a8", qconv_w8_forward)
+del _lib_key
+
+
+def _fake_conv2d_w8(x, w_levels, stride, padding, dilation, dtype):
+    (sh, sw), (ph, pw), (dh, dw) = stride, padding, dilation
+    oh = (x.shape[2] + 2 * ph - dh * (w_levels.shape[2] - 1) - 1) // sh + 1
+    ow = (x.shape[3] + 2 * pw - dw * (w_levels.shape[3] - 1) - 1) // sw + 1
+    return torch.empty((x.shape[0], w_levels.shape[0], oh, ow), dtype=dtype, device=x.device, memory_format=torch.channels_last)
+
+
+@torch.library.register_fake("torchlsq::lsq_conv2d_w8_q8", lib=_lib_def)
+def _fake_conv2d_w8_q8(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation, out_dtype):
+    return _fake_conv2d_w8(x_levels, w_levels, stride, padding, dilation, out_dtype)
+
+
+@torch.library.register_fake("torchlsq::lsq_conv2d_w8_a8", lib=_lib_def)
+def _fake_conv2d_w8_a8(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels, w_scale, w_zero, bias, stride,
+                       padding, dilation):
+    return _fake_conv2d_w8(x, w_levels, stride, padding, dilation, x.dtype)
+
+
+def _conv2d_w8_q8_no_grad(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation, out_dtype):
+    _refuse_grad("lsq_conv2d_w8_q8", s_x, w_scale, bias)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_conv2d_w8_q8(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation,
+                                                   out_dtype)
+
+
+def _conv2d_w8_a8_no_grad(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels, w_scale, w_zero, bias, stride,
+                          padding, dilation):
+    _refuse_grad("lsq_conv2d_w8_a8", x, act_scale, act_shift, w_scale, bias)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.torchlsq.lsq_conv2d_w8_a8(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels,
+                                                   w_scale, w_zero, bias, stride, padding, dilation)
+
+
+_lib_def.impl("lsq_conv2d_w8_q8", _conv2d_w8_q8_no_grad, "Autograd")
+_lib_def.impl("lsq_conv2d_w8_a8", _conv2d_w8_a8_no_grad, "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

@@ -679,18 +679,23 @@ def lsq_linear_packed_a8(x: Tensor, packed: PackedGroupTensor, bias: Tensor = No
 def w8_weight_operands(weight_q: Tensor):
     """(levels [N, K] int8 / uint8, scale [N] float32, zero point [N] int32) of a 2-D per-channel (axis 0) or per-tensor
     `torch.qint8` / `torch.quint8` weight, e.g. `LSQFakeQuantizer.quantize(w)`: what `lsq_linear_w8_q8` / `_a8` take.  A
-    per-tensor quantizer's one pair is repeated N times.  Nothing is read back from the device."""
-    assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 2, \
-        "lsq_linear_w8a8 needs a 2-D torch.qint8 / torch.quint8 weight [out_features, in_features]"
+    per-tensor quantizer's one pair is repeated N times.  Nothing is read back from the device.  A 4-D conv weight
+    [Cout, Cin, kh, kw] gives its 4-D levels and the same two vectors: what `lsq_conv2d_w8_q8` / `_a8` take."""
+    if weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 4:
+        what = "lsq_conv2d_w8a8"        # a conv weight [Cout, Cin, kh, kw]: the same three operands, the levels 4-D
+    else:
+        what = "lsq_linear_w8a8"
+        assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 2, \
+            "lsq_linear_w8a8 needs a 2-D torch.qint8 / torch.quint8 weight [out_features, in_features]"
     levels = weight_q.int_repr()
     N = levels.size(0)
     if weight_q.qscheme() in (torch.per_channel_affine, torch.per_channel_symmetric):
-        assert weight_q.q_per_channel_axis() == 0, "lsq_linear_w8a8 needs a weight quantized per output row (axis 0)"
+        assert weight_q.q_per_channel_axis() == 0, "%s needs a weight quantized per output row (axis 0)" % what
         scale = weight_q.q_per_channel_scales().to(torch.float32)
         zero = weight_q.q_per_channel_zero_points().to(torch.int32)
     else:
         assert weight_q.qscheme() in (torch.per_tensor_affine, torch.per_tensor_symmetric), \
-            "lsq_linear_w8a8 needs a per-channel or per-tensor quantized weight"
+            "%s needs a per-channel or per-tensor quantized weight" % what
         scale = torch.full((N,), weight_q.q_scale(), dtype=torch.float32, device=levels.device)
         zero = torch.full((N,), weight_q.q_zero_point(), dtype=torch.int32, device=levels.device)
     return levels, scale, zero
@@ -730,3 +735,68 @@ def lsq_linear_w8a8(x: Tensor, weight_q: Tensor, bias: Tensor = None, scale: Ten
     type_min = quant_min if type_min is None else type_min
     type_max = quant_max if type_max is None else type_max
     return torch.ops.torchlsq.lsq_linear_w8_a8(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w)
+
+
+def _conv_padding(padding, kernel, stride, dilation):
+    """(ph, pw) of F.conv2d's `padding` argument: ints, a pair, 'valid', or 'same' where it is symmetric (stride 1 and an even
+    dilation * (kernel - 1) per axis; torch pads the odd remainder on one side only, which this op does not do)"""
+    if isinstance(padding, str):
+        if padding == "valid":
+            return (0, 0)
+        if padding != "same":
+            raise ValueError("lsq_conv2d_w8a8: padding must be ints, a pair, 'valid' or 'same', got %r" % padding)
+        if tuple(stride) != (1, 1):
+            raise ValueError("lsq_conv2d_w8a8: padding='same' needs stride 1, got %s" % (tuple(stride),))
+        total = [d * (k - 1) for d, k in zip(dilation, kernel)]
+        if any(t % 2 for t in total):
+            raise ValueError("lsq_conv2d_w8a8: padding='same' is asymmetric for kernel %s with dilation %s (dilation * (kernel - 1) "
+                             "is odd); only symmetric zero padding is served" % (tuple(kernel), tuple(dilation)))
+        return tuple(t // 2 for t in total)
+    return _two(padding, "padding")
+
+
+def _two(v, name):
+    v = tuple(int(e) for e in v) if isinstance(v, (tuple, list)) else (int(v),)
+    if len(v) not in (1, 2):
+        raise ValueError("lsq_conv2d_w8a8: %s must be one int or a pair of ints" % name)
+    return v * 2 if len(v) == 1 else v
+
+
+def lsq_conv2d_w8a8(x: Tensor, weight_q: Tensor, bias: Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
+                    scale: Tensor = None, shift: Tensor = None, quant_min: int = None, quant_max: int = None, type_min: int = None,
+                    type_max: int = None, out_dtype=None) -> Tensor:
+    """A 2-D convolution on 8-bit activations and an 8-bit weight (W8A8), summed in integers: `lsq_linear_w8a8`'s arithmetic with
+    the sum running over every tap (i, j) and input channel c,
+    `y[b, n, oh, ow] = ((s_w[n] * float(I)) * s_x) + bias[n]`, `I = sum (lx[b, c, oh sh - ph + i dh, ow sw - pw + j dw] - zx) *
+    (lw[n, c, i, j] - zw[n])`; a tap in the zero padding contributes 0.  `F.conv2d`'s arguments with `groups == 1` and zero
+    padding: `padding` is ints, a pair, 'valid', or 'same' where that is symmetric.
+
+    `weight_q` is the 4-D per-channel (axis 0) or per-tensor `torch.qint8` / `torch.quint8` tensor that
+    `LSQFakeQuantizer.quantize(conv.weight)` returns.  x [B, Cin, H, W] is floating (with the per-tensor activation quantizer's
+    `scale`, `shift`, `quant_min`, `quant_max`; y has x's dtype) or a per-tensor `torch.quint8` / `torch.qint8` tensor (with
+    `out_dtype`, default float32), exactly as in `lsq_linear_w8a8`; the two forms agree bit for bit.
+
+    The result is [B, Cout, OH, OW] in channels-last memory.  The kernels read channels-last operands: an x or a weight that is
+    not channels-last is copied into that format first (one extra pass over it).  No atomics; repeated calls are bit-identical;
+    the GPU result (liblsq_hip_qconv_w8.so, an int8 matrix-core implicit GEMM) equals the CPU result (one int64 `F.conv2d`)
+    bit for bit.  Inference only."""
+    _assert_has_ops()
+    if groups != 1:
+        raise ValueError("lsq_conv2d_w8a8 serves groups == 1 only, got groups = %d" % groups)
+    assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 4, \
+        "lsq_conv2d_w8a8 needs a 4-D torch.qint8 / torch.quint8 weight [out_channels, in_channels, kh, kw]"
+    stride, dilation = _two(stride, "stride"), _two(dilation, "dilation")
+    padding = _conv_padding(padding, weight_q.shape[2:], stride, dilation)
+    w = w8_weight_operands(weight_q) + (bias, list(stride), list(padding), list(dilation))
+    if x.is_quantized:
+        assert x.qscheme() in (torch.per_tensor_affine, torch.per_tensor_symmetric) and x.dtype in (torch.quint8, torch.qint8), \
+            "lsq_conv2d_w8a8 needs a per-tensor torch.quint8 / torch.qint8 tensor"
+        s_x = torch.tensor([x.q_scale()], dtype=torch.float32, device=x.device)
+        zx = torch.tensor([x.q_zero_point()], dtype=torch.int32, device=x.device)
+        return torch.ops.torchlsq.lsq_conv2d_w8_q8(x.int_repr(), s_x, zx, *w, torch.float32 if out_dtype is None else out_dtype)
+    assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
+        "lsq_conv2d_w8a8 on a floating x needs the activation quantizer's scale, shift, quant_min and quant_max"
+    assert out_dtype is None or out_dtype == x.dtype, "a floating x gives y of x's dtype"
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    return torch.ops.torchlsq.lsq_conv2d_w8_a8(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w)

@@ -13,6 +13,7 @@ from .modules.weight_group import LSQWeightGroup  # noqa: F401
 from .modules.packed_linear import PackedLinear, convert_packed  # noqa: F401
 from .modules.packed_linear_a8 import PackedLinearA8, convert_packed_a8  # noqa: F401
 from .modules.linear_w8a8 import LinearW8A8, convert_w8a8  # noqa: F401
+from .modules.conv_w8a8 import Conv2dW8A8  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
@@ -109,6 +110,6 @@ def prepare_ddp(model, process_group=None, grads="mean"):
     return model
 
 
-__all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "PackedLinearA8", "LinearW8A8", "convert_packed", "convert_packed_a8",
+__all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "PackedLinearA8", "LinearW8A8", "Conv2dW8A8", "convert_packed", "convert_packed_a8",
            "convert_w8a8",
            "enable_rank_sync", "prepare_ddp"] + [row[0] for row in _TABLE]

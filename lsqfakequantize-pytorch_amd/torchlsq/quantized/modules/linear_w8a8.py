@@ -3,7 +3,8 @@ weights.  `LinearW8A8` keeps the weight as its 8-bit LEVELS with one (scale, zer
 per-tensor quantizer of the layer's INPUT: its scale and shift as buffers, its range as extra state.  The forward multiplies
 the input's 8-bit levels with the weight's in integers over all of K (`torchlsq.functional.lsq_linear_w8a8`,
 liblsq_hip_qlinear_w8.so on the GPU): a floating input is quantized on the way, a per-tensor quantized tensor is read as it
-is.  `convert_w8a8(model, input_quantizers)` swaps the listed linear layers for one.
+is.  `convert_w8a8(model, input_quantizers)` swaps the listed linear layers for one (and the listed 2-D convolutions for a
+`Conv2dW8A8`, conv_w8a8.py).
 """
 import copy
 
@@ -12,6 +13,7 @@ from torch import nn
 
 from torchlsq.functional import w8_weight_operands
 from .observers import LSQFakeQuantizer
+from .conv_w8a8 import Conv2dW8A8, _fused_conv, _is_w8_conv
 from .packed_linear_a8 import _per_tensor_constants
 
 _LEVEL_DTYPES = {"int8": torch.int8, "uint8": torch.uint8}
@@ -110,20 +112,27 @@ class LinearW8A8(nn.Module):
 
 
 def convert_w8a8(model, input_quantizers, inplace=False):
-    """Replace the linear layers of `model` that `input_quantizers` lists -- a dict from a module's qualified name (as in
-    `model.named_modules()`) to the trained per-tensor `LSQFakeQuantizer` of its input -- by `LinearW8A8`; everything else is
-    left alone.  A listed name that is no `nn.Linear` with a trained per-channel (ch_axis 0) or per-tensor `LSQFakeQuantizer`
-    weight quantizer without group_size is an error.  Returns the model (a deep copy unless inplace=True; the quantizers are
-    only read)."""
+    """Replace the layers of `model` that `input_quantizers` lists -- a dict from a module's qualified name (as in
+    `model.named_modules()`) to the trained per-tensor `LSQFakeQuantizer` of its input -- by `LinearW8A8` (an `nn.Linear`) or
+    `Conv2dW8A8` (a plain `nn.Conv2d` / `torch.ao.nn.qat.Conv2d` with groups == 1 and padding_mode 'zeros'); everything else
+    is left alone.  A listed name that is neither, or whose weight quantizer is not a trained per-channel (ch_axis 0) or
+    per-tensor `LSQFakeQuantizer` without group_size, is an error; so is a fused Conv-BN / Conv-ReLU QAT module.  Returns the
+    model (a deep copy unless inplace=True; the quantizers are only read)."""
     if not inplace:
         model = copy.deepcopy(model)
     modules = dict(model.named_modules())
     for name, quantizer in input_quantizers.items():
         child = modules.get(name)
-        if child is None or not _is_w8_linear(child):
-            raise ValueError("convert_w8a8: %r is not a linear layer with a trained per-channel (ch_axis 0) or per-tensor "
-                             "LSQFakeQuantizer weight quantizer" % name)
-        new = LinearW8A8.from_float(child, quantizer)
+        if child is not None and _fused_conv(child):
+            raise ValueError("convert_w8a8: %r is a fused %s module, not a linear layer or a plain 2-D convolution: its batch norm "
+                             "is not folded and its ReLU not applied by Conv2dW8A8 (not served)" % (name, type(child).__name__))
+        if child is not None and _is_w8_conv(child):
+            new = Conv2dW8A8.from_float(child, quantizer)
+        elif child is not None and _is_w8_linear(child):
+            new = LinearW8A8.from_float(child, quantizer)
+        else:
+            raise ValueError("convert_w8a8: %r is not a linear layer or a 2-D convolution with groups == 1 and zero padding that has "
+                             "a trained per-channel (ch_axis 0) or per-tensor LSQFakeQuantizer weight quantizer" % name)
         if name == "":
             return new
         parent_name, _, leaf = name.rpartition(".")
