@@ -1,7 +1,8 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
 ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes),
-the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so (ctypes)
+the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so and their form with an 8-bit output
+liblsq_hip_requant_w8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -356,6 +357,38 @@ _QCONV_W8_LIB, qconv_w8_error_str = _load_companion("liblsq_hip_qconv_w8.so", C_
 def qconv_w8_library():
     """The ctypes handle of liblsq_hip_qconv_w8.so (raises if it is missing)."""
     return _require_companion(_QCONV_W8_LIB, "qconv_w8", "the W8A8 conv2d op needs", qconv_w8_error_str)
+
+
+# W8A8 linear and conv2d with an 8-bit output: the next layer's per-tensor quantizer (and a ReLU) in the epilogue
+# (include/lsq_hip_requant_w8.h): a tenth companion library; the ABIs above stay as they are.
+class LsqRequantW8Out(ctypes.Structure):
+    """lsq_requant_w8_out (include/lsq_hip_requant_w8.h): the output quantizer of one call"""
+    _fields_ = [("out_scale", ctypes.c_void_p), ("out_shift", ctypes.c_void_p)] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "relu", "mid_dtype")]
+
+
+REQUANT_W8_ABI_VERSION = 1
+_ROP = ctypes.POINTER(LsqRequantW8Out)
+_PLAN9 = ctypes.POINTER(ctypes.c_int32 * 9)
+C_ABI_REQUANT_W8 = {
+    "lsq_requant_w8_abi_version": (_int, []),
+    "lsq_requant_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_requant_w8_linear_levels": (_int, [_int, _vp, _i64, _vp, _vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _int, _ROP, _vp, _vp]),
+    "lsq_requant_w8_linear": (_int, [_int, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _int,
+                                     _ROP, _vp, _vp, _vp]),
+    "lsq_requant_w8_conv_levels": (_int, [_int, _vp, _vp, _vp, _CGP, _int, _vp, _vp, _vp, _vp, _int, _ROP, _vp, _vp]),
+    "lsq_requant_w8_conv": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _CGP, _int, _vp, _vp, _vp, _vp, _int, _ROP, _vp, _vp,
+                                   _vp]),
+    "lsq_requant_w8_plan_linear": (_int, [_i64, _i64, _i64, _int, _int, _PLAN9]),
+    "lsq_requant_w8_plan_conv": (_int, [_CGP, _int, _int, _PLAN9]),
+}
+_REQUANT_W8_LIB, requant_w8_error_str = _load_companion("liblsq_hip_requant_w8.so", C_ABI_REQUANT_W8, "lsq_requant_w8_abi_version",
+                                                        REQUANT_W8_ABI_VERSION)
+
+
+def requant_w8_library():
+    """The ctypes handle of liblsq_hip_requant_w8.so (raises if it is missing)."""
+    return _require_companion(_REQUANT_W8_LIB, "requant_w8", "the W8A8 ops with an 8-bit output need", requant_w8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

@@ -41,12 +41,14 @@ from ._qgemm_host import qgemm_forward, qgemm_plan  # noqa: F401
 from ._qgemm_a8_host import qgemm_a8_forward, qgemm_a8_forward_levels, qgemm_a8_min_rows, qgemm_a8_plan  # noqa: F401
 from ._qlinear_w8_host import qlinear_w8_forward, qlinear_w8_forward_levels, qlinear_w8_plan  # noqa: F401
 from ._qconv_w8_host import qconv_w8_forward, qconv_w8_forward_levels, qconv_w8_plan  # noqa: F401
+from ._requant_w8_host import (requant_w8_conv, requant_w8_conv_levels, requant_w8_linear, requant_w8_linear_levels,  # noqa: F401
+                               requant_w8_plan_conv, requant_w8_plan_linear)
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -137,6 +139,19 @@ _lib_def.define("lsq_conv2d_w8_q8(Tensor x_levels, Tensor s_x, Tensor zx, Tensor
 _lib_def.define("lsq_conv2d_w8_a8(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
                 "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias, int[2] stride, int[2] padding, "
                 "int[2] dilation) -> Tensor")
+#  * the four W8A8 ops with an 8-bit OUTPUT: the same sums and fp32 steps, a rounding to `mid_dtype`, an optional ReLU and the
+#    next layer's per-tensor quantizer (out_scale, out_shift, its range) in the epilogue; the result is the level tensor (uint8
+#    for a range in 0..255, int8 for one in -128..127) (liblsq_hip_requant_w8.so, include/lsq_hip_requant_w8.h).  Inference only.
+_OUT_Q = "Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, int out_type_max, bool relu"
+_lib_def.define("lsq_linear_w8_q8_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, %s, ScalarType mid_dtype) -> Tensor" % _OUT_Q)
+_lib_def.define("lsq_linear_w8_a8_q(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
+                "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias, %s) -> Tensor" % _OUT_Q)
+_lib_def.define("lsq_conv2d_w8_q8_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, int[2] stride, int[2] padding, int[2] dilation, %s, ScalarType mid_dtype) -> Tensor" % _OUT_Q)
+_lib_def.define("lsq_conv2d_w8_a8_q(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
+                "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias, int[2] stride, int[2] padding, "
+                "int[2] dilation, %s) -> Tensor" % _OUT_Q)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -608,6 +623,63 @@ def _conv2d_w8_a8_no_grad(x, act_scale, act_shift, quant_min, quant_max, type_mi
 
 _lib_def.impl("lsq_conv2d_w8_q8", _conv2d_w8_q8_no_grad, "Autograd")
 _lib_def.impl("lsq_conv2d_w8_a8", _conv2d_w8_a8_no_grad, "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the W8A8 ops with an 8-bit output (_requant_w8_host.py): GPU tensors -> liblsq_hip_requant_w8.so (one call), CPU tensors ->
+# the composition of the ops above that defines them; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_w8_q8_q", requant_w8_linear_levels)
+    _lib_key.impl("lsq_linear_w8_a8_q", requant_w8_linear)
+    _lib_key.impl("lsq_conv2d_w8_q8_q", requant_w8_conv_levels)
+    _lib_key.impl("lsq_conv2d_w8_a8_q", requant_w8_conv)
+del _lib_key
+
+
+def _fake_level_dtype(quant_max, type_max):
+    return torch.uint8 if max(quant_max, type_max) > 127 else torch.int8
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_w8_q8_q", lib=_lib_def)
+def _fake_linear_w8_q8_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, out_scale, out_shift, out_quant_min, out_quant_max,
+                         out_type_min, out_type_max, relu, mid_dtype):
+    return torch.empty(x_levels.shape[:-1] + (w_levels.shape[0],), dtype=_fake_level_dtype(out_quant_max, out_type_max),
+                       device=x_levels.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_w8_a8_q", lib=_lib_def)
+def _fake_linear_w8_a8_q(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels, w_scale, w_zero, bias, out_scale,
+                         out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu):
+    return torch.empty(x.shape[:-1] + (w_levels.shape[0],), dtype=_fake_level_dtype(out_quant_max, out_type_max), device=x.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_conv2d_w8_q8_q", lib=_lib_def)
+def _fake_conv2d_w8_q8_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation, out_scale, out_shift,
+                         out_quant_min, out_quant_max, out_type_min, out_type_max, relu, mid_dtype):
+    return _fake_conv2d_w8(x_levels, w_levels, stride, padding, dilation, _fake_level_dtype(out_quant_max, out_type_max))
+
+
+@torch.library.register_fake("torchlsq::lsq_conv2d_w8_a8_q", lib=_lib_def)
+def _fake_conv2d_w8_a8_q(x, act_scale, act_shift, quant_min, quant_max, type_min, type_max, w_levels, w_scale, w_zero, bias, stride,
+                         padding, dilation, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu):
+    return _fake_conv2d_w8(x, w_levels, stride, padding, dilation, _fake_level_dtype(out_quant_max, out_type_max))
+
+
+def _requant_no_grad(name, grad_args):
+    """the Autograd kernel of an inference-only op: refuses an input that requires grad (`grad_args`: positions of the floating
+    tensors among the arguments), then dispatches below autograd"""
+    def kernel(*args):
+        _refuse_grad(name, *(args[i] for i in grad_args))
+        with torch._C._AutoDispatchBelowAutograd():
+            return getattr(torch.ops.torchlsq, name)(*args)
+    return kernel
+
+
+_lib_def.impl("lsq_linear_w8_q8_q", _requant_no_grad("lsq_linear_w8_q8_q", (1, 4, 6, 7, 8)), "Autograd")
+_lib_def.impl("lsq_linear_w8_a8_q", _requant_no_grad("lsq_linear_w8_a8_q", (0, 1, 2, 8, 10, 11, 12)), "Autograd")
+_lib_def.impl("lsq_conv2d_w8_q8_q", _requant_no_grad("lsq_conv2d_w8_q8_q", (1, 4, 6, 10, 11)), "Autograd")
+_lib_def.impl("lsq_conv2d_w8_a8_q", _requant_no_grad("lsq_conv2d_w8_a8_q", (0, 1, 2, 8, 10, 14, 15)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ from torch.autograd.function import once_differentiable
 
 from . import extension as _E
 from .extension import _assert_has_ops
+from ._qlinear_a8_host import _act_constants
 
 Tensor = torch.Tensor
 
@@ -800,3 +801,123 @@ def lsq_conv2d_w8a8(x: Tensor, weight_q: Tensor, bias: Tensor = None, stride=1, 
     type_min = quant_min if type_min is None else type_min
     type_max = quant_max if type_max is None else type_max
     return torch.ops.torchlsq.lsq_conv2d_w8_a8(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w)
+
+
+class LevelsTensor:
+    """The 8-bit levels of a per-tensor quantized activation with their constants ON THE DEVICE: what one W8A8 layer with an
+    8-bit output hands to the next.  `levels` (uint8 or int8; a convolution's are a logical [B, C, H, W] tensor in channels-last
+    memory), `scale` (float32 [1], the sanitised scale) and `zero_point` (int32 [1]) on the levels' device, and the level range
+    `quant_min`, `quant_max`, `type_min`, `type_max`.  The real value of a level is (level - zero_point) * scale.  Nothing here
+    reads back to the host except `to_quantized()`."""
+
+    def __init__(self, levels, scale, zero_point, quant_min, quant_max, type_min=None, type_max=None):
+        assert levels.dtype in (torch.uint8, torch.int8), "LevelsTensor holds uint8 or int8 levels"
+        assert scale.dtype == torch.float32 and scale.numel() == 1 and zero_point.dtype == torch.int32 and zero_point.numel() == 1, \
+            "LevelsTensor needs one float32 scale and one int32 zero point (tensors on the levels' device)"
+        self.levels, self.scale, self.zero_point = levels, scale.reshape(1), zero_point.reshape(1)
+        self.quant_min, self.quant_max = int(quant_min), int(quant_max)
+        self.type_min = self.quant_min if type_min is None else int(type_min)
+        self.type_max = self.quant_max if type_max is None else int(type_max)
+
+    shape = property(lambda self: self.levels.shape)
+    device = property(lambda self: self.levels.device)
+    dtype = property(lambda self: self.levels.dtype)
+
+    def dequantize(self, dtype=torch.float32) -> Tensor:
+        """(levels - zero_point) * scale in float32, then `dtype`"""
+        return ((self.levels.to(torch.float32) - self.zero_point.to(torch.float32)) * self.scale).to(dtype)
+
+    def to_quantized(self) -> Tensor:
+        """a per-tensor torch.quint8 / torch.qint8 tensor of the same levels; reads scale and zero point back to the host"""
+        return torch._make_per_tensor_quantized_tensor(self.levels, float(self.scale.item()), int(self.zero_point.item()))
+
+    def flatten(self, start_dim=1, end_dim=-1):
+        """the levels flattened like `torch.flatten` (of the logical shape), same constants"""
+        return LevelsTensor(self.levels.flatten(start_dim, end_dim), self.scale, self.zero_point, self.quant_min, self.quant_max,
+                            self.type_min, self.type_max)
+
+    @classmethod
+    def from_quantized(cls, xq: Tensor):
+        """from a per-tensor torch.quint8 / torch.qint8 tensor; its scale and zero point are uploaded once"""
+        assert xq.is_quantized and xq.qscheme() in (torch.per_tensor_affine, torch.per_tensor_symmetric) and \
+            xq.dtype in (torch.quint8, torch.qint8), "LevelsTensor.from_quantized needs a per-tensor torch.quint8 / torch.qint8 tensor"
+        lo, hi = (0, 255) if xq.dtype == torch.quint8 else (-128, 127)
+        return cls(xq.int_repr(), torch.tensor([xq.q_scale()], dtype=torch.float32, device=xq.device),
+                   torch.tensor([xq.q_zero_point()], dtype=torch.int32, device=xq.device), lo, hi, lo, hi)
+
+
+def _levels_out(levels, out_scale, out_shift, rng):
+    s, z = _act_constants(out_scale, out_shift, rng[2], rng[3])
+    return LevelsTensor(levels, s, z, *rng)
+
+
+def _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu):
+    assert out_scale is not None and out_shift is not None and out_quant_min is not None and out_quant_max is not None, \
+        "%s needs the output quantizer's out_scale, out_shift, out_quant_min and out_quant_max" % what
+    tmin = out_quant_min if out_type_min is None else out_type_min
+    tmax = out_quant_max if out_type_max is None else out_type_max
+    sc = out_scale.detach().reshape(-1)[:1].to(torch.float32)
+    sh = out_shift.detach().reshape(-1)[:1].to(torch.float32)
+    return (sc, sh, int(out_quant_min), int(out_quant_max), int(tmin), int(tmax), bool(relu))
+
+
+def lsq_linear_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, scale: Tensor = None, shift: Tensor = None, quant_min: int = None,
+                      quant_max: int = None, type_min: int = None, type_max: int = None, out_scale: Tensor = None,
+                      out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None,
+                      out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32) -> LevelsTensor:
+    """`lsq_linear_w8a8` with an 8-bit output: the integer sum, its fp32 steps `v`, `u = float(round_to(mid_dtype, v))`, an
+    optional ReLU (a select: a NaN stays a NaN) and the levels of the per-tensor quantizer (`out_scale`, `out_shift`,
+    `out_quant_min`, `out_quant_max`, type range) of `u` -- in one launch, one byte written per output
+    (liblsq_hip_requant_w8.so).  Bit for bit the composition `lsq_linear_w8a8(..., out_dtype=mid_dtype)`, the select,
+    `lsq_levels_per_tensor`; `mid_dtype` is the dtype in which the unfused model hands y to the next quantizer.
+
+    x is a `LevelsTensor` (its device constants are used, nothing is read back), a per-tensor `torch.quint8` / `torch.qint8`
+    tensor, or a floating tensor with the INPUT quantizer's `scale`, `shift`, `quant_min`, `quant_max` (then `mid_dtype` is x's
+    dtype).  Returns a `LevelsTensor` whose constants are formed on the device from `out_scale` and `out_shift`.
+    Inference only."""
+    _assert_has_ops()
+    what = "lsq_linear_w8a8_q"
+    w = w8_weight_operands(weight_q) + (bias,)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    if isinstance(x, LevelsTensor):
+        lv = torch.ops.torchlsq.lsq_linear_w8_q8_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype)
+    else:
+        assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
+            "%s on a floating x needs the input quantizer's scale, shift, quant_min and quant_max" % what
+        assert mid_dtype in (None, torch.float32, x.dtype), "a floating x fixes mid_dtype to x's dtype"
+        type_min = quant_min if type_min is None else type_min
+        type_max = quant_max if type_max is None else type_max
+        lv = torch.ops.torchlsq.lsq_linear_w8_a8_q(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w, *o)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_conv2d_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1, scale: Tensor = None,
+                      shift: Tensor = None, quant_min: int = None, quant_max: int = None, type_min: int = None, type_max: int = None,
+                      out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None,
+                      out_type_min: int = None, out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32) -> LevelsTensor:
+    """`lsq_conv2d_w8a8` with an 8-bit output, exactly as `lsq_linear_w8a8_q` is to `lsq_linear_w8a8`.  The returned levels are a
+    logical [B, Cout, OH, OW] tensor in channels-last memory: the next convolution's operand as it lies.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_conv2d_w8a8_q"
+    if groups != 1:
+        raise ValueError("lsq_conv2d_w8a8_q serves groups == 1 only, got groups = %d" % groups)
+    assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 4, \
+        "lsq_conv2d_w8a8_q needs a 4-D torch.qint8 / torch.quint8 weight [out_channels, in_channels, kh, kw]"
+    stride, dilation = _two(stride, "stride"), _two(dilation, "dilation")
+    padding = _conv_padding(padding, weight_q.shape[2:], stride, dilation)
+    w = w8_weight_operands(weight_q) + (bias, list(stride), list(padding), list(dilation))
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    if isinstance(x, LevelsTensor):
+        lv = torch.ops.torchlsq.lsq_conv2d_w8_q8_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype)
+    else:
+        assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
+            "%s on a floating x needs the input quantizer's scale, shift, quant_min and quant_max" % what
+        assert mid_dtype in (None, torch.float32, x.dtype), "a floating x fixes mid_dtype to x's dtype"
+        type_min = quant_min if type_min is None else type_min
+        type_max = quant_max if type_max is None else type_max
+        lv = torch.ops.torchlsq.lsq_conv2d_w8_a8_q(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w, *o)
+    return _levels_out(lv, o[0], o[1], o[2:6])
