@@ -1,8 +1,8 @@
 """The native libraries of the package and how they are opened: liblsq_hip.so (include/lsq_hip.h, ctypes), liblsq_cpu.so
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
 ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes),
-the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so and their form with an 8-bit output
-liblsq_hip_requant_w8.so (ctypes)
+the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so, their form with an 8-bit output
+liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -389,6 +389,41 @@ _REQUANT_W8_LIB, requant_w8_error_str = _load_companion("liblsq_hip_requant_w8.s
 def requant_w8_library():
     """The ctypes handle of liblsq_hip_requant_w8.so (raises if it is missing)."""
     return _require_companion(_REQUANT_W8_LIB, "requant_w8", "the W8A8 ops with an 8-bit output need", requant_w8_error_str)
+
+
+# W8A8 linear and conv2d that close a residual block: a residual given as levels added in the 8-bit epilogue
+# (include/lsq_hip_resadd_w8.h): an eleventh companion library; the ABIs above stay as they are.
+class LsqResaddW8Res(ctypes.Structure):
+    """lsq_resadd_w8_res (include/lsq_hip_resadd_w8.h): the residual levels of one call and their device constants"""
+    _fields_ = [("levels", ctypes.c_void_p), ("level_dtype", ctypes.c_int64), ("scale", ctypes.c_void_p), ("zero_point", ctypes.c_void_p)]
+
+
+class LsqResaddW8Pre(ctypes.Structure):
+    """lsq_resadd_w8_pre (include/lsq_hip_resadd_w8.h): the layer's own output fake-quantizer"""
+    _fields_ = [("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p)] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max")]
+
+
+RESADD_W8_ABI_VERSION = 1
+_RRP = ctypes.POINTER(LsqResaddW8Res)
+_RPP = ctypes.POINTER(LsqResaddW8Pre)
+_PLAN10 = ctypes.POINTER(ctypes.c_int32 * 10)
+C_ABI_RESADD_W8 = {
+    "lsq_resadd_w8_abi_version": (_int, []),
+    "lsq_resadd_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_resadd_w8_linear_levels": (_int, [_int, _vp, _i64, _vp, _vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _int, _ROP, _RRP, _RPP, _vp,
+                                           _vp]),
+    "lsq_resadd_w8_conv_levels": (_int, [_int, _vp, _vp, _vp, _CGP, _int, _vp, _vp, _vp, _vp, _int, _ROP, _RRP, _RPP, _vp, _vp]),
+    "lsq_resadd_w8_plan_linear": (_int, [_i64, _i64, _i64, _int, _int, _int, _PLAN10]),
+    "lsq_resadd_w8_plan_conv": (_int, [_CGP, _int, _int, _int, _PLAN10]),
+}
+_RESADD_W8_LIB, resadd_w8_error_str = _load_companion("liblsq_hip_resadd_w8.so", C_ABI_RESADD_W8, "lsq_resadd_w8_abi_version",
+                                                      RESADD_W8_ABI_VERSION)
+
+
+def resadd_w8_library():
+    """The ctypes handle of liblsq_hip_resadd_w8.so (raises if it is missing)."""
+    return _require_companion(_RESADD_W8_LIB, "resadd_w8", "the W8A8 ops that add a levels residual need", resadd_w8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

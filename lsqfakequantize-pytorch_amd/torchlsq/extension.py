@@ -43,12 +43,13 @@ from ._qlinear_w8_host import qlinear_w8_forward, qlinear_w8_forward_levels, qli
 from ._qconv_w8_host import qconv_w8_forward, qconv_w8_forward_levels, qconv_w8_plan  # noqa: F401
 from ._requant_w8_host import (requant_w8_conv, requant_w8_conv_levels, requant_w8_linear, requant_w8_linear_levels,  # noqa: F401
                                requant_w8_plan_conv, requant_w8_plan_linear)
+from ._resadd_w8_host import resadd_w8_conv_levels, resadd_w8_linear_levels, resadd_w8_plan_conv, resadd_w8_plan_linear  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -152,6 +153,16 @@ _lib_def.define("lsq_conv2d_w8_q8_q(Tensor x_levels, Tensor s_x, Tensor zx, Tens
 _lib_def.define("lsq_conv2d_w8_a8_q(Tensor x, Tensor act_scale, Tensor act_shift, int quant_min, int quant_max, int type_min, "
                 "int type_max, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias, int[2] stride, int[2] padding, "
                 "int[2] dilation, %s) -> Tensor" % _OUT_Q)
+#  * the two levels-in ops of those four with a RESIDUAL given as 8-bit levels (res_levels in the output's shape, res_scale
+#    float32 [1], res_zero int32 [1]) added between the rounding to `mid_dtype` and the ReLU, after the layer's own optional
+#    per-tensor output fake-quantizer (pre_scale, pre_shift, its range): the end of a residual block in one launch
+#    (liblsq_hip_resadd_w8.so, include/lsq_hip_resadd_w8.h).  Inference only.
+_RES_Q = ("Tensor res_levels, Tensor res_scale, Tensor res_zero, Tensor? pre_scale, Tensor? pre_shift, int pre_quant_min, "
+          "int pre_quant_max, int pre_type_min, int pre_type_max")
+_lib_def.define("lsq_linear_w8_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
+_lib_def.define("lsq_conv2d_w8_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, int[2] stride, int[2] padding, int[2] dilation, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -680,6 +691,35 @@ _lib_def.impl("lsq_linear_w8_q8_q", _requant_no_grad("lsq_linear_w8_q8_q", (1, 4
 _lib_def.impl("lsq_linear_w8_a8_q", _requant_no_grad("lsq_linear_w8_a8_q", (0, 1, 2, 8, 10, 11, 12)), "Autograd")
 _lib_def.impl("lsq_conv2d_w8_q8_q", _requant_no_grad("lsq_conv2d_w8_q8_q", (1, 4, 6, 10, 11)), "Autograd")
 _lib_def.impl("lsq_conv2d_w8_a8_q", _requant_no_grad("lsq_conv2d_w8_a8_q", (0, 1, 2, 8, 10, 14, 15)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the W8A8 ops that add a levels residual in the 8-bit epilogue (_resadd_w8_host.py): GPU tensors -> liblsq_hip_resadd_w8.so (one
+# call), CPU tensors -> the composition of the ops above that defines them; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_w8_q8_add_q", resadd_w8_linear_levels)
+    _lib_key.impl("lsq_conv2d_w8_q8_add_q", resadd_w8_conv_levels)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_w8_q8_add_q", lib=_lib_def)
+def _fake_linear_w8_q8_add_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, out_scale, out_shift, out_quant_min, out_quant_max,
+                             out_type_min, out_type_max, relu, mid_dtype, res_levels, res_scale, res_zero, pre_scale, pre_shift,
+                             pre_quant_min, pre_quant_max, pre_type_min, pre_type_max):
+    return torch.empty(x_levels.shape[:-1] + (w_levels.shape[0],), dtype=_fake_level_dtype(out_quant_max, out_type_max),
+                       device=x_levels.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_conv2d_w8_q8_add_q", lib=_lib_def)
+def _fake_conv2d_w8_q8_add_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation, out_scale, out_shift,
+                             out_quant_min, out_quant_max, out_type_min, out_type_max, relu, mid_dtype, res_levels, res_scale, res_zero,
+                             pre_scale, pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max):
+    return _fake_conv2d_w8(x_levels, w_levels, stride, padding, dilation, _fake_level_dtype(out_quant_max, out_type_max))
+
+
+_lib_def.impl("lsq_linear_w8_q8_add_q", _requant_no_grad("lsq_linear_w8_q8_add_q", (1, 4, 6, 7, 8, 16, 18, 19)), "Autograd")
+_lib_def.impl("lsq_conv2d_w8_q8_add_q", _requant_no_grad("lsq_conv2d_w8_q8_add_q", (1, 4, 6, 10, 11, 19, 21, 22)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

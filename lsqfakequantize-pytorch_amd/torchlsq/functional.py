@@ -921,3 +921,70 @@ def lsq_conv2d_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, stride=1, paddin
         type_max = quant_max if type_max is None else type_max
         lv = torch.ops.torchlsq.lsq_conv2d_w8_a8_q(x, scale, shift, int(quant_min), int(quant_max), int(type_min), int(type_max), *w, *o)
     return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def _res_args(what, residual, pre_scale, pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max):
+    assert isinstance(residual, LevelsTensor), "%s needs the residual as a LevelsTensor" % what
+    if pre_scale is None:
+        assert pre_shift is None, "%s: pre_scale and pre_shift come together" % what
+        return (residual.levels, residual.scale, residual.zero_point, None, None, 0, 255, 0, 255)
+    assert pre_shift is not None and pre_quant_min is not None and pre_quant_max is not None, \
+        "%s with a pre-quantizer needs pre_scale, pre_shift, pre_quant_min and pre_quant_max" % what
+    tmin = pre_quant_min if pre_type_min is None else pre_type_min
+    tmax = pre_quant_max if pre_type_max is None else pre_type_max
+    sc = pre_scale.detach().reshape(-1)[:1].to(torch.float32)
+    sh = pre_shift.detach().reshape(-1)[:1].to(torch.float32)
+    return (residual.levels, residual.scale, residual.zero_point, sc, sh, int(pre_quant_min), int(pre_quant_max), int(tmin), int(tmax))
+
+
+def lsq_linear_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTensor, out_scale: Tensor = None, out_shift: Tensor = None,
+                          out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                          relu: bool = False, mid_dtype=torch.float32, pre_scale: Tensor = None, pre_shift: Tensor = None,
+                          pre_quant_min: int = None, pre_quant_max: int = None, pre_type_min: int = None,
+                          pre_type_max: int = None) -> LevelsTensor:
+    """The end of a residual block in one launch: `lsq_linear_w8a8_q` with `residual`, a `LevelsTensor` of the output's shape,
+    added before the ReLU.  With u the layer's value rounded to `mid_dtype`: `p` is u, or with a pre-quantizer (`pre_scale`,
+    `pre_shift`, `pre_quant_min`, `pre_quant_max`, type range: the layer's own output fake-quantizer, as a torch.ao QAT layer
+    applies it before a `FloatFunctional.add`) `lsq(u, ...)`; `t = p + residual.dequantize(mid_dtype)` in `mid_dtype`; an
+    optional ReLU (a select); the levels of the output quantizer (the add's) of t -- one byte read and one written per output
+    (liblsq_hip_resadd_w8.so).  Bit for bit the composition `lsq_linear_w8a8(..., out_dtype=mid_dtype)`, `lsq`, the add, the
+    select, `lsq_levels_per_tensor`.
+
+    x is a `LevelsTensor` or a per-tensor `torch.quint8` / `torch.qint8` tensor.  Returns a `LevelsTensor`; nothing is read
+    back from the device.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_linear_w8a8_add_q"
+    w = w8_weight_operands(weight_q) + (bias,)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
+    r = _res_args(what, residual, pre_scale, pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max)
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    assert isinstance(x, LevelsTensor), "%s needs x as a LevelsTensor or a per-tensor quantized tensor" % what
+    lv = torch.ops.torchlsq.lsq_linear_w8_q8_add_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype, *r)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_conv2d_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTensor, stride=1, padding=0, dilation=1, groups: int = 1,
+                          out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None,
+                          out_type_min: int = None, out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32,
+                          pre_scale: Tensor = None, pre_shift: Tensor = None, pre_quant_min: int = None, pre_quant_max: int = None,
+                          pre_type_min: int = None, pre_type_max: int = None) -> LevelsTensor:
+    """`lsq_conv2d_w8a8_q` with a residual, exactly as `lsq_linear_w8a8_add_q` is to `lsq_linear_w8a8_q`.  `residual` holds a
+    logical [B, Cout, OH, OW] level tensor; one that is not in channels-last memory is copied into that format first.  The
+    returned levels are in channels-last memory.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_conv2d_w8a8_add_q"
+    if groups != 1:
+        raise ValueError("lsq_conv2d_w8a8_add_q serves groups == 1 only, got groups = %d" % groups)
+    assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 4, \
+        "lsq_conv2d_w8a8_add_q needs a 4-D torch.qint8 / torch.quint8 weight [out_channels, in_channels, kh, kw]"
+    stride, dilation = _two(stride, "stride"), _two(dilation, "dilation")
+    padding = _conv_padding(padding, weight_q.shape[2:], stride, dilation)
+    w = w8_weight_operands(weight_q) + (bias, list(stride), list(padding), list(dilation))
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
+    r = _res_args(what, residual, pre_scale, pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max)
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    assert isinstance(x, LevelsTensor), "%s needs x as a LevelsTensor or a per-tensor quantized tensor" % what
+    lv = torch.ops.torchlsq.lsq_conv2d_w8_q8_add_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype, *r)
+    return _levels_out(lv, o[0], o[1], o[2:6])
