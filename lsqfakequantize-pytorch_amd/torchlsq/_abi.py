@@ -2,7 +2,7 @@
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
 ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes),
 the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so, their form with an 8-bit output
-liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so (ctypes)
+liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so, pooling on levels liblsq_hip_pool_w8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -424,6 +424,40 @@ _RESADD_W8_LIB, resadd_w8_error_str = _load_companion("liblsq_hip_resadd_w8.so",
 def resadd_w8_library():
     """The ctypes handle of liblsq_hip_resadd_w8.so (raises if it is missing)."""
     return _require_companion(_RESADD_W8_LIB, "resadd_w8", "the W8A8 ops that add a levels residual need", resadd_w8_error_str)
+
+
+# 2-D max and average pooling on channels-last 8-bit levels (include/lsq_hip_pool_w8.h): a twelfth companion library; the ABIs
+# above stay as they are.
+class LsqPoolW8Geom(ctypes.Structure):
+    """lsq_pool_w8_geom (include/lsq_hip_pool_w8.h): x [B, H, W, C], kernel, stride, padding, dilation, ceil_mode"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "C", "H", "W", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "ceil_mode")]
+
+
+class LsqPoolW8Avg(ctypes.Structure):
+    """lsq_pool_w8_avg (include/lsq_hip_pool_w8.h): the average pool's device constants, output quantizer (or none) and divisor"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_x", "zx", "out_scale", "out_shift")] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "mid_dtype", "count_include_pad",
+                                                    "has_divisor", "divisor_override")]
+
+
+POOL_W8_ABI_VERSION = 1
+_PGP = ctypes.POINTER(LsqPoolW8Geom)
+_PLAN8 = ctypes.POINTER(ctypes.c_int32 * 8)
+C_ABI_POOL_W8 = {
+    "lsq_pool_w8_abi_version": (_int, []),
+    "lsq_pool_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_pool_w8_max": (_int, [_int, _vp, _PGP, _vp, _vp]),
+    "lsq_pool_w8_avg_forward": (_int, [_int, _vp, _PGP, ctypes.POINTER(LsqPoolW8Avg), _vp, _vp]),
+    "lsq_pool_w8_adaptive": (_int, [_i64, _i64, _PGP]),
+    "lsq_pool_w8_plan_max": (_int, [_PGP, _int, _PLAN8]),
+    "lsq_pool_w8_plan_avg": (_int, [_PGP, _int, _PLAN8]),
+}
+_POOL_W8_LIB, pool_w8_error_str = _load_companion("liblsq_hip_pool_w8.so", C_ABI_POOL_W8, "lsq_pool_w8_abi_version", POOL_W8_ABI_VERSION)
+
+
+def pool_w8_library():
+    """The ctypes handle of liblsq_hip_pool_w8.so (raises if it is missing)."""
+    return _require_companion(_POOL_W8_LIB, "pool_w8", "the pooling ops on 8-bit levels need", pool_w8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

@@ -44,12 +44,14 @@ from ._qconv_w8_host import qconv_w8_forward, qconv_w8_forward_levels, qconv_w8_
 from ._requant_w8_host import (requant_w8_conv, requant_w8_conv_levels, requant_w8_linear, requant_w8_linear_levels,  # noqa: F401
                                requant_w8_plan_conv, requant_w8_plan_linear)
 from ._resadd_w8_host import resadd_w8_conv_levels, resadd_w8_linear_levels, resadd_w8_plan_conv, resadd_w8_plan_linear  # noqa: F401
+from ._pool_w8_host import (pool_w8_adaptive_kernel, pool_w8_avg, pool_w8_avg_q, pool_w8_max, pool_w8_plan_avg,  # noqa: F401
+                            pool_w8_plan_max)
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -163,6 +165,17 @@ _lib_def.define("lsq_linear_w8_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, 
                 "Tensor? bias, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
 _lib_def.define("lsq_conv2d_w8_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
                 "Tensor? bias, int[2] stride, int[2] padding, int[2] dilation, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
+#  * 2-D pooling on 8-bit LEVELS [B, C, H, W], read channels-last (liblsq_hip_pool_w8.so, include/lsq_hip_pool_w8.h): the max pool
+#    gives levels of the same quantizer; the average pool sums (level - x_zero) exactly, takes (float(S) * x_scale) / float(D)
+#    in fp32 with ATen's divisor D, rounds to `mid_dtype` and gives the levels of the output quantizer (_q) or the floats
+#    themselves.  The results are [B, C, OH, OW] in channels-last memory.  Inference only.
+_lib_def.define("lsq_max_pool2d_q8(Tensor levels, int[2] kernel_size, int[2] stride, int[2] padding, int[2] dilation, "
+                "bool ceil_mode) -> Tensor")
+_AVG_POOL = ("Tensor levels, Tensor x_scale, Tensor x_zero, int[2] kernel_size, int[2] stride, int[2] padding, bool ceil_mode, "
+             "bool count_include_pad, int? divisor_override")
+_lib_def.define("lsq_avg_pool2d_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
+                "int out_type_max, ScalarType mid_dtype) -> Tensor" % _AVG_POOL)
+_lib_def.define("lsq_avg_pool2d_q8(%s, ScalarType out_dtype) -> Tensor" % _AVG_POOL)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -720,6 +733,49 @@ def _fake_conv2d_w8_q8_add_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias,
 
 _lib_def.impl("lsq_linear_w8_q8_add_q", _requant_no_grad("lsq_linear_w8_q8_add_q", (1, 4, 6, 7, 8, 16, 18, 19)), "Autograd")
 _lib_def.impl("lsq_conv2d_w8_q8_add_q", _requant_no_grad("lsq_conv2d_w8_q8_add_q", (1, 4, 6, 10, 11, 19, 21, 22)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# pooling on 8-bit levels (_pool_w8_host.py): GPU tensors -> liblsq_hip_pool_w8.so (one call), CPU tensors -> the definition in
+# torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_max_pool2d_q8", pool_w8_max)
+    _lib_key.impl("lsq_avg_pool2d_q8_q", pool_w8_avg_q)
+    _lib_key.impl("lsq_avg_pool2d_q8", pool_w8_avg)
+del _lib_key
+
+
+def _fake_pool_w8(levels, kernel_size, stride, padding, dilation, ceil_mode, dtype):
+    def extent(n, k, s, p, d):
+        num = n + 2 * p - d * (k - 1) - 1
+        out = (-(-num // s) if ceil_mode else num // s) + 1
+        return out - 1 if ceil_mode and (out - 1) * s >= n + p else out
+    B, C, H, W = levels.shape
+    return torch.empty((B, C, extent(H, kernel_size[0], stride[0], padding[0], dilation[0]),
+                        extent(W, kernel_size[1], stride[1], padding[1], dilation[1])), dtype=dtype, device=levels.device,
+                       memory_format=torch.channels_last)
+
+
+@torch.library.register_fake("torchlsq::lsq_max_pool2d_q8", lib=_lib_def)
+def _fake_max_pool2d_q8(levels, kernel_size, stride, padding, dilation, ceil_mode):
+    return _fake_pool_w8(levels, kernel_size, stride, padding, dilation, ceil_mode, levels.dtype)
+
+
+@torch.library.register_fake("torchlsq::lsq_avg_pool2d_q8_q", lib=_lib_def)
+def _fake_avg_pool2d_q8_q(levels, x_scale, x_zero, kernel_size, stride, padding, ceil_mode, count_include_pad, divisor_override,
+                          out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype):
+    return _fake_pool_w8(levels, kernel_size, stride, padding, (1, 1), ceil_mode, _fake_level_dtype(out_quant_max, out_type_max))
+
+
+@torch.library.register_fake("torchlsq::lsq_avg_pool2d_q8", lib=_lib_def)
+def _fake_avg_pool2d_q8(levels, x_scale, x_zero, kernel_size, stride, padding, ceil_mode, count_include_pad, divisor_override, out_dtype):
+    return _fake_pool_w8(levels, kernel_size, stride, padding, (1, 1), ceil_mode, out_dtype)
+
+
+_lib_def.impl("lsq_max_pool2d_q8", _requant_no_grad("lsq_max_pool2d_q8", ()), "Autograd")
+_lib_def.impl("lsq_avg_pool2d_q8_q", _requant_no_grad("lsq_avg_pool2d_q8_q", (1, 9, 10)), "Autograd")
+_lib_def.impl("lsq_avg_pool2d_q8", _requant_no_grad("lsq_avg_pool2d_q8", (1,)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

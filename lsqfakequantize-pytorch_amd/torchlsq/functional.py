@@ -988,3 +988,81 @@ def lsq_conv2d_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTen
     assert isinstance(x, LevelsTensor), "%s needs x as a LevelsTensor or a per-tensor quantized tensor" % what
     lv = torch.ops.torchlsq.lsq_conv2d_w8_q8_add_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype, *r)
     return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def _pool_levels(what, x):
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    assert isinstance(x, LevelsTensor) and x.levels.dim() == 4, "%s needs x as a LevelsTensor (or a per-tensor quantized tensor) of [B, C, H, W]" % what
+    return x
+
+
+def _pool_geometry(kernel_size, stride, padding):
+    kernel = _two(kernel_size, "kernel_size")
+    return list(kernel), list(kernel if stride is None or stride == [] else _two(stride, "stride")), list(_two(padding, "padding"))
+
+
+def lsq_max_pool2d_w8(x: LevelsTensor, kernel_size, stride=None, padding=0, dilation=1, ceil_mode: bool = False) -> LevelsTensor:
+    """`F.max_pool2d` on 8-bit levels: the max over each window's taps inside the input of the levels as integers (a tap in the
+    padding does not take part), one byte read and a fraction of one written per activation (liblsq_hip_pool_w8.so).  The
+    result holds levels of the SAME quantizer: it carries x's `scale` and `zero_point` tensors as they are, nothing is copied or
+    read back.  Because dequantize is non-decreasing this is also, bit for bit, `F.max_pool2d(x.dequantize(dtype))` taken back
+    to levels.  `F.max_pool2d`'s arguments; padding is at most half the kernel.  A `LevelsTensor` in NCHW memory is copied to
+    channels-last first; the returned levels are a logical [B, C, OH, OW] tensor in channels-last memory.  Inference only."""
+    _assert_has_ops()
+    x = _pool_levels("lsq_max_pool2d_w8", x)
+    kernel, stride, padding = _pool_geometry(kernel_size, stride, padding)
+    lv = torch.ops.torchlsq.lsq_max_pool2d_q8(x.levels, kernel, stride, padding, list(_two(dilation, "dilation")), bool(ceil_mode))
+    return LevelsTensor(lv, x.scale, x.zero_point, x.quant_min, x.quant_max, x.type_min, x.type_max)
+
+
+def lsq_avg_pool2d_w8_q(x: LevelsTensor, kernel_size, stride=None, padding=0, ceil_mode: bool = False, count_include_pad: bool = True,
+                        divisor_override: int = None, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                        out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                        mid_dtype=torch.float32) -> LevelsTensor:
+    """`F.avg_pool2d` on 8-bit levels with an 8-bit output: the exact integer sum S of (level - zero_point) over each window's taps
+    inside the input, `v = (float(S) * scale) / float(D)` in fp32 with `F.avg_pool2d`'s divisor D (`divisor_override`, else the
+    window clipped to the padded extent with `count_include_pad`, else the taps inside the input), `u = round_to(mid_dtype, v)`
+    and the levels of the per-tensor output quantizer (`out_scale`, `out_shift`, `out_quant_min`, `out_quant_max`, type range) of
+    u -- one launch (liblsq_hip_pool_w8.so), nothing is read back.  v is within two roundings of the exact mean; it is not
+    ATen's float `avg_pool2d`, which sums rounded floats in an order of its own.  Returns a `LevelsTensor` in channels-last
+    memory whose constants are formed on the device.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_avg_pool2d_w8_q"
+    x = _pool_levels(what, x)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    kernel, stride, padding = _pool_geometry(kernel_size, stride, padding)
+    lv = torch.ops.torchlsq.lsq_avg_pool2d_q8_q(x.levels, x.scale, x.zero_point, kernel, stride, padding, bool(ceil_mode),
+                                                bool(count_include_pad), divisor_override, *o[:6], mid_dtype)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_avg_pool2d_w8(x: LevelsTensor, kernel_size, stride=None, padding=0, ceil_mode: bool = False, count_include_pad: bool = True,
+                      divisor_override: int = None, out_dtype=torch.float32) -> Tensor:
+    """`lsq_avg_pool2d_w8_q` without an output quantizer: the averages `round_to(out_dtype, v)` as a floating
+    [B, C, OH, OW] tensor in channels-last memory.  Inference only."""
+    _assert_has_ops()
+    x = _pool_levels("lsq_avg_pool2d_w8", x)
+    kernel, stride, padding = _pool_geometry(kernel_size, stride, padding)
+    return torch.ops.torchlsq.lsq_avg_pool2d_q8(x.levels, x.scale, x.zero_point, kernel, stride, padding, bool(ceil_mode),
+                                                bool(count_include_pad), divisor_override, out_dtype)
+
+
+def lsq_adaptive_avg_pool2d_w8_q(x: LevelsTensor, output_size, out_scale: Tensor = None, out_shift: Tensor = None,
+                                 out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None,
+                                 out_type_max: int = None, mid_dtype=torch.float32) -> LevelsTensor:
+    """`F.adaptive_avg_pool2d` on 8-bit levels with an 8-bit output, for an `output_size` that divides H and W evenly (1: global
+    pooling): `lsq_avg_pool2d_w8_q` with kernel = stride = (H / OH, W / OW).  Any other output size is refused."""
+    _assert_has_ops()
+    x = _pool_levels("lsq_adaptive_avg_pool2d_w8_q", x)
+    kernel = _E.pool_w8_adaptive_kernel(x.shape[2], x.shape[3], output_size)
+    return lsq_avg_pool2d_w8_q(x, kernel, kernel, 0, False, True, None, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
+                               out_type_max, mid_dtype)
+
+
+def lsq_adaptive_avg_pool2d_w8(x: LevelsTensor, output_size, out_dtype=torch.float32) -> Tensor:
+    """`lsq_adaptive_avg_pool2d_w8_q` without an output quantizer: floats out."""
+    _assert_has_ops()
+    x = _pool_levels("lsq_adaptive_avg_pool2d_w8", x)
+    kernel = _E.pool_w8_adaptive_kernel(x.shape[2], x.shape[3], output_size)
+    return lsq_avg_pool2d_w8(x, kernel, kernel, 0, False, True, None, out_dtype)

@@ -16,6 +16,7 @@ from .modules.linear_w8a8 import LinearW8A8, convert_w8a8  # noqa: F401
 from .modules.conv_w8a8 import Conv2dW8A8  # noqa: F401
 from .modules.w8a8_q import Conv2dW8A8Q, LinearW8A8Q, convert_w8a8_q  # noqa: F401
 from .modules.w8a8_add_q import AddW8A8Q, Conv2dW8A8AddQ, LinearW8A8AddQ, convert_w8a8_add_q  # noqa: F401
+from .modules.pool_w8 import AdaptiveAvgPool2dW8Q, AvgPool2dW8Q, MaxPool2dW8, convert_w8a8_pool  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
@@ -115,4 +116,5 @@ def prepare_ddp(model, process_group=None, grads="mean"):
 __all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "PackedLinearA8", "LinearW8A8", "Conv2dW8A8", "convert_packed", "convert_packed_a8",
            "convert_w8a8", "LinearW8A8Q", "Conv2dW8A8Q", "convert_w8a8_q",
            "LinearW8A8AddQ", "Conv2dW8A8AddQ", "AddW8A8Q", "convert_w8a8_add_q",
+           "MaxPool2dW8", "AvgPool2dW8Q", "AdaptiveAvgPool2dW8Q", "convert_w8a8_pool",
            "enable_rank_sync", "prepare_ddp"] + [row[0] for row in _TABLE]
