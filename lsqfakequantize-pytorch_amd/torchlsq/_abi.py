@@ -2,7 +2,7 @@
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
 ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes),
 the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so, their form with an 8-bit output
-liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so, pooling on levels liblsq_hip_pool_w8.so (ctypes)
+liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so, pooling on levels liblsq_hip_pool_w8.so, the depthwise conv2d liblsq_hip_dwconv_w8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -458,6 +458,31 @@ _POOL_W8_LIB, pool_w8_error_str = _load_companion("liblsq_hip_pool_w8.so", C_ABI
 def pool_w8_library():
     """The ctypes handle of liblsq_hip_pool_w8.so (raises if it is missing)."""
     return _require_companion(_POOL_W8_LIB, "pool_w8", "the pooling ops on 8-bit levels need", pool_w8_error_str)
+
+
+# W8A8 depthwise conv2d (groups == C) on channels-last 8-bit levels, levels or floats out (include/lsq_hip_dwconv_w8.h): a
+# thirteenth companion library; the ABIs above stay as they are.
+class LsqDwconvW8Out(ctypes.Structure):
+    """lsq_dwconv_w8_out (include/lsq_hip_dwconv_w8.h): the output quantizer (or none: floats), the activation and mid_dtype"""
+    _fields_ = [("out_scale", ctypes.c_void_p), ("out_shift", ctypes.c_void_p)] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "act", "mid_dtype")]
+
+
+DWCONV_W8_ABI_VERSION = 1
+_DOP = ctypes.POINTER(LsqDwconvW8Out)
+C_ABI_DWCONV_W8 = {
+    "lsq_dwconv_w8_abi_version": (_int, []),
+    "lsq_dwconv_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_dwconv_w8_forward_levels": (_int, [_int, _vp, _vp, _vp, _CGP, _int, _vp, _vp, _vp, _vp, _int, _DOP, _vp, _vp]),
+    "lsq_dwconv_w8_plan": (_int, [_CGP, _int, _int, _PLAN8]),
+}
+_DWCONV_W8_LIB, dwconv_w8_error_str = _load_companion("liblsq_hip_dwconv_w8.so", C_ABI_DWCONV_W8, "lsq_dwconv_w8_abi_version",
+                                                        DWCONV_W8_ABI_VERSION)
+
+
+def dwconv_w8_library():
+    """The ctypes handle of liblsq_hip_dwconv_w8.so (raises if it is missing)."""
+    return _require_companion(_DWCONV_W8_LIB, "dwconv_w8", "the W8A8 depthwise conv2d ops need", dwconv_w8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

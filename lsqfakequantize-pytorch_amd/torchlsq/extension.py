@@ -46,12 +46,13 @@ from ._requant_w8_host import (requant_w8_conv, requant_w8_conv_levels, requant_
 from ._resadd_w8_host import resadd_w8_conv_levels, resadd_w8_linear_levels, resadd_w8_plan_conv, resadd_w8_plan_linear  # noqa: F401
 from ._pool_w8_host import (pool_w8_adaptive_kernel, pool_w8_avg, pool_w8_avg_q, pool_w8_max, pool_w8_plan_avg,  # noqa: F401
                             pool_w8_plan_max)
+from ._dwconv_w8_host import dwconv_w8_levels, dwconv_w8_levels_q, dwconv_w8_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -176,6 +177,16 @@ _AVG_POOL = ("Tensor levels, Tensor x_scale, Tensor x_zero, int[2] kernel_size, 
 _lib_def.define("lsq_avg_pool2d_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
                 "int out_type_max, ScalarType mid_dtype) -> Tensor" % _AVG_POOL)
 _lib_def.define("lsq_avg_pool2d_q8(%s, ScalarType out_dtype) -> Tensor" % _AVG_POOL)
+#  * W8A8 DEPTHWISE conv2d (groups == C, channel multiplier 1) on 8-bit LEVELS [B, C, H, W], read channels-last, and weight LEVELS
+#    given TAP-MAJOR, [kh, kw, C], with one scale (float32) and zero point (int32) per channel (liblsq_hip_dwconv_w8.so,
+#    include/lsq_hip_dwconv_w8.h): the exact integer sum over the taps of one channel, the fp32 steps of the W8A8 ops, a rounding
+#    to `mid_dtype`, act (0 none, 1 ReLU, 2 ReLU6) and the levels of the output quantizer (_q) or the floats themselves.  The
+#    results are [B, C, OH, OW] in channels-last memory.  Inference only.
+_DWCONV = ("Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, Tensor? bias, int[2] stride, "
+           "int[2] padding, int[2] dilation")
+_lib_def.define("lsq_dwconv2d_w8_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
+                "int out_type_max, int act, ScalarType mid_dtype) -> Tensor" % _DWCONV)
+_lib_def.define("lsq_dwconv2d_w8_q8(%s, int act, ScalarType out_dtype) -> Tensor" % _DWCONV)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -776,6 +787,39 @@ def _fake_avg_pool2d_q8(levels, x_scale, x_zero, kernel_size, stride, padding, c
 _lib_def.impl("lsq_max_pool2d_q8", _requant_no_grad("lsq_max_pool2d_q8", ()), "Autograd")
 _lib_def.impl("lsq_avg_pool2d_q8_q", _requant_no_grad("lsq_avg_pool2d_q8_q", (1, 9, 10)), "Autograd")
 _lib_def.impl("lsq_avg_pool2d_q8", _requant_no_grad("lsq_avg_pool2d_q8", (1,)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the W8A8 depthwise conv2d on 8-bit levels (_dwconv_w8_host.py): GPU tensors -> liblsq_hip_dwconv_w8.so (one call), CPU tensors
+# -> the definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_dwconv2d_w8_q8_q", dwconv_w8_levels_q)
+    _lib_key.impl("lsq_dwconv2d_w8_q8", dwconv_w8_levels)
+del _lib_key
+
+
+def _fake_dwconv_w8(x_levels, w_levels, stride, padding, dilation, dtype):
+    B, C, H, W = x_levels.shape
+    kh, kw = w_levels.shape[:2]
+    OH = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
+    OW = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
+    return torch.empty((B, C, OH, OW), dtype=dtype, device=x_levels.device, memory_format=torch.channels_last)
+
+
+@torch.library.register_fake("torchlsq::lsq_dwconv2d_w8_q8_q", lib=_lib_def)
+def _fake_dwconv2d_w8_q8_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation, out_scale, out_shift,
+                           out_quant_min, out_quant_max, out_type_min, out_type_max, act, mid_dtype):
+    return _fake_dwconv_w8(x_levels, w_levels, stride, padding, dilation, _fake_level_dtype(out_quant_max, out_type_max))
+
+
+@torch.library.register_fake("torchlsq::lsq_dwconv2d_w8_q8", lib=_lib_def)
+def _fake_dwconv2d_w8_q8(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, padding, dilation, act, out_dtype):
+    return _fake_dwconv_w8(x_levels, w_levels, stride, padding, dilation, out_dtype)
+
+
+_lib_def.impl("lsq_dwconv2d_w8_q8_q", _requant_no_grad("lsq_dwconv2d_w8_q8_q", (1, 4, 6, 10, 11)), "Autograd")
+_lib_def.impl("lsq_dwconv2d_w8_q8", _requant_no_grad("lsq_dwconv2d_w8_q8", (1, 4, 6)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

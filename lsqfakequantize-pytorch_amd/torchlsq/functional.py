@@ -1066,3 +1066,87 @@ def lsq_adaptive_avg_pool2d_w8(x: LevelsTensor, output_size, out_dtype=torch.flo
     x = _pool_levels("lsq_adaptive_avg_pool2d_w8", x)
     kernel = _E.pool_w8_adaptive_kernel(x.shape[2], x.shape[3], output_size)
     return lsq_avg_pool2d_w8(x, kernel, kernel, 0, False, True, None, out_dtype)
+
+
+_DW_ACTS = {None: 0, "none": 0, "relu": 1, "relu6": 2, False: 0, True: 1, 0: 0, 1: 1, 2: 2}
+
+
+def dw_weight_operands(weight_q: Tensor):
+    """(levels [kh, kw, C] int8 / uint8, TAP-MAJOR, scale [C] float32, zero point [C] int32) of the 4-D [C, 1, kh, kw] per-channel
+    (axis 0) or per-tensor `torch.qint8` / `torch.quint8` weight of a depthwise convolution, e.g. `LSQFakeQuantizer.quantize(w)`:
+    what `lsq_dwconv2d_w8_q8` / `_q` take.  The permutation is one small copy; nothing is read back from the device."""
+    assert weight_q.is_quantized and weight_q.dtype in (torch.qint8, torch.quint8) and weight_q.dim() == 4 and weight_q.shape[1] == 1, \
+        "lsq_depthwise_conv2d_w8a8 needs a 4-D torch.qint8 / torch.quint8 weight [channels, 1, kh, kw] (a channel multiplier is not served)"
+    levels, scale, zero = w8_weight_operands(weight_q)
+    return levels[:, 0].permute(1, 2, 0).contiguous(), scale, zero
+
+
+def _dw_input(what, x, scale, shift, quant_min, quant_max, type_min, type_max):
+    """x as a LevelsTensor: as it is, from a per-tensor quantized tensor, or from a floating x through `lsq_levels_per_tensor`
+    with the input quantizer's constants formed on the device"""
+    if isinstance(x, LevelsTensor):
+        return x
+    if x.is_quantized:
+        return LevelsTensor.from_quantized(x)
+    assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
+        "%s on a floating x needs the input quantizer's scale, shift, quant_min and quant_max" % what
+    type_min = quant_min if type_min is None else type_min
+    type_max = quant_max if type_max is None else type_max
+    rng = (int(quant_min), int(quant_max), int(type_min), int(type_max))
+    sc, sh = scale.detach().reshape(-1)[:1].to(torch.float32), shift.detach().reshape(-1)[:1].to(torch.float32)
+    lv = torch.ops.torchlsq.lsq_levels_per_tensor(x.detach(), sc, sh, *rng, 0)
+    s_x, zx = _act_constants(sc, sh, rng[2], rng[3])
+    return LevelsTensor(lv.view(torch.uint8) if max(rng[1], rng[3]) > 127 else lv, s_x, zx, *rng)
+
+
+def _dw_args(what, weight_q, bias, stride, padding, dilation, act):
+    assert act in _DW_ACTS, "%s: act must be 'none', 'relu' or 'relu6', got %r" % (what, act)
+    wl, ws, wz = dw_weight_operands(weight_q)
+    stride, dilation = _two(stride, "stride"), _two(dilation, "dilation")
+    padding = _conv_padding(padding, wl.shape[:2], stride, dilation)
+    return (wl, ws, wz, bias, list(stride), list(padding), list(dilation)), _DW_ACTS[act]
+
+
+def lsq_depthwise_conv2d_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, stride=1, padding=0, dilation=1, scale: Tensor = None,
+                                shift: Tensor = None, quant_min: int = None, quant_max: int = None, type_min: int = None,
+                                type_max: int = None, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                                out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None, act="none",
+                                mid_dtype=None) -> LevelsTensor:
+    """A DEPTHWISE 2-D convolution (`F.conv2d` with `groups == in_channels == out_channels`) on 8-bit activations and an 8-bit
+    weight with an 8-bit output: per channel c the exact integer `I = sum over the taps inside x of (lx - zx) * (lw[c] - zw[c])`
+    (a tap in the zero padding contributes 0), `v = ((s_w[c] * float(I)) * s_x) + bias[c]` in fp32, `u = round_to(mid_dtype, v)`,
+    `act` ('none', 'relu' or 'relu6'; selects, a NaN stays a NaN) and the levels of the per-tensor output quantizer
+    (`out_scale`, `out_shift`, `out_quant_min`, `out_quant_max`, type range) -- one launch, one byte read and one written per
+    activation (liblsq_hip_dwconv_w8.so); the GPU result equals the CPU result (one int64 grouped `F.conv2d`) bit for bit.
+
+    `weight_q` is the [C, 1, kh, kw] per-channel (axis 0) or per-tensor `torch.qint8` / `torch.quint8` weight that
+    `LSQFakeQuantizer.quantize(conv.weight)` returns.  The kernel reads it tap-major, [kh, kw, C]: THIS FUNCTION PERMUTES IT ON
+    EVERY CALL (one small copy); `torchlsq.quantized.DepthwiseConv2dW8A8Q` stores it that way once, at conversion.
+    x is a `LevelsTensor` (its device constants are used), a per-tensor `torch.quint8` / `torch.qint8` tensor, or a floating
+    [B, C, H, W] tensor with the INPUT quantizer's `scale`, `shift`, `quant_min`, `quant_max`, which goes through
+    `lsq_levels_per_tensor` first (`mid_dtype` then defaults to x's dtype, else to float32).  Nothing is read back to the host.
+    Returns a `LevelsTensor` in channels-last memory.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_depthwise_conv2d_w8a8_q"
+    w, a = _dw_args(what, weight_q, bias, stride, padding, dilation, act)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    if mid_dtype is None:
+        mid_dtype = x.dtype if isinstance(x, Tensor) and not x.is_quantized else torch.float32
+    x = _dw_input(what, x, scale, shift, quant_min, quant_max, type_min, type_max)
+    lv = torch.ops.torchlsq.lsq_dwconv2d_w8_q8_q(x.levels, x.scale, x.zero_point, *w, *o[:6], a, mid_dtype)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_depthwise_conv2d_w8a8(x, weight_q: Tensor, bias: Tensor = None, stride=1, padding=0, dilation=1, scale: Tensor = None,
+                              shift: Tensor = None, quant_min: int = None, quant_max: int = None, type_min: int = None,
+                              type_max: int = None, act="none", out_dtype=None) -> Tensor:
+    """`lsq_depthwise_conv2d_w8a8_q` without an output quantizer: the activated values as `out_dtype` floats (default: a floating
+    x's dtype, else float32), [B, C, OH, OW] in channels-last memory.  The weight is permuted on every call, as there.
+    Inference only."""
+    _assert_has_ops()
+    what = "lsq_depthwise_conv2d_w8a8"
+    w, a = _dw_args(what, weight_q, bias, stride, padding, dilation, act)
+    if out_dtype is None:
+        out_dtype = x.dtype if isinstance(x, Tensor) and not x.is_quantized else torch.float32
+    x = _dw_input(what, x, scale, shift, quant_min, quant_max, type_min, type_max)
+    return torch.ops.torchlsq.lsq_dwconv2d_w8_q8(x.levels, x.scale, x.zero_point, *w, a, out_dtype)
