@@ -2,7 +2,7 @@
 (include/lsq_cpu.h, ctypes), liblsq_hip_group.so (include/lsq_hip_group.h, ctypes), liblsq_hip_pack.so (include/lsq_hip_pack.h,
 ctypes), the linear layers on packed weights liblsq_hip_qlinear.so, liblsq_hip_qlinear_a8.so, liblsq_hip_qgemm.so and liblsq_hip_qgemm_a8.so (ctypes),
 the W8A8 layers on 8-bit levels liblsq_hip_qlinear_w8.so and liblsq_hip_qconv_w8.so, their form with an 8-bit output
-liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so, pooling on levels liblsq_hip_pool_w8.so, the depthwise conv2d liblsq_hip_dwconv_w8.so (ctypes)
+liblsq_hip_requant_w8.so and that form with a levels residual liblsq_hip_resadd_w8.so, pooling on levels liblsq_hip_pool_w8.so, the depthwise conv2d liblsq_hip_dwconv_w8.so, the byte table op and the gate multiply liblsq_hip_eltwise_w8.so (ctypes)
 and _lsq_torch.so (the C++ torch binding of the same C ABI, torch.ops.load_library).
 
 This is the replacement of reference torchlsq/extension.py:12-56, which located `_C.so` and `torch.ops.load_library`-ed it.
@@ -483,6 +483,38 @@ _DWCONV_W8_LIB, dwconv_w8_error_str = _load_companion("liblsq_hip_dwconv_w8.so",
 def dwconv_w8_library():
     """The ctypes handle of liblsq_hip_dwconv_w8.so (raises if it is missing)."""
     return _require_companion(_DWCONV_W8_LIB, "dwconv_w8", "the W8A8 depthwise conv2d ops need", dwconv_w8_error_str)
+
+
+# Elementwise ops on 8-bit levels: a 256-entry byte table and the SE gate multiply (include/lsq_hip_eltwise_w8.h): a fourteenth
+# companion library; the ABIs above stay as they are.
+class LsqEltwiseW8Shape(ctypes.Structure):
+    """lsq_eltwise_w8_shape (include/lsq_hip_eltwise_w8.h): x and y [B, H, W, C], the gate [B, C]"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "C", "H", "W")]
+
+
+class LsqEltwiseW8Mul(ctypes.Structure):
+    """lsq_eltwise_w8_mul (include/lsq_hip_eltwise_w8.h): the gate multiply's device constants, output quantizer (or none) and mid_dtype"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_x", "zx", "s_g", "zg", "out_scale", "out_shift")] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "mid_dtype")]
+
+
+ELTWISE_W8_ABI_VERSION = 1
+_ESP = ctypes.POINTER(LsqEltwiseW8Shape)
+C_ABI_ELTWISE_W8 = {
+    "lsq_eltwise_w8_abi_version": (_int, []),
+    "lsq_eltwise_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_eltwise_w8_lut": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "lsq_eltwise_w8_mul_gate": (_int, [_int, _vp, _int, _vp, _ESP, ctypes.POINTER(LsqEltwiseW8Mul), _vp, _vp]),
+    "lsq_eltwise_w8_plan_lut": (_int, [_i64, _int, _PLAN8]),
+    "lsq_eltwise_w8_plan_mul": (_int, [_ESP, _int, _PLAN8]),
+}
+_ELTWISE_W8_LIB, eltwise_w8_error_str = _load_companion("liblsq_hip_eltwise_w8.so", C_ABI_ELTWISE_W8, "lsq_eltwise_w8_abi_version",
+                                                          ELTWISE_W8_ABI_VERSION)
+
+
+def eltwise_w8_library():
+    """The ctypes handle of liblsq_hip_eltwise_w8.so (raises if it is missing)."""
+    return _require_companion(_ELTWISE_W8_LIB, "eltwise_w8", "the table op and the gate multiply on 8-bit levels need", eltwise_w8_error_str)
 
 
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI

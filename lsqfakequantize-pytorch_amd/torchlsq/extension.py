@@ -47,12 +47,14 @@ from ._resadd_w8_host import resadd_w8_conv_levels, resadd_w8_linear_levels, res
 from ._pool_w8_host import (pool_w8_adaptive_kernel, pool_w8_avg, pool_w8_avg_q, pool_w8_max, pool_w8_plan_avg,  # noqa: F401
                             pool_w8_plan_max)
 from ._dwconv_w8_host import dwconv_w8_levels, dwconv_w8_levels_q, dwconv_w8_plan  # noqa: F401
+from ._eltwise_w8_host import (eltwise_w8_lut, eltwise_w8_mul_gate, eltwise_w8_mul_gate_q, eltwise_w8_plan_lut,  # noqa: F401
+                               eltwise_w8_plan_mul)
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -187,6 +189,17 @@ _DWCONV = ("Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_sc
 _lib_def.define("lsq_dwconv2d_w8_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
                 "int out_type_max, int act, ScalarType mid_dtype) -> Tensor" % _DWCONV)
 _lib_def.define("lsq_dwconv2d_w8_q8(%s, int act, ScalarType out_dtype) -> Tensor" % _DWCONV)
+#  * elementwise ops on 8-bit LEVELS (liblsq_hip_eltwise_w8.so, include/lsq_hip_eltwise_w8.h).  The TABLE op: y = table[x], the
+#    index being the byte as stored (an int8 level l reads entry l & 0xff), in x's shape and memory layout, as `out_dtype` (uint8 /
+#    int8: the same bytes); a 256-entry table holds any elementwise function between two per-tensor 8-bit quantizers
+#    (`torchlsq.functional.lsq_act_table` builds it from existing ops).  The GATE MULTIPLY: x levels [B, C, H, W] (read
+#    channels-last) or [B, C] times gate levels [B, C] or [B, C, 1, 1], each dequantized to `mid_dtype`, one rounded product, and
+#    the levels of the output quantizer (_q) or the floats themselves.  Inference only.
+_lib_def.define("lsq_lut_w8(Tensor x_levels, Tensor table, ScalarType out_dtype) -> Tensor")
+_MUL_GATE = "Tensor x_levels, Tensor x_scale, Tensor x_zero, Tensor g_levels, Tensor g_scale, Tensor g_zero"
+_lib_def.define("lsq_mul_gate_w8_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
+                "int out_type_max, ScalarType mid_dtype) -> Tensor" % _MUL_GATE)
+_lib_def.define("lsq_mul_gate_w8_q8(%s, ScalarType out_dtype) -> Tensor" % _MUL_GATE)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -820,6 +833,43 @@ def _fake_dwconv2d_w8_q8(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, str
 
 _lib_def.impl("lsq_dwconv2d_w8_q8_q", _requant_no_grad("lsq_dwconv2d_w8_q8_q", (1, 4, 6, 10, 11)), "Autograd")
 _lib_def.impl("lsq_dwconv2d_w8_q8", _requant_no_grad("lsq_dwconv2d_w8_q8", (1, 4, 6)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the table op and the gate multiply on 8-bit levels (_eltwise_w8_host.py): GPU tensors -> liblsq_hip_eltwise_w8.so (one call), CPU
+# tensors -> the definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_lut_w8", eltwise_w8_lut)
+    _lib_key.impl("lsq_mul_gate_w8_q8_q", eltwise_w8_mul_gate_q)
+    _lib_key.impl("lsq_mul_gate_w8_q8", eltwise_w8_mul_gate)
+del _lib_key
+
+
+def _fake_like_levels(x_levels, dtype):
+    fmt = torch.channels_last if x_levels.dim() == 4 else torch.contiguous_format
+    return torch.empty(x_levels.shape, dtype=dtype, device=x_levels.device, memory_format=fmt)
+
+
+@torch.library.register_fake("torchlsq::lsq_lut_w8", lib=_lib_def)
+def _fake_lut_w8(x_levels, table, out_dtype):
+    return torch.empty_like(x_levels, dtype=out_dtype)
+
+
+@torch.library.register_fake("torchlsq::lsq_mul_gate_w8_q8_q", lib=_lib_def)
+def _fake_mul_gate_w8_q8_q(x_levels, x_scale, x_zero, g_levels, g_scale, g_zero, out_scale, out_shift, out_quant_min, out_quant_max,
+                           out_type_min, out_type_max, mid_dtype):
+    return _fake_like_levels(x_levels, _fake_level_dtype(out_quant_max, out_type_max))
+
+
+@torch.library.register_fake("torchlsq::lsq_mul_gate_w8_q8", lib=_lib_def)
+def _fake_mul_gate_w8_q8(x_levels, x_scale, x_zero, g_levels, g_scale, g_zero, out_dtype):
+    return _fake_like_levels(x_levels, out_dtype)
+
+
+_lib_def.impl("lsq_lut_w8", _requant_no_grad("lsq_lut_w8", ()), "Autograd")
+_lib_def.impl("lsq_mul_gate_w8_q8_q", _requant_no_grad("lsq_mul_gate_w8_q8_q", (1, 4, 6, 7)), "Autograd")
+_lib_def.impl("lsq_mul_gate_w8_q8", _requant_no_grad("lsq_mul_gate_w8_q8", (1, 4)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

@@ -1150,3 +1150,131 @@ def lsq_depthwise_conv2d_w8a8(x, weight_q: Tensor, bias: Tensor = None, stride=1
         out_dtype = x.dtype if isinstance(x, Tensor) and not x.is_quantized else torch.float32
     x = _dw_input(what, x, scale, shift, quant_min, quant_max, type_min, type_max)
     return torch.ops.torchlsq.lsq_dwconv2d_w8_q8(x.levels, x.scale, x.zero_point, *w, a, out_dtype)
+
+
+# -------------------------------------------------------------------------------------------------
+# elementwise ops on 8-bit levels: activation functions as a 256-entry byte table, and the squeeze-and-excitation multiply
+# -------------------------------------------------------------------------------------------------
+def _named_acts():
+    F = torch.nn.functional
+    return {"identity": None, "relu": F.relu, "relu6": F.relu6, "hardtanh": F.hardtanh, "leaky_relu": F.leaky_relu,
+            "hardswish": F.hardswish, "hardsigmoid": F.hardsigmoid, "silu": F.silu, "gelu": F.gelu,
+            "gelu_tanh": lambda v: F.gelu(v, approximate="tanh"), "sigmoid": torch.sigmoid, "tanh": torch.tanh}
+
+
+def act_function(fn):
+    """(callable or None, name) of an activation given as None (the identity), one of the names "identity", "relu", "relu6",
+    "hardtanh", "leaky_relu", "hardswish", "hardsigmoid", "silu", "gelu", "gelu_tanh", "sigmoid", "tanh", the `torch.nn` module
+    of one of them (its parameters -- a Hardtanh's bounds, a LeakyReLU's slope, a GELU's `approximate` -- are kept), or any
+    other callable, which is taken as it is"""
+    nn, F = torch.nn, torch.nn.functional
+    if fn is None:
+        return None, "identity"
+    if isinstance(fn, str):
+        named = _named_acts()
+        assert fn in named, "unknown activation %r: one of %s, an nn module of one of them, or a callable" % (fn, sorted(named))
+        return named[fn], fn
+    if isinstance(fn, nn.Hardtanh) and not isinstance(fn, nn.ReLU6):
+        lo, hi = float(fn.min_val), float(fn.max_val)
+        return (lambda v: F.hardtanh(v, lo, hi)), "hardtanh(%g, %g)" % (lo, hi)
+    if isinstance(fn, nn.LeakyReLU):
+        slope = float(fn.negative_slope)
+        return (lambda v: F.leaky_relu(v, slope)), "leaky_relu(%g)" % slope
+    if isinstance(fn, nn.GELU):
+        return act_function("gelu_tanh" if fn.approximate == "tanh" else "gelu")
+    for cls, name in ((nn.Identity, "identity"), (nn.ReLU6, "relu6"), (nn.ReLU, "relu"), (nn.Hardswish, "hardswish"),
+                      (nn.Hardsigmoid, "hardsigmoid"), (nn.SiLU, "silu"), (nn.Sigmoid, "sigmoid"), (nn.Tanh, "tanh")):
+        if isinstance(fn, cls):
+            return act_function(name)
+    assert callable(fn), "an activation is a name, a torch.nn activation module or a callable, got %s" % type(fn).__name__
+    return fn, getattr(fn, "__name__", type(fn).__name__)
+
+
+def lsq_act_table(fn, in_scale: Tensor, in_zero_point: Tensor, in_dtype, out_scale: Tensor, out_shift: Tensor, out_quant_min: int,
+                  out_quant_max: int, out_type_min: int = None, out_type_max: int = None, mid_dtype=torch.float32) -> Tensor:
+    """The 256-entry byte table (uint8 [256], on `in_scale`'s device) of an elementwise function between two per-tensor 8-bit
+    quantizers, built from existing ops alone -- no new kernel, nothing read back:
+
+        b  = arange(256, uint8) viewed as `in_dtype` (uint8 / int8): every byte an input level can be stored as
+        u  = LevelsTensor(b, in_scale, in_zero_point).dequantize(mid_dtype)
+        v  = fn(u)                        a torch callable, same shape, must return `mid_dtype`; None: the identity
+        table = lsq_levels_per_tensor(v, out_scale, out_shift, out range, 0) as bytes
+
+    so `table[levels]` (`lsq_lut_w8`) equals the unfused chain dequantize -> fn -> the next quantizer on the same device, bit for
+    bit, for any `fn` (`act_function` lists the names and modules).  The entries of bytes outside the input's
+    quant_min..quant_max are filled the same way and never read.  With `fn=None` the table REQUANTIZES from one per-tensor
+    quantizer to another, which is what the branches of a concatenation need before they can share one.  The clamp-type
+    functions (identity, relu, relu6, hardtanh) give the same table on the CPU and on the GPU; for the transcendental ones ATen's
+    CPU and GPU kernels may round differently, so build the table on the device whose unfused chain it has to equal."""
+    _assert_has_ops()
+    assert in_dtype in (torch.uint8, torch.int8), "lsq_act_table: in_dtype must be torch.uint8 or torch.int8"
+    call, _ = act_function(fn)
+    o = _out_args("lsq_act_table", out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    b = torch.arange(256, dtype=torch.uint8, device=in_scale.device).view(in_dtype)
+    lo, hi = (0, 255) if in_dtype == torch.uint8 else (-128, 127)
+    u = LevelsTensor(b, in_scale.detach(), in_zero_point, lo, hi).dequantize(mid_dtype)
+    v = u if call is None else call(u)
+    assert isinstance(v, Tensor) and v.shape == u.shape and v.dtype == mid_dtype, \
+        "lsq_act_table: the function must return a %s tensor of its input's shape" % str(mid_dtype).replace("torch.", "")
+    return torch.ops.torchlsq.lsq_levels_per_tensor(v, *o[:6], 0).view(torch.uint8)
+
+
+def _levels_in(what, x):
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    assert isinstance(x, LevelsTensor), "%s needs a LevelsTensor (or a per-tensor quantized tensor)" % what
+    return x
+
+
+def lsq_lut_w8(x: LevelsTensor, table: Tensor, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+               out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None) -> LevelsTensor:
+    """`table[x.levels]` in one launch (liblsq_hip_eltwise_w8.so): one byte read and one written per activation, in x's shape
+    and memory layout.  `table` is `lsq_act_table`'s for x's quantizer and the output quantizer given here, whose constants the
+    returned `LevelsTensor` carries (formed on the device).  Inference only."""
+    _assert_has_ops()
+    x = _levels_in("lsq_lut_w8", x)
+    o = _out_args("lsq_lut_w8", out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    lv = torch.ops.torchlsq.lsq_lut_w8(x.levels, table, torch.uint8 if max(o[3], o[5]) > 127 else torch.int8)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_act_w8_q(x: LevelsTensor, fn, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                 out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None, mid_dtype=torch.float32) -> LevelsTensor:
+    """An activation function on 8-bit levels with an 8-bit output: bit for bit `lsq_levels_per_tensor(fn(x.dequantize(mid_dtype)),
+    output quantizer)` on x's device.  THIS FUNCTION BUILDS THE TABLE ON EVERY CALL (`lsq_act_table`: a handful of launches on 256
+    elements) before the one launch of `lsq_lut_w8`; `torchlsq.quantized.ActivationW8Q` builds it once, at conversion.  `fn` as in
+    `act_function`.  Inference only."""
+    x = _levels_in("lsq_act_w8_q", x)
+    table = lsq_act_table(fn, x.scale, x.zero_point, x.levels.dtype, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
+                          out_type_max, mid_dtype)
+    return lsq_lut_w8(x, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max)
+
+
+def _gate_operands(what, x, gate):
+    x, gate = _levels_in(what, x), _levels_in(what, gate)
+    assert x.levels.dim() in (2, 4) and tuple(gate.levels.shape) in (tuple(x.shape[:2]), tuple(x.shape[:2]) + (1, 1)), \
+        "%s needs x of [B, C, H, W] or [B, C] and a gate of [B, C] or [B, C, 1, 1], got %s and %s" % (what, tuple(x.shape), tuple(gate.shape))
+    return x.levels, x.scale, x.zero_point, gate.levels, gate.scale, gate.zero_point
+
+
+def lsq_mul_gate_w8_q(x: LevelsTensor, gate: LevelsTensor, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                      out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                      mid_dtype=torch.float32) -> LevelsTensor:
+    """The squeeze-and-excitation multiply on 8-bit levels with an 8-bit output: x [B, C, H, W] (or [B, C]) times a gate of
+    [B, C] or [B, C, 1, 1], both `LevelsTensor`s of quantizers and level dtypes of their own.  Bit for bit
+    `lsq_levels_per_tensor(x.dequantize(mid_dtype) * gate.dequantize(mid_dtype)[:, :, None, None], output quantizer)`: each operand
+    rounded to `mid_dtype`, one rounded product, the output quantizer's levels -- one launch (liblsq_hip_eltwise_w8.so), one byte
+    read and one written per activation, nothing read back.  Returns a `LevelsTensor` in x's shape (4-D: channels-last memory).
+    Inference only."""
+    _assert_has_ops()
+    what = "lsq_mul_gate_w8_q"
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    lv = torch.ops.torchlsq.lsq_mul_gate_w8_q8_q(*_gate_operands(what, x, gate), *o[:6], mid_dtype)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_mul_gate_w8(x: LevelsTensor, gate: LevelsTensor, out_dtype=torch.float32) -> Tensor:
+    """`lsq_mul_gate_w8_q` without an output quantizer: the products `round_to(out_dtype, a * g)` as a floating tensor in x's
+    shape.  Inference only."""
+    _assert_has_ops()
+    return torch.ops.torchlsq.lsq_mul_gate_w8_q8(*_gate_operands("lsq_mul_gate_w8", x, gate), out_dtype)

@@ -18,6 +18,7 @@ from .modules.w8a8_q import Conv2dW8A8Q, LinearW8A8Q, convert_w8a8_q  # noqa: F4
 from .modules.w8a8_add_q import AddW8A8Q, Conv2dW8A8AddQ, LinearW8A8AddQ, convert_w8a8_add_q  # noqa: F401
 from .modules.pool_w8 import AdaptiveAvgPool2dW8Q, AvgPool2dW8Q, MaxPool2dW8, convert_w8a8_pool  # noqa: F401
 from .modules.dwconv_w8a8 import DepthwiseConv2dW8A8Q, convert_w8a8_depthwise  # noqa: F401
+from .modules.eltwise_w8 import ActivationW8Q, MulGateW8Q, convert_w8a8_eltwise  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
