@@ -22,73 +22,9 @@
 //    butterfly over the wave.  Correct for every legal input; not tuned.
 //  * The fused entry form runs the linear's flat pre-pass (w8_levels_body) over the B H W Cin elements of channels-last x.
 #include "lsq_qconv_w8_tiles.hpp"
-#include "../../../include/lsq_hip_qconv_w8.h"
+#include "lsq_w8_host_checks.hpp"
 
 namespace lsq {
-
-struct W8ConvGeom {         // kernel argument; the host has checked that the coordinates fit 32 bits
-    int64_t Cin, OH, OW, image;     // image = H W Cin, the bytes of one image of x
-    int H, W, kw, sh, sw, ph, pw, dh, dw;
-};
-
-struct W8ConvRow {          // output pixel m = (b, oh, ow): where its receptive field starts
-    int64_t base;           // b * image
-    int ih0, iw0;           // oh sh - ph, ow sw - pw
-};
-
-__device__ __forceinline__ W8ConvRow w8_conv_row(int64_t m, int64_t OH, int64_t OW, int64_t image, int sh, int sw, int ph, int pw) {
-    const int64_t t = m / OW, ow = m - t * OW;
-    const int64_t b = t / OH, oh = t - b * OH;
-    W8ConvRow r;
-    r.base = b * image;
-    r.ih0 = static_cast<int>(oh * sh - ph);
-    r.iw0 = static_cast<int>(ow * sw - pw);
-    return r;
-}
-
-// the implicit [B OH OW, kh kw Cin] matrix of byte operands, Cin % 16 == 0 and K <= 65536 (scalars only: a nested W8ConvGeom
-// sends the struct through scratch memory)
-struct W8ConvSrc {
-    const uint8_t* a;
-    uint32_t flip;          // of a loaded packet
-    uint32_t pad;           // four times the byte zx - off: a tap in the padding
-    int64_t OH, OW, image;
-    unsigned H, W, Cin, kw, dh, dw;
-    int sh, sw, ph, pw;
-    typedef W8ConvRow Row;
-    struct Col {            // k = (i kw + j) Cin + c
-        unsigned idh, jdw;  // i dh, j dw
-        unsigned j, c;
-    };
-    __device__ __forceinline__ Row row(int64_t m) const { return w8_conv_row(m, OH, OW, image, sh, sw, ph, pw); }
-    __device__ __forceinline__ Col col(int64_t k) const {
-        const unsigned kk = static_cast<unsigned>(k);
-        const unsigned tap = kk / Cin, i = tap / kw, j = tap - i * kw;
-        return Col{i * dh, j * dw, j, kk - tap * Cin};
-    }
-    __device__ __forceinline__ void advance(Col& p) const {     // 16 bytes further: Cin % 16 == 0, so c reaches Cin exactly
-        p.c += 16u;
-        if (p.c >= Cin) {
-            p.c = 0u;
-            p.j += 1u;
-            p.jdw += dw;
-            if (p.j == kw) {
-                p.j = 0u;
-                p.jdw = 0u;
-                p.idh += dh;
-            }
-        }
-    }
-    __device__ __forceinline__ u32x4 packet(const Row& r, const Col& p) const {
-        const unsigned ih = static_cast<unsigned>(r.ih0) + p.idh, iw = static_cast<unsigned>(r.iw0) + p.jdw;   // negative: huge
-        u32x4 v = {pad, pad, pad, pad};
-        if (ih < H && iw < W) {
-            const int64_t at = r.base + (static_cast<int64_t>(ih) * W + iw) * Cin + p.c;
-            v = *reinterpret_cast<const u32x4*>(a + at) ^ flip;
-        }
-        return v;
-    }
-};
 
 // ------------------------------------------------------------------------------------------------
 // matrix-core form: lsq_qconv_w8_tiles.hpp's body on the implicit matrix
@@ -97,11 +33,7 @@ template <int SUBS, bool SPLITK>
 __global__ __launch_bounds__(kW8TileWaves * 64, 2) void qconv_w8_tiles_kernel(W8Act act, W8Weight wt, W8Geom geo, W8ConvGeom cg,
                                                                              void* __restrict__ y, int y_dtype) {
     const W8Const ac = w8_constants(act);
-    const uint32_t pad = static_cast<uint32_t>(ac.z & 0xff) * 0x01010101u;
-    const W8ConvSrc src{act.a, ac.flip, pad, cg.OH, cg.OW, cg.image, static_cast<unsigned>(cg.H), static_cast<unsigned>(cg.W),
-                        static_cast<unsigned>(cg.Cin), static_cast<unsigned>(cg.kw), static_cast<unsigned>(cg.dh),
-                        static_cast<unsigned>(cg.dw), cg.sh, cg.sw, cg.ph, cg.pw};
-    w8_tiles_body<SUBS, SPLITK>(src, ac, wt, geo, y, y_dtype);
+    w8_tiles_body<SUBS, SPLITK>(w8_conv_src(act, ac, cg), ac, wt, geo, y, y_dtype);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -161,11 +93,6 @@ __global__ __launch_bounds__(kBlock) void qconv_w8_levels_kernel(const void* __r
 // ------------------------------------------------------------------------------------------------
 // host side: the plan and the launchers
 // ------------------------------------------------------------------------------------------------
-struct W8ConvShape {        // a checked geometry
-    int64_t M, N, K, OH, OW, x_elems;
-    W8ConvGeom cg;
-};
-
 struct W8ConvPlan {
     int form, shape, block, lds, rows, cols, ksplit, subs;
     int64_t grid, row_tiles, col_tiles;
@@ -251,61 +178,12 @@ static hipError_t conv_w8_levels(const void* x, int64_t n, const W8Act& act, voi
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// the geometry's checks; fills `s`
-int check_conv_geom(const char* what, int dtype, const lsq_qconv_w8_geom* g, lsq::W8ConvShape& s) {
-    if (dtype == LSQ_F64) return fail(LSQ_EINVAL, "%s: float64 is not supported (the kernel computes in integers and float32)", what);
-    if (dtype != LSQ_F32 && dtype != LSQ_BF16 && dtype != LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
-    if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
-    typedef long long ll;
-    if (g->B < 1 || g->Cin < 1 || g->H < 1 || g->W < 1)
-        return fail(LSQ_EINVAL, "%s: x is [B, H, W, Cin] = [%lld, %lld, %lld, %lld], every extent must be at least 1", what,
-                    static_cast<ll>(g->B), static_cast<ll>(g->H), static_cast<ll>(g->W), static_cast<ll>(g->Cin));
-    if (g->Cout < 0) return fail(LSQ_EINVAL, "%s: negative Cout = %lld", what, static_cast<ll>(g->Cout));
-    if (g->kh < 1 || g->kw < 1)
-        return fail(LSQ_EINVAL, "%s: the kernel is %lld x %lld, both must be positive", what, static_cast<ll>(g->kh), static_cast<ll>(g->kw));
-    if (g->sh < 1 || g->sw < 1)
-        return fail(LSQ_EINVAL, "%s: the stride is (%lld, %lld), both must be positive", what, static_cast<ll>(g->sh), static_cast<ll>(g->sw));
-    if (g->dh < 1 || g->dw < 1)
-        return fail(LSQ_EINVAL, "%s: the dilation is (%lld, %lld), both must be positive", what, static_cast<ll>(g->dh), static_cast<ll>(g->dw));
-    if (g->ph < 0 || g->pw < 0)
-        return fail(LSQ_EINVAL, "%s: the padding is (%lld, %lld), negative padding is not supported", what, static_cast<ll>(g->ph),
-                    static_cast<ll>(g->pw));
-    const int64_t lim = INT32_MAX;
-    if (g->H > lim || g->W > lim || g->ph > lim || g->pw > lim || g->H + 2 * g->ph > lim || g->W + 2 * g->pw > lim || g->sh > lim ||
-        g->sw > lim || g->dh > lim || g->dw > lim)
-        return fail(LSQ_EINVAL, "%s: a padded extent (H + 2 ph, W + 2 pw), stride or dilation is beyond 31 bits", what);
-    const int64_t eh = g->H + 2 * g->ph - 1, ew = g->W + 2 * g->pw - 1;           // the last padded coordinate
-    if (g->kh - 1 > eh / g->dh || g->kw - 1 > ew / g->dw)
-        return fail(LSQ_EINVAL, "%s: an empty output: the dilated %lld x %lld kernel does not fit the padded [%lld, %lld] image", what,
-                    static_cast<ll>(g->kh), static_cast<ll>(g->kw), static_cast<ll>(eh + 1), static_cast<ll>(ew + 1));
-    s.OH = (eh - g->dh * (g->kh - 1)) / g->sh + 1;
-    s.OW = (ew - g->dw * (g->kw - 1)) / g->sw + 1;
-    const int64_t taps = g->kh * g->kw;                                             // both below 2^31
-    const int64_t pix = s.OH * s.OW, img = g->H * g->W;                             // likewise
-    if (g->Cin > INT64_MAX / taps || g->B > INT64_MAX / pix || g->Cin > INT64_MAX / 4 / img || g->B > INT64_MAX / 4 / (img * g->Cin))
-        return fail(LSQ_EINVAL, "%s: the shapes are beyond 64-bit offsets", what);
-    s.M = g->B * pix;
-    s.N = g->Cout;
-    s.K = taps * g->Cin;
-    s.x_elems = g->B * img * g->Cin;
-    if (s.M > INT64_MAX / std::max<int64_t>(1, std::max(s.N, s.K)) / 4 || s.N > INT64_MAX / s.K)
-        return fail(LSQ_EINVAL, "%s: %lld output pixels on a [%lld, %lld] weight are beyond 64-bit offsets", what, static_cast<ll>(s.M),
-                    static_cast<ll>(s.N), static_cast<ll>(s.K));
-    s.cg = lsq::W8ConvGeom{g->Cin, s.OH, s.OW, img * g->Cin, static_cast<int>(g->H), static_cast<int>(g->W), static_cast<int>(g->kw),
-                           static_cast<int>(g->sh), static_cast<int>(g->sw), static_cast<int>(g->ph), static_cast<int>(g->pw),
-                           static_cast<int>(g->dh), static_cast<int>(g->dw)};
-    return LSQ_OK;
-}
+const char* const kCodes = "LSQ_QCONV_W8";
 
-int check_conv_level_dtype(const char* what, const char* name, int code) {
-    if (code != LSQ_QCONV_W8_U8 && code != LSQ_QCONV_W8_I8)
-        return fail(LSQ_EINVAL, "%s: %s must be LSQ_QCONV_W8_U8 (0) or LSQ_QCONV_W8_I8 (1), got %d", what, name, code);
-    return LSQ_OK;
-}
-
+// (not lsq_w8_host_checks.hpp's check_weights: the bias is held to y's type in other words, and y's alignment is checked here)
 int check_conv_weights(const char* what, int y_dtype, int w_level_dtype, const void* w_levels, const void* w_scale, const void* w_zero,
                        const void* bias, int bias_dtype, const void* y) {
-    if (int rc = check_conv_level_dtype(what, "w_level_dtype", w_level_dtype)) return rc;
+    if (int rc = check_level_dtype(what, kCodes, "w_level_dtype", w_level_dtype)) return rc;
     if (!w_levels || !w_scale || !w_zero || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (bias && bias_dtype != LSQ_F32 && bias_dtype != y_dtype)
         return fail(LSQ_EINVAL, "%s: the bias must be float32 or of y's type, got dtype code %d", what, bias_dtype);
@@ -336,8 +214,9 @@ int lsq_qconv_w8_forward_levels(int level_dtype, const void* x_levels, const voi
                                 int bias_dtype, void* y, int y_dtype, void* stream) {
     const char* what = "lsq_qconv_w8_forward_levels";
     lsq::W8ConvShape s;
-    if (int rc = check_conv_geom(what, y_dtype, geom, s)) return rc;
-    if (int rc = check_conv_level_dtype(what, "level_dtype", level_dtype)) return rc;
+    if (int rc = check_dtype(what, y_dtype)) return rc;
+    if (int rc = check_conv_geom(what, geom, s)) return rc;
+    if (int rc = check_level_dtype(what, kCodes, "level_dtype", level_dtype)) return rc;
     if (!x_levels || !s_x || !zx) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (int rc = check_conv_weights(what, y_dtype, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
     if (!aligned_to(s_x, 4) || !aligned_to(zx, 4)) return fail(LSQ_EINVAL, "%s: s_x and zx must be element-aligned", what);
@@ -350,8 +229,7 @@ int lsq_qconv_w8_forward_levels(int level_dtype, const void* x_levels, const voi
     act.zx = static_cast<const int32_t*>(zx);
     act.off = level_dtype == LSQ_QCONV_W8_U8 ? 128 : 0;
     act.fused = 0;
-    const lsq::W8Weight wt{static_cast<const uint8_t*>(w_levels), static_cast<const float*>(w_scale), static_cast<const int32_t*>(w_zero),
-                           bias, bias_dtype, w_level_dtype == LSQ_QCONV_W8_U8 ? 128 : 0};
+    const lsq::W8Weight wt = weight_arg(w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype);
     return hip_status(lsq::conv_w8_launch(pl, act, wt, s, y, y_dtype, static_cast<hipStream_t>(stream)), what);
 }
 
@@ -361,12 +239,9 @@ int lsq_qconv_w8_forward(int dtype, const void* x, const void* scale, const void
                          void* stream) {
     const char* what = "lsq_qconv_w8_forward";
     lsq::W8ConvShape s;
-    if (int rc = check_conv_geom(what, dtype, geom, s)) return rc;
-    const long long lo = std::min(quant_min, type_min), hi = std::max(quant_max, type_max);
-    if (quant_min > quant_max || type_min > type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-        return fail(LSQ_EINVAL, "%s: [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must lie within "
-                    "0..255 or within -128..127", what, static_cast<long long>(quant_min), static_cast<long long>(quant_max),
-                    static_cast<long long>(type_min), static_cast<long long>(type_max));
+    if (int rc = check_dtype(what, dtype)) return rc;
+    if (int rc = check_conv_geom(what, geom, s)) return rc;
+    if (int rc = check_byte_range(what, "", quant_min, quant_max, type_min, type_max)) return rc;
     if (!x || !scale || !shift) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (int rc = check_conv_weights(what, dtype, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
     if (!aligned_to(x, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: x and y must be element-aligned", what);
@@ -385,10 +260,9 @@ int lsq_qconv_w8_forward(int dtype, const void* x, const void* scale, const void
     act.qmax = static_cast<float>(quant_max);
     act.tmin = static_cast<float>(type_min);
     act.tmax = static_cast<float>(type_max);
-    act.off = hi > 127 ? 128 : 0;
+    act.off = std::max(quant_max, type_max) > 127 ? 128 : 0;
     act.fused = 1;
-    const lsq::W8Weight wt{static_cast<const uint8_t*>(w_levels), static_cast<const float*>(w_scale), static_cast<const int32_t*>(w_zero),
-                           bias, bias_dtype, w_level_dtype == LSQ_QCONV_W8_U8 ? 128 : 0};
+    const lsq::W8Weight wt = weight_arg(w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = hipSuccess;
     switch (dtype) {
@@ -403,18 +277,11 @@ int lsq_qconv_w8_forward(int dtype, const void* x, const void* scale, const void
 int lsq_qconv_w8_plan(const lsq_qconv_w8_geom* geom, int aligned, int32_t* out8) {
     const char* what = "lsq_qconv_w8_plan";
     lsq::W8ConvShape s;
-    if (int rc = check_conv_geom(what, LSQ_F32, geom, s)) return rc;
+    if (int rc = check_conv_geom(what, geom, s)) return rc;
     if (!out8) return fail(LSQ_EINVAL, "%s: NULL output", what);
     lsq::W8ConvPlan pl;
     if (int rc = checked_conv_plan(what, pl, s, aligned != 0)) return rc;
-    out8[0] = pl.form;
-    out8[1] = pl.shape;
-    out8[2] = static_cast<int32_t>(pl.grid);
-    out8[3] = pl.block;
-    out8[4] = pl.rows;
-    out8[5] = pl.cols;
-    out8[6] = pl.lds;
-    out8[7] = pl.ksplit;
+    write_plan(pl, out8);
     return LSQ_OK;
 }
 

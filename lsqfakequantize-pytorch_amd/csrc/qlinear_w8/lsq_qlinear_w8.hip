@@ -126,8 +126,9 @@ __global__ __launch_bounds__(kW8Block) void qlinear_w8_decode_kernel(W8Act act, 
 
 // ------------------------------------------------------------------------------------------------
 // matrix-core form, TILES: any number of rows
-// (csrc/qconv_w8/lsq_qconv_w8_tiles.hpp holds this kernel once more, over a source of the A packet, for the convolution: shared
-//  as a function it changes these kernels' instruction streams (profiles/r16_qconv_w8_isa_diff.txt).  A fix here belongs there too.)
+// (This K loop is written out here, in csrc/qconv_w8/lsq_w8_tiles_loop.hpp's w8_tiles_run, which nearly every other W8A8 tile kernel
+//  runs, and in one more place named there: shared as a function it changes these kernels by 10 to 34 VGPRs.  A fix
+//  here belongs there too.)
 // ------------------------------------------------------------------------------------------------
 template <int SUBS, bool SPLITK>
 __global__ __launch_bounds__(kW8TileWaves * 64, 2) void qlinear_w8_tiles_kernel(W8Act act, W8Weight wt, W8Geom geo, void* __restrict__ y,

@@ -14,75 +14,13 @@
 //  * GENERIC form (every other legal call): the generic kernels' integer sum (one wave per output column and four rows),
 //    the same epilogue function, byte stores.  Correct, not tuned.
 //  * The fused entry forms run the flat pre-pass w8_levels_body first.
-// W8ConvGeom, W8ConvSrc, w8_conv_row and the geometry's checks are csrc/qconv_w8/lsq_qconv_w8.hip's, which is a translation
-// unit and not a header: a fix there belongs here too.
+// W8ConvGeom, W8ConvSrc and w8_conv_row are csrc/qconv_w8/lsq_w8_conv_src.hpp's, the checks csrc/qconv_w8/lsq_w8_host_checks.hpp's
+// and, the output quantizer's, lsq_requant_w8_checks.hpp's.  The linear tile kernels run lsq_requant_w8_tiles.hpp's written-out
+// body, the convolution's the shared one (the reason: there).
 #include "lsq_requant_w8_tiles.hpp"
-#include "../../../include/lsq_hip_requant_w8.h"
+#include "lsq_requant_w8_checks.hpp"
 
 namespace lsq {
-
-struct W8ConvGeom {         // kernel argument; the host has checked that the coordinates fit 32 bits
-    int64_t Cin, OH, OW, image;     // image = H W Cin, the bytes of one image of x
-    int H, W, kw, sh, sw, ph, pw, dh, dw;
-};
-
-struct W8ConvRow {          // output pixel m = (b, oh, ow): where its receptive field starts
-    int64_t base;           // b * image
-    int ih0, iw0;           // oh sh - ph, ow sw - pw
-};
-
-__device__ __forceinline__ W8ConvRow w8_conv_row(int64_t m, int64_t OH, int64_t OW, int64_t image, int sh, int sw, int ph, int pw) {
-    const int64_t t = m / OW, ow = m - t * OW;
-    const int64_t b = t / OH, oh = t - b * OH;
-    W8ConvRow r;
-    r.base = b * image;
-    r.ih0 = static_cast<int>(oh * sh - ph);
-    r.iw0 = static_cast<int>(ow * sw - pw);
-    return r;
-}
-
-// the implicit [B OH OW, kh kw Cin] matrix of byte operands, Cin % 16 == 0 and K <= 65536 (scalars only)
-struct W8ConvSrc {
-    const uint8_t* a;
-    uint32_t flip;          // of a loaded packet
-    uint32_t pad;           // four times the byte zx - off: a tap in the padding
-    int64_t OH, OW, image;
-    unsigned H, W, Cin, kw, dh, dw;
-    int sh, sw, ph, pw;
-    typedef W8ConvRow Row;
-    struct Col {            // k = (i kw + j) Cin + c
-        unsigned idh, jdw;  // i dh, j dw
-        unsigned j, c;
-    };
-    __device__ __forceinline__ Row row(int64_t m) const { return w8_conv_row(m, OH, OW, image, sh, sw, ph, pw); }
-    __device__ __forceinline__ Col col(int64_t k) const {
-        const unsigned kk = static_cast<unsigned>(k);
-        const unsigned tap = kk / Cin, i = tap / kw, j = tap - i * kw;
-        return Col{i * dh, j * dw, j, kk - tap * Cin};
-    }
-    __device__ __forceinline__ void advance(Col& p) const {     // 16 bytes further: Cin % 16 == 0, so c reaches Cin exactly
-        p.c += 16u;
-        if (p.c >= Cin) {
-            p.c = 0u;
-            p.j += 1u;
-            p.jdw += dw;
-            if (p.j == kw) {
-                p.j = 0u;
-                p.jdw = 0u;
-                p.idh += dh;
-            }
-        }
-    }
-    __device__ __forceinline__ u32x4 packet(const Row& r, const Col& p) const {
-        const unsigned ih = static_cast<unsigned>(r.ih0) + p.idh, iw = static_cast<unsigned>(r.iw0) + p.jdw;   // negative: huge
-        u32x4 v = {pad, pad, pad, pad};
-        if (ih < H && iw < W) {
-            const int64_t at = r.base + (static_cast<int64_t>(ih) * W + iw) * Cin + p.c;
-            v = *reinterpret_cast<const u32x4*>(a + at) ^ flip;
-        }
-        return v;
-    }
-};
 
 // ------------------------------------------------------------------------------------------------
 // matrix-core form
@@ -92,18 +30,14 @@ __global__ __launch_bounds__(kW8TileWaves * 64, 2) void requant_w8_linear_tiles_
                                                                                       uint8_t* __restrict__ y) {
     const W8Const ac = w8_constants(act);
     const W8LinSrc src{act.a, ac.flip, geo.K};
-    w8q_tiles_body<SUBS, SPLITK>(src, ac, wt, geo, out, y);
+    w8q_lin_tiles_body<SUBS, SPLITK>(src, ac, wt, geo, out, y);
 }
 
 template <int SUBS, bool SPLITK>
 __global__ __launch_bounds__(kW8TileWaves * 64, 2) void requant_w8_conv_tiles_kernel(W8Act act, W8Weight wt, W8Geom geo, W8ConvGeom cg,
                                                                                     W8OutArg out, uint8_t* __restrict__ y) {
     const W8Const ac = w8_constants(act);
-    const uint32_t pad = static_cast<uint32_t>(ac.z & 0xff) * 0x01010101u;
-    const W8ConvSrc src{act.a, ac.flip, pad, cg.OH, cg.OW, cg.image, static_cast<unsigned>(cg.H), static_cast<unsigned>(cg.W),
-                        static_cast<unsigned>(cg.Cin), static_cast<unsigned>(cg.kw), static_cast<unsigned>(cg.dh),
-                        static_cast<unsigned>(cg.dw), cg.sh, cg.sw, cg.ph, cg.pw};
-    w8q_tiles_body<SUBS, SPLITK>(src, ac, wt, geo, out, y);
+    w8q_tiles_body<SUBS, SPLITK>(w8_conv_src(act, ac, cg), ac, wt, geo, out, y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -195,11 +129,6 @@ __global__ __launch_bounds__(kBlock) void requant_w8_levels_kernel(const void* _
 // ------------------------------------------------------------------------------------------------
 // host side: the plan and the launchers
 // ------------------------------------------------------------------------------------------------
-struct W8ConvShape {        // a checked geometry
-    int64_t M, N, K, OH, OW, x_elems;
-    W8ConvGeom cg;
-};
-
 struct W8QPlan {
     int form, shape, block, lds, rows, cols, ksplit, subs, store;
     int64_t grid, row_tiles, col_tiles;
@@ -310,174 +239,15 @@ static hipError_t requant_prepass(int dtype, const void* x, int64_t n, const W8A
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-typedef long long ll;
-
-int check_dtype(const char* what, int dtype) {
-    if (dtype == LSQ_F64) return fail(LSQ_EINVAL, "%s: float64 is not supported (the kernel computes in integers and float32)", what);
-    if (dtype != LSQ_F32 && dtype != LSQ_BF16 && dtype != LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
-    return LSQ_OK;
-}
-
-// the output quantizer's checks; the mid dtype (which takes the place of y's dtype in the other checks) into `mid`
-int check_out(const char* what, const lsq_requant_w8_out* o, int& mid, lsq::W8OutArg& arg) {
-    if (!o) return fail(LSQ_EINVAL, "%s: NULL output quantizer", what);
-    if (o->mid_dtype != LSQ_F32 && o->mid_dtype != LSQ_BF16 && o->mid_dtype != LSQ_F16)
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(o->mid_dtype));
-    if (!o->out_scale || !o->out_shift) return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift", what);
-    if (!aligned_to(o->out_scale, 4) || !aligned_to(o->out_shift, 4))
-        return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
-    const ll lo = std::min(o->quant_min, o->type_min), hi = std::max(o->quant_max, o->type_max);
-    if (o->quant_min > o->quant_max || o->type_min > o->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-        return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                    "lie within 0..255 or within -128..127", what, static_cast<ll>(o->quant_min), static_cast<ll>(o->quant_max),
-                    static_cast<ll>(o->type_min), static_cast<ll>(o->type_max));
-    mid = static_cast<int>(o->mid_dtype);
-    arg = lsq::W8OutArg{static_cast<const float*>(o->out_scale), static_cast<const float*>(o->out_shift),
-                        static_cast<float>(o->quant_min), static_cast<float>(o->quant_max), static_cast<float>(o->type_min),
-                        static_cast<float>(o->type_max), o->relu ? 1 : 0, mid, 0};
-    return LSQ_OK;
-}
-
-int check_linear_shape(const char* what, int64_t M, int64_t N, int64_t K) {
-    const ll m = M, n = N, k = K;
-    if (N < 0 || K < 0) return fail(LSQ_EINVAL, "%s: negative weight shape [%lld, %lld]", what, n, k);
-    if (M < 1) return fail(LSQ_EINVAL, "%s: M = %lld rows of x, at least 1 is needed", what, m);
-    if (M > INT64_MAX / std::max<int64_t>(1, std::max(N, K)) / 4 || N > INT64_MAX / std::max<int64_t>(1, K))
-        return fail(LSQ_EINVAL, "%s: M = %lld rows of x on a [%lld, %lld] weight are beyond 64-bit offsets", what, m, n, k);
-    return LSQ_OK;
-}
-
-// the geometry's checks (check_conv_geom of csrc/qconv_w8/lsq_qconv_w8.hip); fills `s`
-int check_conv_geom(const char* what, const lsq_qconv_w8_geom* g, lsq::W8ConvShape& s) {
-    if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
-    if (g->B < 1 || g->Cin < 1 || g->H < 1 || g->W < 1)
-        return fail(LSQ_EINVAL, "%s: x is [B, H, W, Cin] = [%lld, %lld, %lld, %lld], every extent must be at least 1", what,
-                    static_cast<ll>(g->B), static_cast<ll>(g->H), static_cast<ll>(g->W), static_cast<ll>(g->Cin));
-    if (g->Cout < 0) return fail(LSQ_EINVAL, "%s: negative Cout = %lld", what, static_cast<ll>(g->Cout));
-    if (g->kh < 1 || g->kw < 1)
-        return fail(LSQ_EINVAL, "%s: the kernel is %lld x %lld, both must be positive", what, static_cast<ll>(g->kh), static_cast<ll>(g->kw));
-    if (g->sh < 1 || g->sw < 1)
-        return fail(LSQ_EINVAL, "%s: the stride is (%lld, %lld), both must be positive", what, static_cast<ll>(g->sh), static_cast<ll>(g->sw));
-    if (g->dh < 1 || g->dw < 1)
-        return fail(LSQ_EINVAL, "%s: the dilation is (%lld, %lld), both must be positive", what, static_cast<ll>(g->dh), static_cast<ll>(g->dw));
-    if (g->ph < 0 || g->pw < 0)
-        return fail(LSQ_EINVAL, "%s: the padding is (%lld, %lld), negative padding is not supported", what, static_cast<ll>(g->ph),
-                    static_cast<ll>(g->pw));
-    const int64_t lim = INT32_MAX;
-    if (g->H > lim || g->W > lim || g->ph > lim || g->pw > lim || g->H + 2 * g->ph > lim || g->W + 2 * g->pw > lim || g->sh > lim ||
-        g->sw > lim || g->dh > lim || g->dw > lim)
-        return fail(LSQ_EINVAL, "%s: a padded extent (H + 2 ph, W + 2 pw), stride or dilation is beyond 31 bits", what);
-    const int64_t eh = g->H + 2 * g->ph - 1, ew = g->W + 2 * g->pw - 1;           // the last padded coordinate
-    if (g->kh - 1 > eh / g->dh || g->kw - 1 > ew / g->dw)
-        return fail(LSQ_EINVAL, "%s: an empty output: the dilated %lld x %lld kernel does not fit the padded [%lld, %lld] image", what,
-                    static_cast<ll>(g->kh), static_cast<ll>(g->kw), static_cast<ll>(eh + 1), static_cast<ll>(ew + 1));
-    s.OH = (eh - g->dh * (g->kh - 1)) / g->sh + 1;
-    s.OW = (ew - g->dw * (g->kw - 1)) / g->sw + 1;
-    const int64_t taps = g->kh * g->kw;                                             // both below 2^31
-    const int64_t pix = s.OH * s.OW, img = g->H * g->W;                             // likewise
-    if (g->Cin > INT64_MAX / taps || g->B > INT64_MAX / pix || g->Cin > INT64_MAX / 4 / img || g->B > INT64_MAX / 4 / (img * g->Cin))
-        return fail(LSQ_EINVAL, "%s: the shapes are beyond 64-bit offsets", what);
-    s.M = g->B * pix;
-    s.N = g->Cout;
-    s.K = taps * g->Cin;
-    s.x_elems = g->B * img * g->Cin;
-    if (s.M > INT64_MAX / std::max<int64_t>(1, std::max(s.N, s.K)) / 4 || s.N > INT64_MAX / s.K)
-        return fail(LSQ_EINVAL, "%s: %lld output pixels on a [%lld, %lld] weight are beyond 64-bit offsets", what, static_cast<ll>(s.M),
-                    static_cast<ll>(s.N), static_cast<ll>(s.K));
-    s.cg = lsq::W8ConvGeom{g->Cin, s.OH, s.OW, img * g->Cin, static_cast<int>(g->H), static_cast<int>(g->W), static_cast<int>(g->kw),
-                           static_cast<int>(g->sh), static_cast<int>(g->sw), static_cast<int>(g->ph), static_cast<int>(g->pw),
-                           static_cast<int>(g->dh), static_cast<int>(g->dw)};
-    return LSQ_OK;
-}
-
-int check_level_dtype(const char* what, const char* name, int code) {
-    if (code != LSQ_REQUANT_W8_U8 && code != LSQ_REQUANT_W8_I8)
-        return fail(LSQ_EINVAL, "%s: %s must be LSQ_REQUANT_W8_U8 (0) or LSQ_REQUANT_W8_I8 (1), got %d", what, name, code);
-    return LSQ_OK;
-}
-
-// `mid`: the dtype of the unfused op's y
-int check_weights(const char* what, int mid, int w_level_dtype, const void* w_levels, const void* w_scale, const void* w_zero,
-                  const void* bias, int bias_dtype, const void* y) {
-    if (int rc = check_level_dtype(what, "w_level_dtype", w_level_dtype)) return rc;
-    if (!w_levels || !w_scale || !w_zero || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
-    if (bias && bias_dtype != LSQ_F32 && bias_dtype != mid)
-        return fail(LSQ_EINVAL, "%s: the bias must be float32 or of mid_dtype, got dtype code %d", what, bias_dtype);
-    if (!aligned_to(w_scale, 4) || !aligned_to(w_zero, 4) || (bias && !aligned_to(bias, elem_bytes(bias_dtype))))
-        return fail(LSQ_EINVAL, "%s: w_scale, w_zero and bias must be element-aligned", what);
-    return LSQ_OK;
-}
-
-int check_levels_in(const char* what, int level_dtype, const void* x_levels, const void* s_x, const void* zx) {
-    if (int rc = check_level_dtype(what, "level_dtype", level_dtype)) return rc;
-    if (!x_levels || !s_x || !zx) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
-    if (!aligned_to(s_x, 4) || !aligned_to(zx, 4)) return fail(LSQ_EINVAL, "%s: s_x and zx must be element-aligned", what);
-    return LSQ_OK;
-}
-
 int check_float_in(const char* what, int dtype, int mid, const void* x, const void* scale, const void* shift, int64_t quant_min,
                    int64_t quant_max, int64_t type_min, int64_t type_max) {
     if (dtype != mid)
         return fail(LSQ_EINVAL, "%s: mid_dtype (code %d) must be x's dtype (code %d): the unfused op's y has x's dtype", what, mid, dtype);
-    const ll lo = std::min(quant_min, type_min), hi = std::max(quant_max, type_max);
-    if (quant_min > quant_max || type_min > type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-        return fail(LSQ_EINVAL, "%s: [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must lie within "
-                    "0..255 or within -128..127", what, static_cast<ll>(quant_min), static_cast<ll>(quant_max),
-                    static_cast<ll>(type_min), static_cast<ll>(type_max));
+    if (int rc = check_byte_range(what, "", quant_min, quant_max, type_min, type_max)) return rc;
     if (!x || !scale || !shift) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (!aligned_to(x, elem_bytes(dtype))) return fail(LSQ_EINVAL, "%s: x must be element-aligned", what);
     if (!aligned_to(scale, 4) || !aligned_to(shift, 4)) return fail(LSQ_EINVAL, "%s: scale and shift must be element-aligned", what);
     return LSQ_OK;
-}
-
-int check_grid(const char* what, const lsq::W8QPlan& pl, int64_t M, int64_t N) {
-    if (pl.grid > INT32_MAX)
-        return fail(LSQ_EINVAL, "%s: %lld rows by %lld output columns are beyond a 31-bit grid", what, static_cast<ll>(M), static_cast<ll>(N));
-    return LSQ_OK;
-}
-
-lsq::W8Act levels_act(int level_dtype, const void* x_levels, const void* s_x, const void* zx) {
-    lsq::W8Act act{};
-    act.a = static_cast<const uint8_t*>(x_levels);
-    act.scale = static_cast<const float*>(s_x);
-    act.zx = static_cast<const int32_t*>(zx);
-    act.off = level_dtype == LSQ_REQUANT_W8_U8 ? 128 : 0;
-    act.fused = 0;
-    act.aligned = aligned_to(x_levels, 16) ? 1 : 0;
-    return act;
-}
-
-lsq::W8Act fused_act(const void* levels_ws, const void* scale, const void* shift, int64_t quant_min, int64_t quant_max,
-                     int64_t type_min, int64_t type_max) {
-    lsq::W8Act act{};
-    act.a = static_cast<const uint8_t*>(levels_ws);
-    act.scale = static_cast<const float*>(scale);
-    act.shift = static_cast<const float*>(shift);
-    act.qmin = static_cast<float>(quant_min);
-    act.qmax = static_cast<float>(quant_max);
-    act.tmin = static_cast<float>(type_min);
-    act.tmax = static_cast<float>(type_max);
-    act.off = std::max(quant_max, type_max) > 127 ? 128 : 0;
-    act.fused = 1;
-    act.aligned = 1;
-    return act;
-}
-
-lsq::W8Weight weight_arg(int w_level_dtype, const void* w_levels, const void* w_scale, const void* w_zero, const void* bias, int bias_dtype) {
-    return lsq::W8Weight{static_cast<const uint8_t*>(w_levels), static_cast<const float*>(w_scale), static_cast<const int32_t*>(w_zero),
-                         bias, bias_dtype, w_level_dtype == LSQ_REQUANT_W8_U8 ? 128 : 0};
-}
-
-void write_plan(const lsq::W8QPlan& pl, int32_t* out9) {
-    out9[0] = pl.form;
-    out9[1] = pl.shape;
-    out9[2] = static_cast<int32_t>(pl.grid);
-    out9[3] = pl.block;
-    out9[4] = pl.rows;
-    out9[5] = pl.cols;
-    out9[6] = pl.lds;
-    out9[7] = pl.ksplit;
-    out9[8] = pl.store;
 }
 
 }  // namespace
@@ -496,10 +266,10 @@ int lsq_requant_w8_linear_levels(int level_dtype, const void* x_levels, int64_t 
     lsq::W8OutArg oa{};
     if (int rc = check_out(what, out, mid, oa)) return rc;
     if (int rc = check_linear_shape(what, M, N, K)) return rc;
-    if (int rc = check_levels_in(what, level_dtype, x_levels, s_x, zx)) return rc;
-    if (int rc = check_weights(what, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
+    if (int rc = check_levels_in(what, kCodes, level_dtype, x_levels, s_x, zx)) return rc;
+    if (int rc = check_weights(what, kCodes, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
     const lsq::W8QPlan pl = lsq::plan_requant_linear(M, N, K, aligned_to(w_levels, 16) && aligned_to(x_levels, 16), aligned_to(y, 16));
-    if (int rc = check_grid(what, pl, M, N)) return rc;
+    if (int rc = check_grid(what, pl.grid, M, N)) return rc;
     if (N == 0) return LSQ_OK;
     return hip_status(lsq::requant_launch(pl, levels_act(level_dtype, x_levels, s_x, zx),
                                           weight_arg(w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype), M, N, K, nullptr, oa,
@@ -517,9 +287,9 @@ int lsq_requant_w8_linear(int dtype, const void* x, int64_t M, const void* scale
     if (int rc = check_out(what, out, mid, oa)) return rc;
     if (int rc = check_linear_shape(what, M, N, K)) return rc;
     if (int rc = check_float_in(what, dtype, mid, x, scale, shift, quant_min, quant_max, type_min, type_max)) return rc;
-    if (int rc = check_weights(what, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
+    if (int rc = check_weights(what, kCodes, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
     const lsq::W8QPlan pl = lsq::plan_requant_linear(M, N, K, aligned_to(w_levels, 16), aligned_to(y, 16));
-    if (int rc = check_grid(what, pl, M, N)) return rc;
+    if (int rc = check_grid(what, pl.grid, M, N)) return rc;
     if (!levels_ws || !aligned_to(levels_ws, 16))
         return fail(LSQ_EINVAL, "%s: levels_ws must be a 16-byte aligned device buffer of M * K bytes", what);
     if (N == 0) return LSQ_OK;
@@ -540,10 +310,10 @@ int lsq_requant_w8_conv_levels(int level_dtype, const void* x_levels, const void
     lsq::W8ConvShape s;
     if (int rc = check_out(what, out, mid, oa)) return rc;
     if (int rc = check_conv_geom(what, geom, s)) return rc;
-    if (int rc = check_levels_in(what, level_dtype, x_levels, s_x, zx)) return rc;
-    if (int rc = check_weights(what, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
+    if (int rc = check_levels_in(what, kCodes, level_dtype, x_levels, s_x, zx)) return rc;
+    if (int rc = check_weights(what, kCodes, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
     const lsq::W8QPlan pl = lsq::plan_requant_conv(s, aligned_to(w_levels, 16) && aligned_to(x_levels, 16), aligned_to(y, 16));
-    if (int rc = check_grid(what, pl, s.M, s.N)) return rc;
+    if (int rc = check_grid(what, pl.grid, s.M, s.N)) return rc;
     if (s.N == 0) return LSQ_OK;
     return hip_status(lsq::requant_launch(pl, levels_act(level_dtype, x_levels, s_x, zx),
                                           weight_arg(w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype), s.M, s.N, s.K, &s.cg, oa,
@@ -562,9 +332,9 @@ int lsq_requant_w8_conv(int dtype, const void* x, const void* scale, const void*
     if (int rc = check_out(what, out, mid, oa)) return rc;
     if (int rc = check_conv_geom(what, geom, s)) return rc;
     if (int rc = check_float_in(what, dtype, mid, x, scale, shift, quant_min, quant_max, type_min, type_max)) return rc;
-    if (int rc = check_weights(what, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
+    if (int rc = check_weights(what, kCodes, mid, w_level_dtype, w_levels, w_scale, w_zero, bias, bias_dtype, y)) return rc;
     const lsq::W8QPlan pl = lsq::plan_requant_conv(s, aligned_to(w_levels, 16), aligned_to(y, 16));
-    if (int rc = check_grid(what, pl, s.M, s.N)) return rc;
+    if (int rc = check_grid(what, pl.grid, s.M, s.N)) return rc;
     if (!levels_ws || !aligned_to(levels_ws, 16))
         return fail(LSQ_EINVAL, "%s: levels_ws must be a 16-byte aligned device buffer of B * H * W * Cin bytes", what);
     if (s.N == 0) return LSQ_OK;
@@ -580,8 +350,9 @@ int lsq_requant_w8_plan_linear(int64_t M, int64_t N, int64_t K, int aligned, int
     if (int rc = check_linear_shape(what, M, N, K)) return rc;
     if (!out9) return fail(LSQ_EINVAL, "%s: NULL output", what);
     const lsq::W8QPlan pl = lsq::plan_requant_linear(M, N, K, aligned != 0, y_aligned != 0);
-    if (int rc = check_grid(what, pl, M, N)) return rc;
+    if (int rc = check_grid(what, pl.grid, M, N)) return rc;
     write_plan(pl, out9);
+    out9[8] = pl.store;
     return LSQ_OK;
 }
 
@@ -591,8 +362,9 @@ int lsq_requant_w8_plan_conv(const lsq_qconv_w8_geom* geom, int aligned, int y_a
     if (int rc = check_conv_geom(what, geom, s)) return rc;
     if (!out9) return fail(LSQ_EINVAL, "%s: NULL output", what);
     const lsq::W8QPlan pl = lsq::plan_requant_conv(s, aligned != 0, y_aligned != 0);
-    if (int rc = check_grid(what, pl, s.M, s.N)) return rc;
+    if (int rc = check_grid(what, pl.grid, s.M, s.N)) return rc;
     write_plan(pl, out9);
+    out9[8] = pl.store;
     return LSQ_OK;
 }
 

@@ -1,8 +1,5 @@
-// lsq_requant_w8_tiles.hpp -- the W8A8 TILES kernel with an 8-bit output: the K loop of csrc/qconv_w8/lsq_qconv_w8_tiles.hpp's
-// w8_tiles_body (a function template over the SOURCE of a 16-byte packet of the A operand, see there), step for step, and a
-// new epilogue that requantizes in registers, gathers the tile's bytes in LDS and stores 16-byte packets along n.  The loop is
-// written out here rather than shared through one more template parameter of w8_tiles_body: liblsq_hip_qconv_w8.so stays
-// byte for byte what it is ("Code sharing").  A fix to the loop belongs in all three copies.
+// lsq_requant_w8_tiles.hpp -- the W8A8 TILES kernel with an 8-bit output: csrc/qconv_w8/lsq_w8_tiles_loop.hpp's body with an
+// epilogue that requantizes in registers, gathers the tile's bytes in LDS and stores 16-byte packets along n.
 #pragma once
 #include "../qconv_w8/lsq_qconv_w8_tiles.hpp"
 
@@ -58,12 +55,68 @@ struct W8LinSrc {
     }
 };
 
-// the tile's bytes in LDS: wide tiles over the staging area, split K behind the four int32 tiles that lie over it
+// the tile's bytes in LDS, [kRows][kCols]: wide tiles over the staging area, split K behind the four int32 tiles that lie
+// over it.  A lane of the epilogue holds four rows of ONE column: stored from there the bytes would be 1-byte stores strided
+// by N.
 template <int SUBS, bool SPLITK>
-constexpr int w8q_out_offset() { return SPLITK ? kW8TileWaves * SUBS * 64 * 16 : 0; }
+__device__ __forceinline__ unsigned char* w8q_tile_bytes() {
+    typedef W8TileShape<SUBS, SPLITK> T;
+    constexpr int kOffset = SPLITK ? kW8TileWaves * SUBS * 64 * 16 : 0;
+    static_assert(kOffset + T::kRows * T::kCols <= T::kRows * kW8TileStride, "the byte tile fits the staging area");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    return smem + kOffset;
+}
+
+// the stores of the byte tile, along n, after the barrier behind the epilogue.  Bytes of columns n >= N and of rows m >= rows
+// are never read.
+template <int SUBS, bool SPLITK>
+__device__ __forceinline__ void w8q_store_tile(const W8TileAt at, int64_t N, int packets, uint8_t* __restrict__ y) {
+    typedef W8TileShape<SUBS, SPLITK> T;
+    const unsigned char* outb = w8q_tile_bytes<SUBS, SPLITK>();
+    const int tid = static_cast<int>(threadIdx.x);
+    if (packets) {                                  // N % 16 == 0: a packet that starts inside N lies inside N
+        constexpr int kPackets = T::kCols / 16;     // per row
+        for (int it = tid; it < T::kRows * kPackets; it += T::kThreads) {
+            const int m = it / kPackets, p = it - m * kPackets;
+            const int64_t n = at.nt0 + p * 16;
+            if (m < at.rows && n < N)
+                *reinterpret_cast<u32x4*>(y + (at.m0 + m) * N + n) = *reinterpret_cast<const u32x4*>(outb + m * T::kCols + p * 16);
+        }
+    } else {
+        for (int it = tid; it < T::kRows * T::kCols; it += T::kThreads) {
+            const int m = it / T::kCols, c = it - m * T::kCols;
+            const int64_t n = at.nt0 + c;
+            if (m < at.rows && n < N) y[(at.m0 + m) * N + n] = outb[it];
+        }
+    }
+}
 
 template <int SUBS, bool SPLITK, typename Src>
 __device__ __forceinline__ void w8q_tiles_body(const Src src, const W8Const ac, const W8Weight& wt, const W8Geom& geo,
+                                               const W8OutArg& out, uint8_t* __restrict__ y) {
+    constexpr int kCols = W8TileShape<SUBS, SPLITK>::kCols;
+    unsigned char* outb = w8q_tile_bytes<SUBS, SPLITK>();
+    const W8TileAt at = w8_tile_at<SUBS, SPLITK>(geo);
+    w8_tiles_run<SUBS, SPLITK>(src, ac, wt, geo, [] {}, [] {}, [&] {
+        const W8OutQ oq = w8q_constants(out);
+        return [=, &wt](int64_t I, int m, int c, int64_t n) { outb[m * kCols + c] = w8q_byte(I, wt, ac.s_x, n, oq); };
+    });
+    __syncthreads();
+    w8q_store_tile<SUBS, SPLITK>(at, geo.N, out.packets, y);
+}
+
+// ------------------------------------------------------------------------------------------------
+// WRITTEN OUT, for requant_w8_linear_tiles_kernel only: w8q_tiles_body as one function, K loop included.  On w8_tiles_run the
+// split-K SUBS = 8 linear kernel measured 1.7-2.0 % slower on [4096, 4096] at M = 128 (its K loop the same instructions in
+// other registers); written out, the six linear kernels are instruction for instruction what they were ("One
+// tile loop").  A fix to w8_tiles_run's loop or to w8q_store_tile belongs here too.
+// ------------------------------------------------------------------------------------------------
+// the tile's bytes in LDS: wide tiles over the staging area, split K behind the four int32 tiles that lie over it
+template <int SUBS, bool SPLITK>
+constexpr int w8q_lin_out_offset() { return SPLITK ? kW8TileWaves * SUBS * 64 * 16 : 0; }
+
+template <int SUBS, bool SPLITK, typename Src>
+__device__ __forceinline__ void w8q_lin_tiles_body(const Src src, const W8Const ac, const W8Weight& wt, const W8Geom& geo,
                                                const W8OutArg& out, uint8_t* __restrict__ y) {
     constexpr int kRows = SUBS * 16;
     constexpr int kThreads = kW8TileWaves * 64;
@@ -71,13 +124,13 @@ __device__ __forceinline__ void w8q_tiles_body(const Src src, const W8Const ac, 
     constexpr int kItems = (kRows * 4 + kThreads - 1) / kThreads;      // (row, 64 bytes) staging items per thread
     constexpr int kCols = SPLITK ? kW8Tile : kW8Tile * kW8TileWaves;   // output columns of the tile
     static_assert(kThreads % 4 == 0, "a thread's items share their quarter of the step");
-    static_assert(w8q_out_offset<SUBS, SPLITK>() + kRows * kCols <= kRows * kW8TileStride, "the byte tile fits the staging area");
+    static_assert(w8q_lin_out_offset<SUBS, SPLITK>() + kRows * kCols <= kRows * kW8TileStride, "the byte tile fits the staging area");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* xs = smem;                                                   // [kRows][kW8TileStride]
     int32_t* rowsum = reinterpret_cast<int32_t*>(smem + kRows * kW8TileStride);  // [kRows][4]
     int32_t* redC = rowsum + kRows * 4;                                         // [wave][column]
     int32_t* redP = reinterpret_cast<int32_t*>(smem);                           // split K: [wave][sub-tile][lane][register], over xs
-    unsigned char* outb = smem + w8q_out_offset<SUBS, SPLITK>();                // [kRows][kCols], over xs
+    unsigned char* outb = smem + w8q_lin_out_offset<SUBS, SPLITK>();                // [kRows][kCols], over xs
 
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
     const int nl = lane & 15, q = lane >> 4;
@@ -230,5 +283,6 @@ __device__ __forceinline__ void w8q_tiles_body(const Src src, const W8Const ac, 
         }
     }
 }
+
 
 }  // namespace lsq
