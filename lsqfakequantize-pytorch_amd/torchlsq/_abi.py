@@ -517,6 +517,37 @@ def eltwise_w8_library():
     return _require_companion(_ELTWISE_W8_LIB, "eltwise_w8", "the table op and the gate multiply on 8-bit levels need", eltwise_w8_error_str)
 
 
+# LayerNorm and RMSNorm on 8-bit levels with exact integer row statistics (include/lsq_hip_norm_w8.h): a fifteenth companion
+# library; the ABIs above stay as they are.
+class LsqNormW8Geom(ctypes.Structure):
+    """lsq_norm_w8_geom (include/lsq_hip_norm_w8.h): x and y [R, C], the kind of norm and the level dtype"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("R", "C", "kind", "x_dtype")]
+
+
+class LsqNormW8Consts(ctypes.Structure):
+    """lsq_norm_w8_consts (include/lsq_hip_norm_w8.h): the device constants, weight and bias (or none), output quantizer (or none),
+    the dtypes and eps"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_x", "zx", "weight", "bias", "out_scale", "out_shift")] + \
+               [(name, ctypes.c_int64) for name in ("param_dtype", "quant_min", "quant_max", "type_min", "type_max", "mid_dtype")] + \
+               [("eps", ctypes.c_float)]
+
+
+NORM_W8_ABI_VERSION = 1
+_NGP = ctypes.POINTER(LsqNormW8Geom)
+C_ABI_NORM_W8 = {
+    "lsq_norm_w8_abi_version": (_int, []),
+    "lsq_norm_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_norm_w8": (_int, [_NGP, ctypes.POINTER(LsqNormW8Consts), _vp, _vp, _vp]),
+    "lsq_norm_w8_plan": (_int, [_NGP, _int, _int, _int, _PLAN8]),
+}
+_NORM_W8_LIB, norm_w8_error_str = _load_companion("liblsq_hip_norm_w8.so", C_ABI_NORM_W8, "lsq_norm_w8_abi_version", NORM_W8_ABI_VERSION)
+
+
+def norm_w8_library():
+    """The ctypes handle of liblsq_hip_norm_w8.so (raises if it is missing)."""
+    return _require_companion(_NORM_W8_LIB, "norm_w8", "LayerNorm and RMSNorm on 8-bit levels need", norm_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -49,12 +49,13 @@ from ._pool_w8_host import (pool_w8_adaptive_kernel, pool_w8_avg, pool_w8_avg_q,
 from ._dwconv_w8_host import dwconv_w8_levels, dwconv_w8_levels_q, dwconv_w8_plan  # noqa: F401
 from ._eltwise_w8_host import (eltwise_w8_lut, eltwise_w8_mul_gate, eltwise_w8_mul_gate_q, eltwise_w8_plan_lut,  # noqa: F401
                                eltwise_w8_plan_mul)
+from ._norm_w8_host import norm_w8_layer, norm_w8_layer_q, norm_w8_plan, norm_w8_rms, norm_w8_rms_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -200,6 +201,16 @@ _MUL_GATE = "Tensor x_levels, Tensor x_scale, Tensor x_zero, Tensor g_levels, Te
 _lib_def.define("lsq_mul_gate_w8_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
                 "int out_type_max, ScalarType mid_dtype) -> Tensor" % _MUL_GATE)
 _lib_def.define("lsq_mul_gate_w8_q8(%s, ScalarType out_dtype) -> Tensor" % _MUL_GATE)
+#  * LayerNorm and RMSNorm on 8-bit LEVELS (liblsq_hip_norm_w8.so, include/lsq_hip_norm_w8.h): the last axis of a level tensor of
+#    any shape is normalised with EXACT integer row statistics (LayerNorm does not use the zero point at all), then
+#    (t * weight) + bias in float32, one rounding to `mid_dtype`, and the levels of the output quantizer (_q) or the floats
+#    themselves, in x's shape.  Not ATen's layer_norm: a small share of the levels differs by one.  Inference only.
+_NORM = "Tensor x_levels, Tensor x_scale, Tensor x_zero, Tensor? weight, Tensor? bias, float eps"
+for _norm_name in ("lsq_layer_norm_w8_q8", "lsq_rms_norm_w8_q8"):
+    _lib_def.define("%s_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
+                    "int out_type_max, ScalarType mid_dtype) -> Tensor" % (_norm_name, _NORM))
+    _lib_def.define("%s(%s, ScalarType out_dtype) -> Tensor" % (_norm_name, _NORM))
+del _norm_name
 
 
 # -------------------------------------------------------------------------------------------------
@@ -907,3 +918,32 @@ def _runtime_version():
 _lib_def.impl("_cuda_version", _runtime_version, "CompositeExplicitAutograd")
 
 _check_hip_version()
+
+
+# -------------------------------------------------------------------------------------------------
+# LayerNorm and RMSNorm on 8-bit levels (_norm_w8_host.py): GPU tensors -> liblsq_hip_norm_w8.so (one call), CPU tensors -> the
+# definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_layer_norm_w8_q8_q", norm_w8_layer_q)
+    _lib_key.impl("lsq_layer_norm_w8_q8", norm_w8_layer)
+    _lib_key.impl("lsq_rms_norm_w8_q8_q", norm_w8_rms_q)
+    _lib_key.impl("lsq_rms_norm_w8_q8", norm_w8_rms)
+del _lib_key
+
+
+def _fake_norm_w8_q(x_levels, x_scale, x_zero, weight, bias, eps, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
+                    out_type_max, mid_dtype):
+    return torch.empty(x_levels.shape, dtype=_fake_level_dtype(out_quant_max, out_type_max), device=x_levels.device)
+
+
+def _fake_norm_w8(x_levels, x_scale, x_zero, weight, bias, eps, out_dtype):
+    return torch.empty(x_levels.shape, dtype=out_dtype, device=x_levels.device)
+
+
+for _norm_name in ("lsq_layer_norm_w8_q8", "lsq_rms_norm_w8_q8"):
+    torch.library.register_fake("torchlsq::%s_q" % _norm_name, _fake_norm_w8_q, lib=_lib_def)
+    torch.library.register_fake("torchlsq::%s" % _norm_name, _fake_norm_w8, lib=_lib_def)
+    _lib_def.impl(_norm_name + "_q", _requant_no_grad(_norm_name + "_q", (1, 3, 4, 6, 7)), "Autograd")
+    _lib_def.impl(_norm_name, _requant_no_grad(_norm_name, (1, 3, 4)), "Autograd")
+del _norm_name

@@ -1278,3 +1278,81 @@ def lsq_mul_gate_w8(x: LevelsTensor, gate: LevelsTensor, out_dtype=torch.float32
     shape.  Inference only."""
     _assert_has_ops()
     return torch.ops.torchlsq.lsq_mul_gate_w8_q8(*_gate_operands("lsq_mul_gate_w8", x, gate), out_dtype)
+
+
+def _norm_rows(what, x, weight, bias, normalized_shape, dim):
+    """(levels whose LAST axis is the normalised one, as a dense view where x's memory allows it; weight and bias flattened; the
+    way back to x's shape and memory format)"""
+    x = _levels_in(what, x)
+    lv = x.levels
+    if dim in (1, -3) and lv.dim() == 4:
+        # channels-last memory: [B, H, W, C] is a dense view, C per pixel is the trailing axis
+        assert normalized_shape is None or tuple(normalized_shape) == (lv.shape[1],), \
+            "%s: dim=1 normalises over the %d channels, got normalized_shape %s" % (what, lv.shape[1], tuple(normalized_shape))
+        rows, back = lv.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1), lambda y: y.permute(0, 3, 1, 2)
+    else:
+        assert dim in (-1, lv.dim() - 1), \
+            "%s: dim must be -1 (the trailing axes) or 1 for a 4-D levels tensor in channels-last memory (C per pixel), got dim=%r for %d " \
+            "dims" % (what, dim, lv.dim())
+        n = 1 if normalized_shape is None else len(tuple(normalized_shape))
+        assert 1 <= n <= lv.dim() and (normalized_shape is None or tuple(normalized_shape) == tuple(lv.shape[-n:])), \
+            "%s: normalized_shape %s is not the trailing shape of %s" % (what, normalized_shape, tuple(lv.shape))
+        shape = tuple(lv.shape)
+        rows, back = lv.contiguous().reshape(shape[:len(shape) - n] + (-1,)), lambda y: y.reshape(shape)
+    w = None if weight is None else weight.detach().reshape(-1)
+    b = None if bias is None else bias.detach().reshape(-1)
+    return x, rows, w, b, back
+
+
+def _norm_w8_q(op, what, x, weight, bias, eps, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype,
+               normalized_shape, dim):
+    _assert_has_ops()
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    x, rows, w, b, back = _norm_rows(what, x, weight, bias, normalized_shape, dim)
+    lv = op(rows, x.scale, x.zero_point, w, b, float(eps), *o[:6], mid_dtype)
+    return _levels_out(back(lv), o[0], o[1], o[2:6])
+
+
+def _norm_w8(op, what, x, weight, bias, eps, out_dtype, normalized_shape, dim):
+    _assert_has_ops()
+    x, rows, w, b, back = _norm_rows(what, x, weight, bias, normalized_shape, dim)
+    return back(op(rows, x.scale, x.zero_point, w, b, float(eps), out_dtype))
+
+
+def lsq_layer_norm_w8_q(x: LevelsTensor, weight: Tensor = None, bias: Tensor = None, eps: float = 1e-5, out_scale: Tensor = None,
+                        out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None,
+                        out_type_max: int = None, mid_dtype=torch.float32, normalized_shape=None, dim: int = -1) -> LevelsTensor:
+    """LayerNorm on 8-bit levels with an 8-bit output, one launch (liblsq_hip_norm_w8.so): one byte read and one written per
+    activation, nothing read back.  The row statistics are EXACT integers of the levels (and do not depend on the zero point):
+    S1 = sum b, S2 = sum b^2, V = C S2 - S1^2, t = float(C b - S1) * ((1 / sqrt(float(V) / (C C) + eps / s_x^2)) / C), then
+    `(t * weight) + bias` in float32, one rounding to `mid_dtype`, and the output quantizer's levels.  The CPU path is this
+    definition in torch ops and the GPU equals it bit for bit.  IT IS NOT ATen's `layer_norm`: against
+    `lsq_levels_per_tensor(F.layer_norm(x.dequantize()))` a small share of the levels differs by one.
+    `dim=-1` normalises the trailing axis, or the trailing axes `normalized_shape` flattened (weight and bias of that shape);
+    `dim=1` is for a 4-D levels tensor in channels-last memory and normalises over C per pixel (ConvNeXt's norm).  Returns a
+    `LevelsTensor` in x's shape and memory format.  A constant row gives level(bias); with eps = 0 it gives quant_min (0 * inf).
+    Inference only."""
+    return _norm_w8_q(torch.ops.torchlsq.lsq_layer_norm_w8_q8_q, "lsq_layer_norm_w8_q", x, weight, bias, eps, out_scale, out_shift,
+                      out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype, normalized_shape, dim)
+
+
+def lsq_layer_norm_w8(x: LevelsTensor, weight: Tensor = None, bias: Tensor = None, eps: float = 1e-5, out_dtype=torch.float32,
+                      normalized_shape=None, dim: int = -1) -> Tensor:
+    """`lsq_layer_norm_w8_q` without an output quantizer: the normalised values rounded once to `out_dtype`, as a floating tensor
+    in x's shape and memory format.  Inference only."""
+    return _norm_w8(torch.ops.torchlsq.lsq_layer_norm_w8_q8, "lsq_layer_norm_w8", x, weight, bias, eps, out_dtype, normalized_shape, dim)
+
+
+def lsq_rms_norm_w8_q(x: LevelsTensor, weight: Tensor = None, bias: Tensor = None, eps: float = 1e-6, out_scale: Tensor = None,
+                      out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None,
+                      out_type_max: int = None, mid_dtype=torch.float32, normalized_shape=None, dim: int = -1) -> LevelsTensor:
+    """RMSNorm on 8-bit levels with an 8-bit output, one launch: d = b - zero_point, Q = sum d^2 (an exact integer),
+    t = float(d) * (1 / sqrt(float(Q) / C + eps / s_x^2)), then as `lsq_layer_norm_w8_q`.  Inference only."""
+    return _norm_w8_q(torch.ops.torchlsq.lsq_rms_norm_w8_q8_q, "lsq_rms_norm_w8_q", x, weight, bias, eps, out_scale, out_shift,
+                      out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype, normalized_shape, dim)
+
+
+def lsq_rms_norm_w8(x: LevelsTensor, weight: Tensor = None, bias: Tensor = None, eps: float = 1e-6, out_dtype=torch.float32,
+                    normalized_shape=None, dim: int = -1) -> Tensor:
+    """`lsq_rms_norm_w8_q` without an output quantizer: floats of `out_dtype` in x's shape and memory format.  Inference only."""
+    return _norm_w8(torch.ops.torchlsq.lsq_rms_norm_w8_q8, "lsq_rms_norm_w8", x, weight, bias, eps, out_dtype, normalized_shape, dim)
