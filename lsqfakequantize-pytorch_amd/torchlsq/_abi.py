@@ -548,6 +548,55 @@ def norm_w8_library():
     return _require_companion(_NORM_W8_LIB, "norm_w8", "LayerNorm and RMSNorm on 8-bit levels need", norm_w8_error_str)
 
 
+# The attention core on 8-bit levels: a strided batched matmul and a softmax on an integer table (include/lsq_hip_attn_w8.h): a
+# sixteenth companion library; the ABIs above stay as they are.
+class LsqAttnW8Strides(ctypes.Structure):
+    """lsq_attn_w8_strides (include/lsq_hip_attn_w8.h): the two batch strides and the row stride of one tensor, in elements"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("s0", "s1", "ld")]
+
+
+class LsqBmmW8Geom(ctypes.Structure):
+    """lsq_bmm_w8_geom (include/lsq_hip_attn_w8.h): the extents, the form, the level dtypes and the strides of A, B and y"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B0", "B1", "M", "N", "K", "form", "a_dtype", "b_dtype")] + \
+               [(name, LsqAttnW8Strides) for name in ("a", "b", "y")]
+
+
+class LsqAttnW8Out(ctypes.Structure):
+    """lsq_attn_w8_out (include/lsq_hip_attn_w8.h): the output quantizer (or none: floats) and mid_dtype"""
+    _fields_ = [("out_scale", ctypes.c_void_p), ("out_shift", ctypes.c_void_p)] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "mid_dtype")]
+
+
+class LsqBmmW8Consts(ctypes.Structure):
+    """lsq_bmm_w8_consts (include/lsq_hip_attn_w8.h): each operand's scale and zero point on the device"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_a", "z_a", "s_b", "z_b")]
+
+
+class LsqSoftmaxW8Geom(ctypes.Structure):
+    """lsq_softmax_w8_geom (include/lsq_hip_attn_w8.h): x and y [R, C] with their row strides, and the level dtype"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("R", "C", "ldx", "ldy", "x_dtype")]
+
+
+ATTN_W8_ABI_VERSION = 1
+_BGP = ctypes.POINTER(LsqBmmW8Geom)
+_AOP = ctypes.POINTER(LsqAttnW8Out)
+_SGP = ctypes.POINTER(LsqSoftmaxW8Geom)
+C_ABI_ATTN_W8 = {
+    "lsq_attn_w8_abi_version": (_int, []),
+    "lsq_attn_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_bmm_w8": (_int, [_BGP, ctypes.POINTER(LsqBmmW8Consts), _AOP, _vp, _vp, _vp, _vp]),
+    "lsq_bmm_w8_plan": (_int, [_BGP, _int, _int, _int, _PLAN8]),
+    "lsq_softmax_w8": (_int, [_SGP, _AOP, _vp, _vp, _vp, _vp]),
+    "lsq_softmax_w8_plan": (_int, [_SGP, _int, _PLAN8]),
+}
+_ATTN_W8_LIB, attn_w8_error_str = _load_companion("liblsq_hip_attn_w8.so", C_ABI_ATTN_W8, "lsq_attn_w8_abi_version", ATTN_W8_ABI_VERSION)
+
+
+def attn_w8_library():
+    """The ctypes handle of liblsq_hip_attn_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_W8_LIB, "attn_w8", "batched matmul and softmax on 8-bit levels need", attn_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -50,12 +50,14 @@ from ._dwconv_w8_host import dwconv_w8_levels, dwconv_w8_levels_q, dwconv_w8_pla
 from ._eltwise_w8_host import (eltwise_w8_lut, eltwise_w8_mul_gate, eltwise_w8_mul_gate_q, eltwise_w8_plan_lut,  # noqa: F401
                                eltwise_w8_plan_mul)
 from ._norm_w8_host import norm_w8_layer, norm_w8_layer_q, norm_w8_plan, norm_w8_rms, norm_w8_rms_q  # noqa: F401
+from ._attn_w8_host import (attn_w8_bmm, attn_w8_bmm_q, attn_w8_plan_bmm, attn_w8_plan_softmax, attn_w8_softmax,  # noqa: F401
+                            attn_w8_softmax_q)
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -211,6 +213,19 @@ for _norm_name in ("lsq_layer_norm_w8_q8", "lsq_rms_norm_w8_q8"):
                     "int out_type_max, ScalarType mid_dtype) -> Tensor" % (_norm_name, _NORM))
     _lib_def.define("%s(%s, ScalarType out_dtype) -> Tensor" % (_norm_name, _NORM))
 del _norm_name
+#  * the attention core on 8-bit LEVELS (liblsq_hip_attn_w8.so, include/lsq_hip_attn_w8.h).  The BATCHED MATMUL: a [.., M, K] times
+#    b [.., K, N] (`transpose_b`: [.., N, K]) per batch, 2 to 4 axes, the same batch axes, each operand uint8 / int8 with one scale
+#    and zero point; the exact integer sum, (b_scale * float(I)) * a_scale, one rounding to `mid_dtype`, and the levels of the output
+#    quantizer (_q) or the floats themselves, [.., M, N] dense.  Operands whose innermost stride is 1 are read in place.  The
+#    SOFTMAX over the last axis: E = table[max - level] with `table` int32 [256] (`torchlsq.functional.lsq_softmax_table`), the
+#    exact integer sum S, float(E) * (1 / float(S)), then as above; `row_pad` pads the rows of the result's memory to a multiple of
+#    that many bytes and returns the [.., :C] view.  Not ATen's softmax: at most one level differs.  Inference only.
+_BMM = "Tensor a_levels, Tensor a_scale, Tensor a_zero, Tensor b_levels, Tensor b_scale, Tensor b_zero, bool transpose_b"
+_ATTN_OUT_Q = "Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, int out_type_max, ScalarType mid_dtype"
+_lib_def.define("lsq_bmm_w8_q8_q(%s, %s) -> Tensor" % (_BMM, _ATTN_OUT_Q))
+_lib_def.define("lsq_bmm_w8_q8(%s, ScalarType out_dtype) -> Tensor" % _BMM)
+_lib_def.define("lsq_softmax_w8_q8_q(Tensor x_levels, Tensor table, %s, int row_pad=1) -> Tensor" % _ATTN_OUT_Q)
+_lib_def.define("lsq_softmax_w8_q8(Tensor x_levels, Tensor table, ScalarType out_dtype) -> Tensor")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -947,3 +962,50 @@ for _norm_name in ("lsq_layer_norm_w8_q8", "lsq_rms_norm_w8_q8"):
     _lib_def.impl(_norm_name + "_q", _requant_no_grad(_norm_name + "_q", (1, 3, 4, 6, 7)), "Autograd")
     _lib_def.impl(_norm_name, _requant_no_grad(_norm_name, (1, 3, 4)), "Autograd")
 del _norm_name
+
+
+# -------------------------------------------------------------------------------------------------
+# the attention core on 8-bit levels (_attn_w8_host.py): GPU tensors -> liblsq_hip_attn_w8.so (one call), CPU tensors -> the
+# definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_bmm_w8_q8_q", attn_w8_bmm_q)
+    _lib_key.impl("lsq_bmm_w8_q8", attn_w8_bmm)
+    _lib_key.impl("lsq_softmax_w8_q8_q", attn_w8_softmax_q)
+    _lib_key.impl("lsq_softmax_w8_q8", attn_w8_softmax)
+del _lib_key
+
+
+def _fake_bmm_shape(a_levels, b_levels, transpose_b):
+    return tuple(a_levels.shape[:-1]) + (b_levels.shape[-2] if transpose_b else b_levels.shape[-1],)
+
+
+def _fake_bmm_w8_q(a_levels, a_scale, a_zero, b_levels, b_scale, b_zero, transpose_b, out_scale, out_shift, out_quant_min, out_quant_max,
+                   out_type_min, out_type_max, mid_dtype):
+    return torch.empty(_fake_bmm_shape(a_levels, b_levels, transpose_b), dtype=_fake_level_dtype(out_quant_max, out_type_max),
+                       device=a_levels.device)
+
+
+def _fake_bmm_w8(a_levels, a_scale, a_zero, b_levels, b_scale, b_zero, transpose_b, out_dtype):
+    return torch.empty(_fake_bmm_shape(a_levels, b_levels, transpose_b), dtype=out_dtype, device=a_levels.device)
+
+
+def _fake_softmax_w8_q(x_levels, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype, row_pad=1):
+    C = x_levels.shape[-1]
+    full = torch.empty(tuple(x_levels.shape[:-1]) + ((C + row_pad - 1) // row_pad * row_pad,),
+                       dtype=_fake_level_dtype(out_quant_max, out_type_max), device=x_levels.device)
+    return full[..., :C]
+
+
+def _fake_softmax_w8(x_levels, table, out_dtype):
+    return torch.empty(x_levels.shape, dtype=out_dtype, device=x_levels.device)
+
+
+torch.library.register_fake("torchlsq::lsq_bmm_w8_q8_q", _fake_bmm_w8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_bmm_w8_q8", _fake_bmm_w8, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_softmax_w8_q8_q", _fake_softmax_w8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_softmax_w8_q8", _fake_softmax_w8, lib=_lib_def)
+_lib_def.impl("lsq_bmm_w8_q8_q", _requant_no_grad("lsq_bmm_w8_q8_q", (1, 4, 7, 8)), "Autograd")
+_lib_def.impl("lsq_bmm_w8_q8", _requant_no_grad("lsq_bmm_w8_q8", (1, 4)), "Autograd")
+_lib_def.impl("lsq_softmax_w8_q8_q", _requant_no_grad("lsq_softmax_w8_q8_q", (2, 3)), "Autograd")
+_lib_def.impl("lsq_softmax_w8_q8", _requant_no_grad("lsq_softmax_w8_q8", ()), "Autograd")

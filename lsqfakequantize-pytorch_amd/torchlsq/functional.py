@@ -1356,3 +1356,115 @@ def lsq_rms_norm_w8(x: LevelsTensor, weight: Tensor = None, bias: Tensor = None,
                     normalized_shape=None, dim: int = -1) -> Tensor:
     """`lsq_rms_norm_w8_q` without an output quantizer: floats of `out_dtype` in x's shape and memory format.  Inference only."""
     return _norm_w8(torch.ops.torchlsq.lsq_rms_norm_w8_q8, "lsq_rms_norm_w8", x, weight, bias, eps, out_dtype, normalized_shape, dim)
+
+
+def _bmm_w8_args(what, a, b, transpose_b):
+    a, b = _levels_in(what, a), _levels_in(what, b)
+    squeeze = []
+    la, lb = a.levels, b.levels
+    if la.dim() == 1:
+        la, squeeze = la.contiguous().unsqueeze(0), squeeze + [-2]
+    if lb.dim() == 1:
+        lb = lb.contiguous().unsqueeze(0 if transpose_b else -1)
+        squeeze = squeeze + [-1]
+    assert la.dim() == lb.dim() or la.dim() == 2 or lb.dim() == 2, \
+        "%s: a and b need the same batch axes (they are not broadcast), got %s and %s" % (what, tuple(a.shape), tuple(b.shape))
+    if la.dim() < lb.dim():         # a 2-D operand beside a batched one is repeated as a view: a zero batch stride
+        la = la.expand(tuple(lb.shape[:-2]) + tuple(la.shape))
+    elif lb.dim() < la.dim():
+        lb = lb.expand(tuple(la.shape[:-2]) + tuple(lb.shape))
+    return (la, a.scale, a.zero_point, lb, b.scale, b.zero_point, bool(transpose_b)), squeeze
+
+
+def _squeeze(y, dims):
+    """drops the axes a 1-D operand added: -1 is N (b was 1-D), -2 is M (a was 1-D)"""
+    if -1 in dims:
+        y = y.squeeze(-1)
+    if -2 in dims:
+        y = y.squeeze(-1 if -1 in dims else -2)
+    return y
+
+
+def lsq_bmm_w8_q(a: LevelsTensor, b: LevelsTensor, transpose_b: bool = False, out_scale: Tensor = None, out_shift: Tensor = None,
+                 out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                 mid_dtype=torch.float32, out: Tensor = None) -> LevelsTensor:
+    """A batched matmul of two `LevelsTensor`s with an 8-bit output, one launch (liblsq_hip_attn_w8.so): a [.., M, K] times
+    b [.., K, N], or b [.., N, K] with `transpose_b` (q k^T), up to two batch axes, the same on both sides; each operand uint8 or
+    int8 with its own per-tensor constants.  I = sum_k (la - za)(lb - zb) is exact, v = (s_b * float(I)) * s_a two rounded float32
+    multiplies -- `lsq_linear_w8a8`'s steps with b in the weight's role and no bias --, one rounding to `mid_dtype`, then the
+    output quantizer's levels.  There is no alpha: the 1 / sqrt(D) of attention goes into `lsq_softmax_table` or is absorbed by
+    the scores' quantizer.  The CPU path is this definition in torch ops and the GPU equals it bit for bit.
+
+    THE OPERANDS ARE READ IN PLACE where their innermost stride is 1: a `qkv.view(B, T, 3, H, D)[:, :, i].permute(0, 2, 1, 3)` view,
+    probabilities with padded rows (`lsq_softmax_w8_q(row_pad=16)`).  On the GPU, bases and strides that are multiples of 16 run on
+    the matrix cores (K, or N of a [.., K, N] b, need not be a multiple of 16); anything else legal takes a generic kernel.  A 1-D
+    operand (taken as `torch.matmul` takes it), a view without unit innermost stride, or one whose rows overlap (an expanded or
+    sliding-window view) IS MADE DENSE FIRST.  `out`: a uint8 / int8 tensor [.., M, N] with unit innermost stride and rows that do
+    not overlap to write into, e.g. the [B, H, T, D] view of a [B, T, H D] buffer; bytes outside it are not written.  WITH `out` THE
+    CALL GOES TO THE HOST FUNCTION DIRECTLY, not through `torch.ops.torchlsq.lsq_bmm_w8_q8_q` (an op returns a fresh tensor): the same
+    checks and kernels run, but the op's fake kernel and its Autograd kernel that refuses grad do not.  Returns a `LevelsTensor` whose constants are formed on the device.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_bmm_w8_q"
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    args, squeeze = _bmm_w8_args(what, a, b, transpose_b)
+    if out is None:
+        lv = torch.ops.torchlsq.lsq_bmm_w8_q8_q(*args, *o[:6], mid_dtype)
+    else:
+        from .extension import attn_w8_bmm_q
+        assert not squeeze, "%s: `out` is not served with a 1-D operand" % what
+        lv = attn_w8_bmm_q(*args, *o[:6], mid_dtype, out=out)
+    return _levels_out(_squeeze(lv, squeeze), o[0], o[1], o[2:6])
+
+
+def lsq_bmm_w8(a: LevelsTensor, b: LevelsTensor, transpose_b: bool = False, out_dtype=torch.float32) -> Tensor:
+    """`lsq_bmm_w8_q` without an output quantizer: `round_to(out_dtype, (s_b * float(I)) * s_a)` as a floating tensor [.., M, N].
+    A 1-D operand, a view without unit innermost stride, or one whose rows overlap is made dense first.  Inference only."""
+    _assert_has_ops()
+    args, squeeze = _bmm_w8_args("lsq_bmm_w8", a, b, transpose_b)
+    return _squeeze(torch.ops.torchlsq.lsq_bmm_w8_q8(*args, out_dtype), squeeze)
+
+
+def lsq_softmax_table(x_scale: Tensor, alpha: float = 1.0) -> Tensor:
+    """The 256-entry table (int32 [256], on `x_scale`'s device) of `lsq_softmax_w8_q` for levels of a per-tensor quantizer with the
+    scale `x_scale` (a `LevelsTensor.scale`), built from existing torch ops, nothing read back.  In float64:
+
+        table[d] = int32(rint(exp(-(float64(s_x) * float64(float32(alpha))) * d) * 2^24)),   d = 0 .. 255
+
+    so table[0] = 2^24 and the entries do not increase.  `alpha` carries attention's 1 / sqrt(D).  A float64 exp may differ in its
+    last place between devices, hence an entry by 1: for equal results on two devices build the table once and move it."""
+    a = float(torch.tensor(float(alpha), dtype=torch.float32))
+    t = x_scale.detach().reshape(-1)[:1].to(torch.float64) * a
+    d = torch.arange(256, dtype=torch.float64, device=x_scale.device)
+    return torch.round(torch.exp(-t * d) * float(1 << 24)).to(torch.int32)
+
+
+def lsq_softmax_w8_q(x: LevelsTensor, table: Tensor, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                     out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None, mid_dtype=torch.float32,
+                     out: Tensor = None, row_pad: int = 1) -> LevelsTensor:
+    """Softmax over the last axis of 8-bit levels with an 8-bit output, one launch (liblsq_hip_attn_w8.so), no exp in the kernel:
+    m = max b, E_i = table[m - b_i] (`lsq_softmax_table` for x's scale), S = sum E an EXACT integer with no summation order,
+    p_i = float(E_i) * (1.0f / float(S)), one rounding to `mid_dtype`, then the output quantizer's levels.  x's scale and zero
+    point are not read: they live in the table.  The CPU path is this definition in torch ops and the GPU equals it bit for bit for
+    the same table.  IT IS NOT ATen's `softmax`: against `lsq_levels_per_tensor(F.softmax(alpha * x.dequantize()))` at most one
+    level differs.  x is read in place where its innermost stride is 1 and its rows lie one stride apart (else
+    it is made dense first).  `row_pad=16` allocates the result with rows padded to a multiple of 16 bytes and returns the
+    [.., :C] view, so that a following `lsq_bmm_w8_q` runs on the matrix cores for any C; `out`: a tensor of x's shape to write
+    into instead -- that call goes to the host function directly, not through `torch.ops.torchlsq.lsq_softmax_w8_q8_q`: the same
+    checks and kernels, without the op's fake kernel and its Autograd kernel that refuses grad.  Returns a `LevelsTensor`.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_softmax_w8_q"
+    x = _levels_in(what, x)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    if out is None:
+        lv = torch.ops.torchlsq.lsq_softmax_w8_q8_q(x.levels, table, *o[:6], mid_dtype, int(row_pad))
+    else:
+        from .extension import attn_w8_softmax_q
+        lv = attn_w8_softmax_q(x.levels, table, *o[:6], mid_dtype, 1, out=out)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float32) -> Tensor:
+    """`lsq_softmax_w8_q` without an output quantizer: the probabilities rounded once to `out_dtype`, in x's shape.
+    Inference only."""
+    _assert_has_ops()
+    return torch.ops.torchlsq.lsq_softmax_w8_q8(_levels_in("lsq_softmax_w8", x).levels, table, out_dtype)

@@ -20,6 +20,7 @@ from .modules.pool_w8 import AdaptiveAvgPool2dW8Q, AvgPool2dW8Q, MaxPool2dW8, co
 from .modules.dwconv_w8a8 import DepthwiseConv2dW8A8Q, convert_w8a8_depthwise  # noqa: F401
 from .modules.eltwise_w8 import ActivationW8Q, MulGateW8Q, convert_w8a8_eltwise  # noqa: F401
 from .modules.norm_w8 import LayerNormW8Q, RMSNormW8Q, convert_w8a8_norm  # noqa: F401
+from .modules.attn_w8 import AttentionCoreW8Q, MatmulW8Q, SoftmaxW8Q  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
@@ -120,5 +121,5 @@ __all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "PackedLinearA8
            "convert_w8a8", "LinearW8A8Q", "Conv2dW8A8Q", "convert_w8a8_q",
            "LinearW8A8AddQ", "Conv2dW8A8AddQ", "AddW8A8Q", "convert_w8a8_add_q",
            "MaxPool2dW8", "AvgPool2dW8Q", "AdaptiveAvgPool2dW8Q", "convert_w8a8_pool",
-           "DepthwiseConv2dW8A8Q", "convert_w8a8_depthwise", "LayerNormW8Q", "RMSNormW8Q", "convert_w8a8_norm",
+           "DepthwiseConv2dW8A8Q", "convert_w8a8_depthwise", "LayerNormW8Q", "RMSNormW8Q", "convert_w8a8_norm", "AttentionCoreW8Q", "MatmulW8Q", "SoftmaxW8Q",
            "enable_rank_sync", "prepare_ddp"] + [row[0] for row in _TABLE]

@@ -1,0 +1,127 @@
+"""Modules that keep the attention core of a converted token block in 8-bit LEVELS: `MatmulW8Q` (where a block calls a
+`FloatFunctional.matmul`), `SoftmaxW8Q` (which builds and owns the integer table) and `AttentionCoreW8Q` (softmax(q k^T) v in three
+launches) -- `torchlsq.functional.lsq_bmm_w8_q` / `lsq_softmax_w8_q`, liblsq_hip_attn_w8.so on the GPU.  The forwards take
+`LevelsTensor`s; nothing is read back to the host, and the chain can be captured in a graph.  There is no converter: attention
+blocks differ too much in how they spell the core, so a block is rewritten by hand around these modules.
+
+The softmax is the package's own definition (include/lsq_hip_attn_w8.h), not ATen's: against the unfused
+`dequantize -> F.softmax -> levels` at most one level differs.
+"""
+import torch
+from torch import nn
+
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_bmm_w8, lsq_bmm_w8_q, lsq_softmax_table, lsq_softmax_w8,
+                                 lsq_softmax_w8_q)
+from .packed_linear_a8 import _per_tensor_constants
+from .w8a8_q import _MID_DTYPES, _as_levels
+
+
+def _mid(mid_dtype):
+    assert mid_dtype in _MID_DTYPES.values(), "mid_dtype must be torch.float32, torch.bfloat16 or torch.float16"
+    return mid_dtype
+
+
+class _OutQ(nn.Module):
+    """buffers `<name>_scale` and `<name>_shift` (float32 [1]) and the range of one trained per-tensor output quantizer, or none"""
+
+    def _set_out(self, name, quantizer, what):
+        if quantizer is None:
+            setattr(self, name + "_range", None)
+            self.register_buffer(name + "_scale", torch.ones(1, dtype=torch.float32))
+            self.register_buffer(name + "_shift", torch.zeros(1, dtype=torch.float32))
+            return
+        scale, shift, *rng = _per_tensor_constants(quantizer, "%s (%s quantizer)" % (what, name))
+        self.register_buffer(name + "_scale", scale)
+        self.register_buffer(name + "_shift", shift)
+        setattr(self, name + "_range", tuple(rng))
+
+    def _out(self, name):
+        return (getattr(self, name + "_scale"), getattr(self, name + "_shift")) + getattr(self, name + "_range")
+
+
+def _levels(what, *xs):
+    xs = tuple(_as_levels(x) for x in xs)
+    assert all(isinstance(x, LevelsTensor) for x in xs), "%s reads levels: LevelsTensors or per-tensor quantized tensors" % what
+    return xs
+
+
+class MatmulW8Q(_OutQ):
+    """`torch.matmul(a, b)` (`transpose_b`: of a and b^T) on two `LevelsTensor`s: one launch, a `LevelsTensor` of
+    `output_quantizer` (a trained per-tensor `LSQFakeQuantizer`; None: floats of `mid_dtype`).  Inference only."""
+
+    def __init__(self, output_quantizer=None, transpose_b=False, mid_dtype=torch.float32):
+        super().__init__()
+        self.transpose_b, self.mid_dtype = bool(transpose_b), _mid(mid_dtype)
+        self._set_out("output", output_quantizer, "MatmulW8Q")
+
+    def forward(self, a, b, out=None):
+        a, b = _levels("MatmulW8Q", a, b)
+        if self.output_range is None:
+            return lsq_bmm_w8(a, b, self.transpose_b, self.mid_dtype)
+        return lsq_bmm_w8_q(a, b, self.transpose_b, *self._out("output"), self.mid_dtype, out=out)
+
+    matmul = forward
+
+    def extra_repr(self):
+        return "transpose_b=%s, %s, mid_dtype=%s" % (self.transpose_b, "output levels %d..%d" % self.output_range[:2]
+                                                     if self.output_range else "floats out", str(self.mid_dtype).replace("torch.", ""))
+
+
+class SoftmaxW8Q(_OutQ):
+    """Softmax over the last axis of a `LevelsTensor` of `input_quantizer` (a trained per-tensor `LSQFakeQuantizer`, or the float32
+    [1] scale of the incoming `LevelsTensor`): builds `lsq_softmax_table(s_x, alpha)` once, on the quantizer's device, and owns it
+    as the buffer `table` (int32 [256]).  `alpha` carries attention's 1 / sqrt(D).  Returns a `LevelsTensor` of `output_quantizer`
+    (None: floats of `mid_dtype`); `row_pad` as in `lsq_softmax_w8_q`.  Inference only."""
+
+    def __init__(self, input_quantizer, output_quantizer=None, alpha=1.0, mid_dtype=torch.float32, row_pad=16):
+        super().__init__()
+        self.alpha, self.mid_dtype, self.row_pad = float(alpha), _mid(mid_dtype), int(row_pad)
+        if isinstance(input_quantizer, torch.Tensor):
+            s_x = input_quantizer.detach().reshape(-1)[:1].to(torch.float32)
+        else:
+            scale, shift, _, _, tmin, tmax = _per_tensor_constants(input_quantizer, "SoftmaxW8Q (input quantizer)")
+            s_x = _act_constants(scale, shift, tmin, tmax)[0]
+        self.register_buffer("table", lsq_softmax_table(s_x, self.alpha))
+        self._set_out("output", output_quantizer, "SoftmaxW8Q")
+
+    def forward(self, x, out=None):
+        x, = _levels("SoftmaxW8Q", x)
+        if self.output_range is None:
+            return lsq_softmax_w8(x, self.table, self.mid_dtype)
+        return lsq_softmax_w8_q(x, self.table, *self._out("output"), self.mid_dtype, out=out, row_pad=self.row_pad)
+
+    def extra_repr(self):
+        return "alpha=%g, %s, mid_dtype=%s" % (self.alpha, "output levels %d..%d" % self.output_range[:2] if self.output_range
+                                               else "floats out", str(self.mid_dtype).replace("torch.", ""))
+
+
+class AttentionCoreW8Q(nn.Module):
+    """softmax(alpha q k^T) v on levels: q, k, v `LevelsTensor`s [B, H, T, D] (views of one qkv buffer are read in place) -> a
+    `LevelsTensor` [B, T, H D] of `out_quantizer`, in three launches: the scores q k^T as levels of `scores_quantizer`, their
+    softmax through the table of (`scores_quantizer`'s scale, `alpha`) as levels of `probs_quantizer` in rows padded to 16
+    bytes, and p v written through the [B, H, T, D] view of the result.  The three quantizers are trained per-tensor
+    `LSQFakeQuantizer`s.  The two matmuls write into buffers this module allocates (`out=`), so they call the host functions
+    directly and not `torch.ops.torchlsq.lsq_bmm_w8_q8_q`: the same checks and kernels run, graph capture works, but the ops' fake
+    kernels and their Autograd kernels that refuse grad do not cover the core; the softmax goes through its op.  Inference only."""
+
+    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32):
+        super().__init__()
+        self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
+        self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16)
+        self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
+        assert None not in (self.scores.output_range, self.softmax.output_range, self.context.output_range), \
+            "AttentionCoreW8Q needs the three trained quantizers"
+
+    def forward(self, q, k, v):
+        q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        assert q.levels.dim() == 4 and q.shape == k.shape == v.shape, \
+            "AttentionCoreW8Q needs q, k and v of one shape [B, H, T, D], got %s, %s and %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape))
+        B, H, T, D = (int(n) for n in q.shape)
+        # the scores' rows are padded to 16 bytes like the probabilities': both are then stored and read as packets for any T
+        rng = self.scores.output_range
+        scores = torch.empty((B, H, T, (T + 15) // 16 * 16), dtype=torch.uint8 if max(rng[1], rng[3]) > 127 else torch.int8, device=q.device)
+        p = self.softmax(self.scores(q, k, out=scores[..., :T]))
+        rng = self.context.output_range
+        buf = torch.empty((B, T, H * D), dtype=torch.uint8 if max(rng[1], rng[3]) > 127 else torch.int8, device=q.device)
+        y = self.context(p, v, out=buf.view(B, T, H, D).permute(0, 2, 1, 3))
+        return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
