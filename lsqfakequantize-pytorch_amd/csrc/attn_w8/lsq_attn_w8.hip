@@ -25,6 +25,8 @@
 #include "../lsq_kernels.hpp"
 #include "../lsq_companion_abi.hpp"
 #include "../qlinear_w8/lsq_w8_shared.hpp"
+#include "lsq_attn_w8_dev.hpp"
+#include "lsq_attn_w8_checks.hpp"
 #include "../../../include/lsq_hip_attn_w8.h"
 
 namespace lsq {
@@ -40,54 +42,11 @@ constexpr int kSmxRows = 4;                     // rows a group walks where the 
 constexpr int64_t kSmxFill = 512;               // ... that is: at least this many workgroups
 static_assert(kBlock == 256, "four waves per workgroup");
 
-struct AttnOut {            // kernel argument: the output side
-    const float* scale;     // NULL: a floating y
-    const float* shift;
-    float qmin, qmax, tmin, tmax;
-    int mid;
-};
-
-struct AttnQ {
-    QParams<float> qp;
-    Range<float> r;
-    int levels_out, mid;
-};
-
-__device__ __forceinline__ AttnQ attn_constants(const AttnOut& o) {
-    AttnQ q;
-    q.r = Range<float>{o.qmin, o.qmax, o.tmin, o.tmax};
-    q.levels_out = o.scale != nullptr;
-    if (q.levels_out) q.qp = make_qparams<float>(sanitize_scale_per_tensor<float>(o.scale[0]), o.shift[0], q.r);
-    else q.qp = QParams<float>{1.0f, 1.0f, 0.0f};
-    q.mid = o.mid;
-    return q;
-}
-
-// both roundings are formed and one is selected: no branch in the epilogue
-__device__ __forceinline__ float attn_round_mid(float v, int mid) {
-    const float b = static_cast<float>(io_bf16::to_elem(v)), h = static_cast<float>(io_f16::to_elem(v));
-    return mid == LSQ_BF16 ? b : (mid == LSQ_F16 ? h : v);
-}
-
-__device__ __forceinline__ uint32_t attn_byte(float u, const AttnQ& q) {
-    return static_cast<uint32_t>(static_cast<int>(level<float>(u, q.qp, q.r)) & 0xff);
-}
-
 // u (a value of mid) as element `at` of a floating y
 __device__ __forceinline__ void attn_store_float(void* y, int64_t at, float u, int mid) {
     if (mid == LSQ_F32) static_cast<float*>(y)[at] = u;
     else if (mid == LSQ_BF16) static_cast<__bf16*>(y)[at] = io_bf16::passthrough(u);
     else static_cast<_Float16*>(y)[at] = static_cast<_Float16>(u);
-}
-
-// the packet's bytes from `valid` on become 0 (valid >= 16: none)
-__device__ __forceinline__ u32x4 attn_mask_tail(u32x4 v, int valid) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = min(max(valid - 4 * i, 0), 4);
-        v[i] &= n >= 4 ? 0xffffffffu : ((1u << (8 * n)) - 1u);
-    }
-    return v;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -107,32 +66,6 @@ struct BmmArg {             // kernel argument
     int off_a, off_b;       // 128: uint8 levels (the byte ^ 0x80 read as int8 is the level - 128); 0: int8
     int y_packets;          // levels out: y's base and strides are multiples of 16
 };
-
-// the fp32 steps of the contract on the exact integer, and the rounding to mid
-__device__ __forceinline__ float bmm_value(float fI, float s_a, float s_b, int mid) {
-    return attn_round_mid(__fmul_rn(__fmul_rn(s_b, fI), s_a), mid);
-}
-
-__device__ __forceinline__ float bmm_value(int64_t I, float s_a, float s_b, int mid) { return bmm_value(static_cast<float>(I), s_a, s_b, mid); }
-
-// I from the raw sums, P = sum a b, C = sum_k b, S = sum_k a, as w8_exact forms it -- but with 64-bit zero points and in wrapping
-// unsigned arithmetic: exact wherever I fits 64 bits (every zero point within -32768..32767), no signed overflow anywhere
-__device__ __forceinline__ int64_t bmm_exact(int64_t P, int64_t C, int64_t S, int64_t K, int64_t z_a, int64_t z_b) {
-    const uint64_t za = static_cast<uint64_t>(z_a), zb = static_cast<uint64_t>(z_b);
-    return static_cast<int64_t>(static_cast<uint64_t>(P) - za * static_cast<uint64_t>(C) - zb * static_cast<uint64_t>(S) +
-                                static_cast<uint64_t>(K) * za * zb);
-}
-
-// the 4 x 4 block of bytes of four words transposed: c[k] = byte k of each word, in their order
-__device__ __forceinline__ void attn_transpose4(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t (&c)[4]) {
-    // __builtin_amdgcn_perm(hi, lo, sel): selector bytes 0..3 take lo's bytes, 4..7 hi's
-    const uint32_t lo01 = __builtin_amdgcn_perm(x1, x0, 0x05010400u), hi01 = __builtin_amdgcn_perm(x1, x0, 0x07030602u);
-    const uint32_t lo23 = __builtin_amdgcn_perm(x3, x2, 0x05010400u), hi23 = __builtin_amdgcn_perm(x3, x2, 0x07030602u);
-    c[0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
-    c[1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
-    c[2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
-    c[3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
-}
 
 template <bool NN>
 __global__ __launch_bounds__(kBlock) void bmm_w8_mfma_kernel(BmmGeom g, BmmArg a, AttnOut o, const uint8_t* __restrict__ A,
@@ -212,6 +145,8 @@ __global__ __launch_bounds__(kBlock) void bmm_w8_mfma_kernel(BmmGeom g, BmmArg a
     if constexpr (NN) __syncthreads();                  // the last step's reads of LDS are done
     // |I| <= K max|la - za| max|lb - zb|: where that stays below 2^31 (every K up to 32768 with zero points inside the level
     // ranges) the four terms are summed in 32 wrapping bits and converted with one instruction; the value is the same integer
+    // (lsq_attn_w8_dev.hpp's bmm_int_constants / bmm_int_float state the same selection for the fused kernel; called from here they
+    // change this kernel's register allocation and compare senses, so it keeps its own text: profiles/r24_attn_w8_shared_isa_diff.txt)
     const int64_t reach_a = max(z_a + 128, 127 - z_a), reach_b = max(z_b + 128, 127 - z_b);        // max |a - z| over a in -128..127
     const bool narrow = reach_a < 65536 && reach_b < 65536 && g.K * reach_a * reach_b < (int64_t{1} << 31);
     const uint32_t kzz = static_cast<uint32_t>(g.K) * static_cast<uint32_t>(z_a) * static_cast<uint32_t>(z_b);
@@ -287,13 +222,6 @@ struct SmxGeom {            // kernel argument
     int C, packets, K;      // elements of a row, ceil(C / 16), rows per group
     uint32_t flip;          // 0x80808080 for int8 levels (biased by 128 on load), 0 for uint8
 };
-
-__device__ __forceinline__ uint64_t smx_shfl_xor_u64(uint64_t v, int mask) {
-    return static_cast<uint64_t>(w8_shfl_xor_i64(static_cast<int64_t>(v), mask));
-}
-
-// p of the contract rounded to mid: float(E) is exact (E <= 2^24)
-__device__ __forceinline__ float smx_value(int E, float r, int mid) { return attn_round_mid(__fmul_rn(static_cast<float>(E), r), mid); }
 
 // a packet of outputs, the first `cnt` of them stored: `at` in elements of y; y 16-byte aligned, at % 16 == 0
 __device__ __forceinline__ void smx_store16(void* y, int64_t at, const float (&u)[16], int cnt, const AttnQ& q) {
@@ -508,46 +436,6 @@ inline SmxKernel packets_kernel(int L, int P) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-typedef long long ll;
-
-bool level_dtype(int64_t code) { return code == LSQ_ATTN_W8_U8 || code == LSQ_ATTN_W8_I8; }
-bool float_dtype(int64_t code) { return code == LSQ_F32 || code == LSQ_BF16 || code == LSQ_F16; }
-
-bool overlap(const void* p, int64_t p_bytes, const void* r, int64_t r_bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(r);
-    return a < b + static_cast<uintptr_t>(r_bytes) && b < a + static_cast<uintptr_t>(p_bytes);
-}
-
-// elements from the first to one past the last of a [B0, B1, rows, cols] tensor
-int64_t span_of(const lsq_attn_w8_strides& s, int64_t B0, int64_t B1, int64_t rows, int64_t cols) {
-    return (B0 - 1) * s.s0 + (B1 - 1) * s.s1 + (rows - 1) * s.ld + cols;
-}
-
-int check_strides(const char* what, const char* name, const lsq_attn_w8_strides& s, int64_t cols) {
-    if (s.ld < cols) return fail(LSQ_EINVAL, "%s: %s's row stride %lld is smaller than its row of %lld", what, name, static_cast<ll>(s.ld), static_cast<ll>(cols));
-    if (s.s0 < 0 || s.s1 < 0)
-        return fail(LSQ_EINVAL, "%s: %s's batch strides (%lld, %lld) must not be negative", what, name, static_cast<ll>(s.s0), static_cast<ll>(s.s1));
-    return LSQ_OK;
-}
-
-// y's rows and batches must not overlap each other: the strides sorted, each must clear the span of those below it
-bool self_overlap(const lsq_attn_w8_strides& s, int64_t B0, int64_t B1, int64_t rows, int64_t cols) {
-    int64_t st[3] = {s.s0, s.s1, s.ld}, ex[3] = {B0, B1, rows};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (st[j] < st[i]) {
-                std::swap(st[i], st[j]);
-                std::swap(ex[i], ex[j]);
-            }
-    int64_t span = cols;
-    for (int i = 0; i < 3; ++i) {
-        if (ex[i] == 1) continue;
-        if (st[i] < span) return true;
-        span += (ex[i] - 1) * st[i];
-    }
-    return false;
-}
-
 int check_bmm_geom(const char* what, const lsq_bmm_w8_geom* g) {
     if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
     if (g->form != LSQ_ATTN_W8_NN && g->form != LSQ_ATTN_W8_NT)
@@ -572,37 +460,6 @@ int check_bmm_geom(const char* what, const lsq_bmm_w8_geom* g) {
         return fail(LSQ_EINVAL, "%s: y's rows or batches overlap each other (strides %lld, %lld, %lld for [%lld, %lld, %lld, %lld])", what,
                     static_cast<ll>(g->y.s0), static_cast<ll>(g->y.s1), static_cast<ll>(g->y.ld), static_cast<ll>(g->B0),
                     static_cast<ll>(g->B1), static_cast<ll>(g->M), static_cast<ll>(g->N));
-    return LSQ_OK;
-}
-
-constexpr int64_t kMaxGrid = (int64_t{1} << 24) - 1;
-
-int check_grid(const char* what, int64_t grid) {
-    // 256 threads a workgroup: the whole launch stays below 2^32 threads, which every HIP runtime accepts
-    if (grid > kMaxGrid) return fail(LSQ_EINVAL, "%s: %lld workgroups are beyond 2^24 - 1", what, static_cast<ll>(grid));
-    return LSQ_OK;
-}
-
-// the output side; the bytes of one element of y into `y_elem`
-int check_out(const char* what, const lsq_attn_w8_out* c, lsq::AttnOut& arg, int64_t& y_elem) {
-    if (!c) return fail(LSQ_EINVAL, "%s: NULL output description", what);
-    if (!float_dtype(c->mid_dtype))
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(c->mid_dtype));
-    if ((c->out_scale == nullptr) != (c->out_shift == nullptr))
-        return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift: they come together", what);
-    if (c->out_scale && (!aligned_to(c->out_scale, 4) || !aligned_to(c->out_shift, 4)))
-        return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
-    if (c->out_scale) {
-        const ll lo = std::min(c->quant_min, c->type_min), hi = std::max(c->quant_max, c->type_max);
-        if (c->quant_min > c->quant_max || c->type_min > c->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-            return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                        "lie within 0..255 or within -128..127", what, static_cast<ll>(c->quant_min), static_cast<ll>(c->quant_max),
-                        static_cast<ll>(c->type_min), static_cast<ll>(c->type_max));
-    }
-    y_elem = c->out_scale ? 1 : static_cast<int64_t>(elem_bytes(static_cast<int>(c->mid_dtype)));
-    arg = lsq::AttnOut{static_cast<const float*>(c->out_scale), static_cast<const float*>(c->out_shift), static_cast<float>(c->quant_min),
-                       static_cast<float>(c->quant_max), static_cast<float>(c->type_min), static_cast<float>(c->type_max),
-                       static_cast<int>(c->mid_dtype)};
     return LSQ_OK;
 }
 

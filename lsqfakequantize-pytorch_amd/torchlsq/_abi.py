@@ -597,6 +597,37 @@ def attn_w8_library():
     return _require_companion(_ATTN_W8_LIB, "attn_w8", "batched matmul and softmax on 8-bit levels need", attn_w8_error_str)
 
 
+# The attention core on 8-bit levels in one launch, scores and probabilities in LDS (include/lsq_hip_attn_fused_w8.h): a seventeenth
+# companion library; the ABIs above stay as they are.
+class LsqAttnFusedW8Geom(ctypes.Structure):
+    """lsq_attn_fused_w8_geom (include/lsq_hip_attn_fused_w8.h): the extents, the level dtypes and the strides of q, k, v and y"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "H", "Tq", "Tk", "D", "q_dtype", "k_dtype", "v_dtype")] + \
+               [(name, LsqAttnW8Strides) for name in ("q", "k", "v", "y")]
+
+
+class LsqAttnFusedW8Consts(ctypes.Structure):
+    """lsq_attn_fused_w8_consts (include/lsq_hip_attn_fused_w8.h): the scale and zero point of q, k, v and of the probabilities as an
+    operand, on the device"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_q", "z_q", "s_k", "z_k", "s_v", "z_v", "s_p", "z_p")]
+
+
+ATTN_FUSED_W8_ABI_VERSION = 1
+_AFGP = ctypes.POINTER(LsqAttnFusedW8Geom)
+C_ABI_ATTN_FUSED_W8 = {
+    "lsq_attn_fused_w8_abi_version": (_int, []),
+    "lsq_attn_fused_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_attn_fused_w8": (_int, [_AFGP, ctypes.POINTER(LsqAttnFusedW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_attn_fused_w8_plan": (_int, [_AFGP, _int, _int, _PLAN8]),
+}
+_ATTN_FUSED_W8_LIB, attn_fused_w8_error_str = _load_companion("liblsq_hip_attn_fused_w8.so", C_ABI_ATTN_FUSED_W8,
+                                                              "lsq_attn_fused_w8_abi_version", ATTN_FUSED_W8_ABI_VERSION)
+
+
+def attn_fused_w8_library():
+    """The ctypes handle of liblsq_hip_attn_fused_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_FUSED_W8_LIB, "attn_fused_w8", "the fused attention core on 8-bit levels needs", attn_fused_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

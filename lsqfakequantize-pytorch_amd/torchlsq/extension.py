@@ -52,12 +52,13 @@ from ._eltwise_w8_host import (eltwise_w8_lut, eltwise_w8_mul_gate, eltwise_w8_m
 from ._norm_w8_host import norm_w8_layer, norm_w8_layer_q, norm_w8_plan, norm_w8_rms, norm_w8_rms_q  # noqa: F401
 from ._attn_w8_host import (attn_w8_bmm, attn_w8_bmm_q, attn_w8_plan_bmm, attn_w8_plan_softmax, attn_w8_softmax,  # noqa: F401
                             attn_w8_softmax_q)
+from ._attn_fused_w8_host import attn_fused_w8_plan, attn_fused_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -226,6 +227,15 @@ _lib_def.define("lsq_bmm_w8_q8_q(%s, %s) -> Tensor" % (_BMM, _ATTN_OUT_Q))
 _lib_def.define("lsq_bmm_w8_q8(%s, ScalarType out_dtype) -> Tensor" % _BMM)
 _lib_def.define("lsq_softmax_w8_q8_q(Tensor x_levels, Tensor table, %s, int row_pad=1) -> Tensor" % _ATTN_OUT_Q)
 _lib_def.define("lsq_softmax_w8_q8(Tensor x_levels, Tensor table, ScalarType out_dtype) -> Tensor")
+#  * the same attention core in ONE launch (liblsq_hip_attn_fused_w8.so, include/lsq_hip_attn_fused_w8.h): q [B, H, Tq, D], k and v
+#    [B, H, Tk, D] levels with one scale and zero point each, the softmax's `table`, and the three output quantizers (the scores', the
+#    probabilities', the context's) -> the context's levels [B, Tq, H D].  Byte for byte lsq_bmm_w8_q8_q (q k^T), lsq_softmax_w8_q8_q,
+#    lsq_bmm_w8_q8_q (p v) composed; the scores and probabilities stay in LDS where the fused kernel serves the shape, every other
+#    legal input runs the three launches.  Inference only.
+_ATTN_SIDE = "Tensor %s_scale, Tensor %s_shift, int %s_quant_min, int %s_quant_max, int %s_type_min, int %s_type_max"
+_lib_def.define("lsq_attention_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, Tensor k_zero, "
+                "Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype) -> Tensor"
+                % tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1009,3 +1019,25 @@ _lib_def.impl("lsq_bmm_w8_q8_q", _requant_no_grad("lsq_bmm_w8_q8_q", (1, 4, 7, 8
 _lib_def.impl("lsq_bmm_w8_q8", _requant_no_grad("lsq_bmm_w8_q8", (1, 4)), "Autograd")
 _lib_def.impl("lsq_softmax_w8_q8_q", _requant_no_grad("lsq_softmax_w8_q8_q", (2, 3)), "Autograd")
 _lib_def.impl("lsq_softmax_w8_q8", _requant_no_grad("lsq_softmax_w8_q8", ()), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the attention core on 8-bit levels in one launch (_attn_fused_w8_host.py): GPU tensors -> liblsq_hip_attn_fused_w8.so (one call; the
+# three launches of liblsq_hip_attn_w8.so where the fused kernel does not serve the shape), CPU tensors -> the three CPU paths
+# composed; a shape-only kernel.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_attention_w8_q8_q", attn_fused_w8_q)
+del _lib_key
+
+
+def _fake_attention_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table, scores_scale, scores_shift,
+                         scores_quant_min, scores_quant_max, scores_type_min, scores_type_max, probs_scale, probs_shift, probs_quant_min,
+                         probs_quant_max, probs_type_min, probs_type_max, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
+                         out_type_max, mid_dtype):
+    B, H, Tq, D = q_levels.shape
+    return torch.empty((B, Tq, H * D), dtype=_fake_level_dtype(out_quant_max, out_type_max), device=q_levels.device)
+
+
+torch.library.register_fake("torchlsq::lsq_attention_w8_q8_q", _fake_attention_w8_q, lib=_lib_def)
+_lib_def.impl("lsq_attention_w8_q8_q", _requant_no_grad("lsq_attention_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")

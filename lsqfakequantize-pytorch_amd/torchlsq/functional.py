@@ -1463,6 +1463,34 @@ def lsq_softmax_w8_q(x: LevelsTensor, table: Tensor, out_scale: Tensor = None, o
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 
+def lsq_attention_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor, table: Tensor, scores_out, probs_out, out,
+                       mid_dtype=torch.float32) -> LevelsTensor:
+    """The attention core softmax(q k^T) v on 8-bit levels with an 8-bit output IN ONE LAUNCH (liblsq_hip_attn_fused_w8.so): q
+    [B, H, Tq, D], k and v [B, H, Tk, D] `LevelsTensor`s (views of one qkv buffer are read in place), `table` the softmax's
+    (`lsq_softmax_table` of the scores' scale and alpha), and the three output sides `scores_out`, `probs_out`, `out`, each the
+    6-tuple (scale, shift, quant_min, quant_max, type_min, type_max) of a per-tensor quantizer as `MatmulW8Q._out()` yields it.
+    There is no new arithmetic: the result is, byte for byte,
+
+        s = lsq_bmm_w8_q(q, k, True, *scores_out, mid_dtype);  p = lsq_softmax_w8_q(s, table, *probs_out, mid_dtype)
+        y = lsq_bmm_w8_q(p, v, False, *out, mid_dtype, out=<the [B, H, Tq, D] view of a [B, Tq, H D] buffer>)
+
+    returned as a `LevelsTensor` [B, Tq, H D] of `out`'s quantizer.  On the GPU the scores and probabilities are bytes in LDS and
+    never reach memory where q, k, v have 16-byte aligned bases and strides that are multiples of 16, D % 16 == 0, 16 <= D <= 128 and
+    Tk <= 2048 (`torchlsq.extension.attn_fused_w8_plan` says which); every other input the three ops serve runs those three
+    launches.  The CPU path is the composition above and the GPU equals it bit for bit.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_attention_w8_q"
+    q, k, v = _levels_in(what, q), _levels_in(what, k), _levels_in(what, v)
+    sides = []
+    for name, side in (("scores_out", scores_out), ("probs_out", probs_out), ("out", out)):
+        assert side is not None and len(side) == 6, "%s: %s must be (scale, shift, quant_min, quant_max, type_min, type_max)" % (what, name)
+        sides.append(_out_args("%s (%s)" % (what, name), *side, False))
+    lv = torch.ops.torchlsq.lsq_attention_w8_q8_q(q.levels, q.scale, q.zero_point, k.levels, k.scale, k.zero_point, v.levels, v.scale,
+                                                  v.zero_point, table, *sides[0][:6], *sides[1][:6], *sides[2][:6], mid_dtype)
+    o = sides[2]
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
 def lsq_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float32) -> Tensor:
     """`lsq_softmax_w8_q` without an output quantizer: the probabilities rounded once to `out_dtype`, in x's shape.
     Inference only."""

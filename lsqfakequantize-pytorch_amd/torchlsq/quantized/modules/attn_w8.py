@@ -1,6 +1,7 @@
 """Modules that keep the attention core of a converted token block in 8-bit LEVELS: `MatmulW8Q` (where a block calls a
 `FloatFunctional.matmul`), `SoftmaxW8Q` (which builds and owns the integer table) and `AttentionCoreW8Q` (softmax(q k^T) v in three
-launches) -- `torchlsq.functional.lsq_bmm_w8_q` / `lsq_softmax_w8_q`, liblsq_hip_attn_w8.so on the GPU.  The forwards take
+launches, or with `fused=True` in one: `lsq_attention_w8_q`, liblsq_hip_attn_fused_w8.so) -- `torchlsq.functional.lsq_bmm_w8_q` /
+`lsq_softmax_w8_q`, liblsq_hip_attn_w8.so on the GPU.  The forwards take
 `LevelsTensor`s; nothing is read back to the host, and the chain can be captured in a graph.  There is no converter: attention
 blocks differ too much in how they spell the core, so a block is rewritten by hand around these modules.
 
@@ -10,8 +11,8 @@ The softmax is the package's own definition (include/lsq_hip_attn_w8.h), not ATe
 import torch
 from torch import nn
 
-from torchlsq.functional import (LevelsTensor, _act_constants, lsq_bmm_w8, lsq_bmm_w8_q, lsq_softmax_table, lsq_softmax_w8,
-                                 lsq_softmax_w8_q)
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q, lsq_softmax_table,
+                                 lsq_softmax_w8, lsq_softmax_w8_q)
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import _MID_DTYPES, _as_levels
 
@@ -102,10 +103,16 @@ class AttentionCoreW8Q(nn.Module):
     bytes, and p v written through the [B, H, T, D] view of the result.  The three quantizers are trained per-tensor
     `LSQFakeQuantizer`s.  The two matmuls write into buffers this module allocates (`out=`), so they call the host functions
     directly and not `torch.ops.torchlsq.lsq_bmm_w8_q8_q`: the same checks and kernels run, graph capture works, but the ops' fake
-    kernels and their Autograd kernels that refuse grad do not cover the core; the softmax goes through its op.  Inference only."""
+    kernels and their Autograd kernels that refuse grad do not cover the core; the softmax goes through its op.
 
-    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32):
+    `fused=True` (opt-in; an attribute, not a buffer: the `state_dict` is the same) sends the same constants and the same table
+    through `torchlsq.functional.lsq_attention_w8_q` instead: ONE launch where liblsq_hip_attn_fused_w8.so serves the shape (the scores
+    and probabilities stay in LDS), the three launches elsewhere -- the same bytes either way, and q and k, v may differ in T.
+    Inference only."""
+
+    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False):
         super().__init__()
+        self.fused = bool(fused)
         self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
         self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16)
         self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
@@ -114,6 +121,9 @@ class AttentionCoreW8Q(nn.Module):
 
     def forward(self, q, k, v):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        if self.fused:
+            return lsq_attention_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
+                                      self.context._out("output"), self.scores.mid_dtype)
         assert q.levels.dim() == 4 and q.shape == k.shape == v.shape, \
             "AttentionCoreW8Q needs q, k and v of one shape [B, H, T, D], got %s, %s and %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape))
         B, H, T, D = (int(n) for n in q.shape)
@@ -125,3 +135,7 @@ class AttentionCoreW8Q(nn.Module):
         buf = torch.empty((B, T, H * D), dtype=torch.uint8 if max(rng[1], rng[3]) > 127 else torch.int8, device=q.device)
         y = self.context(p, v, out=buf.view(B, T, H, D).permute(0, 2, 1, 3))
         return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
+
+    def extra_repr(self):
+        return "fused=%s (%s)" % (self.fused, "lsq_attention_w8_q: one launch where the fused kernel serves the shape" if self.fused
+                                  else "three launches")
