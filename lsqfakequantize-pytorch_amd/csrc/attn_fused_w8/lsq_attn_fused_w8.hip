@@ -5,10 +5,10 @@
 // and probability rows in LDS are wave-private and no workgroup barrier stands between the phases.
 //  1 SCORES   the wave's q packets (one u32x4 per lane per 64 of D) stay in registers; per 16-key sub-tile k's rows are the MFMA B
 //             operand straight from memory (v_mfma_i32_16x16x64_i8), sum q and sum k come from the all-ones MFMAs in the
-//             accumulator's layout; I, bmm_value and attn_byte as in bmm_w8_mfma_kernel; the score BYTE goes into LDS [64][ld].
+//             accumulator's layout; I, bmm_value and w8o_byte as in bmm_w8_mfma_kernel; the score BYTE goes into LDS [64][ld].
 //  2 SOFTMAX  in place: a row in the registers of a group of L lanes (a second packet per lane above 1024 keys only), the byte max, E = table[m - b]
 //             from the 1 KB copy of the table in LDS, a 32-bit partial per lane (at most 32 entries of 2^24) widened to 64 bits
-//             before it crosses lanes, one __fdiv_rn, smx_value, attn_byte of the probabilities' quantizer.  Columns >= Tk take no
+//             before it crosses lanes, one __fdiv_rn, smx_value, w8o_byte of the probabilities' quantizer.  Columns >= Tk take no
 //             part; what the last packet holds beyond Tk is masked where phase 3 reads it (LDS is not zeroed between workgroups).
 //  3 CONTEXT  NN with K = Tk, N = D: A packets from the wave's LDS rows (ds_read_b128), v[b, h] staged per 64-key step through LDS
 //             transposed into [D][80] (attn_transpose4), shared by the four waves -- the kernel's only barriers besides the one
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void attn_fused_w8_kernel(FusedGeom g, Fuse
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float u = bmm_value(bmm_int_float(ex, P[i], Cs[i], Rs[i]), s_q, s_k, sq.mid);
-                sc[(wave * 16 + 4 * q + i) * g.ld + 16 * j + nl] = static_cast<unsigned char>(attn_byte(u, sq));
+                sc[(wave * 16 + 4 * q + i) * g.ld + 16 * j + nl] = static_cast<unsigned char>(w8o_byte(u, sq));
             }
             cur[0] = nxt[0];
             cur[1] = nxt[1];
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void attn_fused_w8_kernel(FusedGeom g, Fuse
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int b = static_cast<int>((v[jj][i / 4] >> (8 * (i % 4))) & 0xffu);
-                    w[i / 4] |= attn_byte(smx_value(tab[(m - b) & 0xff], r, pq.mid), pq) << (8 * (i % 4));
+                    w[i / 4] |= w8o_byte(smx_value(tab[(m - b) & 0xff], r, pq.mid), pq) << (8 * (i % 4));
                 }
                 if (p < nsub) *reinterpret_cast<u32x4*>(row + 16 * p) = u32x4{w[0], w[1], w[2], w[3]};
             }
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void attn_fused_w8_kernel(FusedGeom g, Fuse
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float u = bmm_value(bmm_int_float(ex, P[j][i], Cs[j][i], Rs[i]), s_p, s_v, oq.mid);
-                stage[(wave * 16 + 4 * q + i) * g.D + 16 * j + nl] = static_cast<unsigned char>(attn_byte(u, oq));
+                stage[(wave * 16 + 4 * q + i) * g.D + 16 * j + nl] = static_cast<unsigned char>(w8o_byte(u, oq));
             }
         }
     }
@@ -291,8 +291,6 @@ __global__ __launch_bounds__(kBlock) void attn_fused_w8_kernel(FusedGeom g, Fuse
 // ------------------------------------------------------------------------------------------------
 // host side: the plan
 // ------------------------------------------------------------------------------------------------
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b ? 1 : 0); }
-
 struct FusedPlan {
     int family, block, rows, ld, lds, dynamic, store;
     int64_t grid;

@@ -42,13 +42,6 @@ constexpr int kSmxRows = 4;                     // rows a group walks where the 
 constexpr int64_t kSmxFill = 512;               // ... that is: at least this many workgroups
 static_assert(kBlock == 256, "four waves per workgroup");
 
-// u (a value of mid) as element `at` of a floating y
-__device__ __forceinline__ void attn_store_float(void* y, int64_t at, float u, int mid) {
-    if (mid == LSQ_F32) static_cast<float*>(y)[at] = u;
-    else if (mid == LSQ_BF16) static_cast<__bf16*>(y)[at] = io_bf16::passthrough(u);
-    else static_cast<_Float16*>(y)[at] = static_cast<_Float16>(u);
-}
-
 // ------------------------------------------------------------------------------------------------
 // batched matmul
 // ------------------------------------------------------------------------------------------------
@@ -166,8 +159,8 @@ __global__ __launch_bounds__(kBlock) void bmm_w8_mfma_kernel(BmmGeom g, BmmArg a
                     fI = static_cast<float>(bmm_exact(P[j][i], Cs[j][i], Rs[i], g.K, z_a, z_b));
                 }
                 const float u = bmm_value(fI, s_a, s_b, oq.mid);
-                if (oq.levels_out) lds[r * kAttnTile + c] = static_cast<unsigned char>(attn_byte(u, oq));
-                else if (m0 + r < g.M && n0 + c < g.N) attn_store_float(y, ybase + static_cast<int64_t>(m0 + r) * g.y_ld + n0 + c, u, oq.mid);
+                if (oq.levels_out) lds[r * kAttnTile + c] = static_cast<unsigned char>(w8o_byte(u, oq));
+                else if (m0 + r < g.M && n0 + c < g.N) w8o_store_float(y, ybase + static_cast<int64_t>(m0 + r) * g.y_ld + n0 + c, u, oq.mid);
             }
         }
     }
@@ -210,8 +203,10 @@ __global__ __launch_bounds__(kBlock) void bmm_w8_generic_kernel(BmmGeom g, BmmAr
     const AttnQ oq = attn_constants(o);
     const float u = bmm_value(I, a.s_a[0], a.s_b[0], oq.mid);
     const int64_t at = b0 * g.y_s0 + b1 * g.y_s1 + static_cast<int64_t>(m) * g.y_ld + n;
-    if (oq.levels_out) static_cast<uint8_t*>(y)[at] = static_cast<uint8_t>(attn_byte(u, oq));
-    else attn_store_float(y, at, u, oq.mid);
+    // w8o_store1's two lines, written out here, in smx_store16 and in softmax_w8_generic_kernel: called as one function they change
+    // this kernel's branch senses and the register allocation of the softmax packet kernels (profiles/r25_w8_out_side_isa_diff.txt)
+    if (oq.levels_out) static_cast<uint8_t*>(y)[at] = static_cast<uint8_t>(w8o_byte(u, oq));
+    else w8o_store_float(y, at, u, oq.mid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -229,7 +224,7 @@ __device__ __forceinline__ void smx_store16(void* y, int64_t at, const float (&u
         uint32_t w[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            w[i] = attn_byte(u[4 * i], q) | attn_byte(u[4 * i + 1], q) << 8 | attn_byte(u[4 * i + 2], q) << 16 | attn_byte(u[4 * i + 3], q) << 24;
+            w[i] = w8o_byte(u[4 * i], q) | w8o_byte(u[4 * i + 1], q) << 8 | w8o_byte(u[4 * i + 2], q) << 16 | w8o_byte(u[4 * i + 3], q) << 24;
         *reinterpret_cast<u32x4*>(static_cast<uint8_t*>(y) + at) = u32x4{w[0], w[1], w[2], w[3]};
     } else if (cnt >= 16 && q.mid == LSQ_F32) {
         u32x4* out = reinterpret_cast<u32x4*>(static_cast<float*>(y) + at);
@@ -240,8 +235,8 @@ __device__ __forceinline__ void smx_store16(void* y, int64_t at, const float (&u
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             if (i < cnt) {
-                if (q.levels_out) static_cast<uint8_t*>(y)[at + i] = static_cast<uint8_t>(attn_byte(u[i], q));
-                else attn_store_float(y, at + i, u[i], q.mid);
+                if (q.levels_out) static_cast<uint8_t*>(y)[at + i] = static_cast<uint8_t>(w8o_byte(u[i], q));
+                else w8o_store_float(y, at + i, u[i], q.mid);
             }
         }
     }
@@ -337,16 +332,14 @@ __global__ __launch_bounds__(kBlock) void softmax_w8_generic_kernel(SmxGeom g, A
     for (int i = lane; i < g.C; i += kSmxWave) {
         const float u = smx_value(table[(m - static_cast<int>(static_cast<uint32_t>(src[i]) ^ flip)) & 0xff], r, q.mid);
         const int64_t at = row * g.ldy + i;
-        if (q.levels_out) static_cast<uint8_t*>(y)[at] = static_cast<uint8_t>(attn_byte(u, q));
-        else attn_store_float(y, at, u, q.mid);
+        if (q.levels_out) static_cast<uint8_t*>(y)[at] = static_cast<uint8_t>(w8o_byte(u, q));
+        else w8o_store_float(y, at, u, q.mid);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side: the plans
 // ------------------------------------------------------------------------------------------------
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b ? 1 : 0); }
-
 struct BmmPlan {
     int family, block, rows, cols, lds, store;
     int64_t grid;

@@ -6,20 +6,13 @@
 #include <algorithm>
 
 #include "../lsq_companion_abi.hpp"
+#include "../lsq_w8_out_side_host.hpp"
 #include "../../../include/lsq_hip_attn_w8.h"
 #include "lsq_attn_w8_dev.hpp"
 
 namespace {
 
-typedef long long ll;
-
 bool level_dtype(int64_t code) { return code == LSQ_ATTN_W8_U8 || code == LSQ_ATTN_W8_I8; }
-bool float_dtype(int64_t code) { return code == LSQ_F32 || code == LSQ_BF16 || code == LSQ_F16; }
-
-bool overlap(const void* p, int64_t p_bytes, const void* r, int64_t r_bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(r);
-    return a < b + static_cast<uintptr_t>(r_bytes) && b < a + static_cast<uintptr_t>(p_bytes);
-}
 
 // elements from the first to one past the last of a [B0, B1, rows, cols] tensor
 int64_t span_of(const lsq_attn_w8_strides& s, int64_t B0, int64_t B1, int64_t rows, int64_t cols) {
@@ -62,24 +55,7 @@ int check_grid(const char* what, int64_t grid) {
 // the output side; the bytes of one element of y into `y_elem`
 int check_out(const char* what, const lsq_attn_w8_out* c, lsq::AttnOut& arg, int64_t& y_elem) {
     if (!c) return fail(LSQ_EINVAL, "%s: NULL output description", what);
-    if (!float_dtype(c->mid_dtype))
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(c->mid_dtype));
-    if ((c->out_scale == nullptr) != (c->out_shift == nullptr))
-        return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift: they come together", what);
-    if (c->out_scale && (!aligned_to(c->out_scale, 4) || !aligned_to(c->out_shift, 4)))
-        return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
-    if (c->out_scale) {
-        const ll lo = std::min(c->quant_min, c->type_min), hi = std::max(c->quant_max, c->type_max);
-        if (c->quant_min > c->quant_max || c->type_min > c->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-            return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                        "lie within 0..255 or within -128..127", what, static_cast<ll>(c->quant_min), static_cast<ll>(c->quant_max),
-                        static_cast<ll>(c->type_min), static_cast<ll>(c->type_max));
-    }
-    y_elem = c->out_scale ? 1 : static_cast<int64_t>(elem_bytes(static_cast<int>(c->mid_dtype)));
-    arg = lsq::AttnOut{static_cast<const float*>(c->out_scale), static_cast<const float*>(c->out_shift), static_cast<float>(c->quant_min),
-                       static_cast<float>(c->quant_max), static_cast<float>(c->type_min), static_cast<float>(c->type_max),
-                       static_cast<int>(c->mid_dtype)};
-    return LSQ_OK;
+    return check_out_side(what, *c, arg, y_elem);
 }
 
 }  // namespace

@@ -6,6 +6,7 @@
 // (profiles/r24_attn_w8_shared_isa_diff.txt).
 #pragma once
 #include "../lsq_kernels.hpp"
+#include "../lsq_w8_out_side.hpp"
 #include "../qlinear_w8/lsq_w8_shared.hpp"
 
 namespace lsq {
@@ -17,30 +18,12 @@ struct AttnOut {            // kernel argument: the output side
     int mid;
 };
 
-struct AttnQ {
-    QParams<float> qp;
-    Range<float> r;
-    int levels_out, mid;
-};
+typedef W8OutSide AttnQ;     // the output side alone: the rounding, the byte and the stores are lsq_w8_out_side.hpp's
 
 __device__ __forceinline__ AttnQ attn_constants(const AttnOut& o) {
     AttnQ q;
-    q.r = Range<float>{o.qmin, o.qmax, o.tmin, o.tmax};
-    q.levels_out = o.scale != nullptr;
-    if (q.levels_out) q.qp = make_qparams<float>(sanitize_scale_per_tensor<float>(o.scale[0]), o.shift[0], q.r);
-    else q.qp = QParams<float>{1.0f, 1.0f, 0.0f};
-    q.mid = o.mid;
+    w8o_constants(q, o);
     return q;
-}
-
-// both roundings are formed and one is selected: no branch in the epilogue
-__device__ __forceinline__ float attn_round_mid(float v, int mid) {
-    const float b = static_cast<float>(io_bf16::to_elem(v)), h = static_cast<float>(io_f16::to_elem(v));
-    return mid == LSQ_BF16 ? b : (mid == LSQ_F16 ? h : v);
-}
-
-__device__ __forceinline__ uint32_t attn_byte(float u, const AttnQ& q) {
-    return static_cast<uint32_t>(static_cast<int>(level<float>(u, q.qp, q.r)) & 0xff);
 }
 
 // the packet's bytes from `valid` on become 0 (valid >= 16: none)
@@ -55,7 +38,7 @@ __device__ __forceinline__ u32x4 attn_mask_tail(u32x4 v, int valid) {
 
 // the fp32 steps of the contract on the exact integer, and the rounding to mid
 __device__ __forceinline__ float bmm_value(float fI, float s_a, float s_b, int mid) {
-    return attn_round_mid(__fmul_rn(__fmul_rn(s_b, fI), s_a), mid);
+    return w8o_round_mid(__fmul_rn(__fmul_rn(s_b, fI), s_a), mid);
 }
 
 __device__ __forceinline__ float bmm_value(int64_t I, float s_a, float s_b, int mid) { return bmm_value(static_cast<float>(I), s_a, s_b, mid); }
@@ -116,6 +99,6 @@ __device__ __forceinline__ uint64_t smx_shfl_xor_u64(uint64_t v, int mask) {
 }
 
 // p of the contract rounded to mid: float(E) is exact (E <= 2^24)
-__device__ __forceinline__ float smx_value(int E, float r, int mid) { return attn_round_mid(__fmul_rn(static_cast<float>(E), r), mid); }
+__device__ __forceinline__ float smx_value(int E, float r, int mid) { return w8o_round_mid(__fmul_rn(static_cast<float>(E), r), mid); }
 
 }  // namespace lsq

@@ -19,7 +19,7 @@
 //  * PACKETS, every other window (dwconv_w8_packets_loop_kernel): one pixel per lane, the taps inside x in a loop with run-time
 //    bounds; sum a, sum b and T over those taps.
 //  * GENERIC (C % 16 != 0 or a misaligned buffer): one lane per output element, byte loads, (l - zx) (w - zw) as it stands.
-// One epilogue (dw_value, dw_byte; four channels at a time in dw_group) serves all of them; it has no branch on the bias's dtype
+// One epilogue (dw_value, w8o_byte; four channels at a time in dw_group) serves all of them; it has no branch on the bias's dtype
 // or on mid_dtype: both candidates are formed and one is selected, so that nothing stands between a packet's loads and its
 // arithmetic.
 #include <hip/hip_runtime.h>
@@ -28,6 +28,8 @@
 
 #include "../lsq_kernels.hpp"
 #include "../lsq_companion_abi.hpp"
+#include "../lsq_w8_out_side.hpp"
+#include "../lsq_w8_out_side_host.hpp"
 #include "../qlinear_w8/lsq_w8_shared.hpp"
 #include "../../../include/lsq_hip_dwconv_w8.h"
 
@@ -71,13 +73,10 @@ struct DwArg {              // kernel argument: the constants of one call
     int offx, offw;         // 128 for int8 levels (biased on load), 0 for uint8
 };
 
-struct DwQ {                // the same, read once per thread
-    QParams<float> qp;
-    Range<float> r;
+struct DwQ : W8OutSide {    // the same, read once per thread
     float s_x;
     int zx;                 // as it is
     float lo, hi;           // the bounds of the selects
-    int levels_out, mid;
     // the bias, read without a branch: both pointers are always loadable for C elements (w_scale stands in where the bias is
     // absent or of the other width), and the selects below pick the value, or -0.0f, which no sum is changed by
     const float* bias32;
@@ -87,13 +86,9 @@ struct DwQ {                // the same, read once per thread
 
 __device__ __forceinline__ DwQ dw_constants(const DwArg& a) {
     DwQ q;
-    q.r = Range<float>{a.qmin, a.qmax, a.tmin, a.tmax};
-    q.levels_out = a.scale != nullptr;
-    if (q.levels_out) q.qp = make_qparams<float>(sanitize_scale_per_tensor<float>(a.scale[0]), a.shift[0], q.r);
-    else q.qp = QParams<float>{1.0f, 1.0f, 0.0f};
+    w8o_constants(q, a);
     q.s_x = a.s_x[0];
     q.zx = a.zx[0];
-    q.mid = a.mid;
     q.lo = a.act >= LSQ_DWCONV_W8_ACT_RELU ? 0.0f : -__builtin_huge_valf();
     q.hi = a.act == LSQ_DWCONV_W8_ACT_RELU6 ? 6.0f : __builtin_huge_valf();
     q.has_bias = a.bias != nullptr;
@@ -111,12 +106,6 @@ __device__ __forceinline__ float dw_act(float u, float lo, float hi) {
     return (u > hi) ? hi : u;
 }
 
-// both roundings are formed and one is selected: no branch stands between the loads and the arithmetic of a packet
-__device__ __forceinline__ float dw_round_mid(float v, int mid) {
-    const float b = static_cast<float>(io_bf16::to_elem(v)), h = static_cast<float>(io_f16::to_elem(v));
-    return mid == LSQ_BF16 ? b : (mid == LSQ_F16 ? h : v);
-}
-
 // bias[c] as float32, -0.0f without a bias (v + -0.0f is v, bit for bit, a zero of either sign and a NaN included)
 __device__ __forceinline__ float dw_bias(const DwQ& q, int64_t c) {
     const float b32 = q.bias32[c];
@@ -130,19 +119,7 @@ __device__ __forceinline__ float dw_bias(const DwQ& q, int64_t c) {
 // the fp32 steps of the contract on the exact integer, the rounding to mid_dtype and the selects: r of the contract
 __device__ __forceinline__ float dw_value(int I, float s_w, float bias, const DwQ& q) {
     const float v = __fadd_rn(__fmul_rn(__fmul_rn(s_w, static_cast<float>(I)), q.s_x), bias);
-    return dw_act(dw_round_mid(v, q.mid), q.lo, q.hi);
-}
-
-__device__ __forceinline__ uint8_t dw_byte(float r, const DwQ& q) {
-    return static_cast<uint8_t>(static_cast<int>(level<float>(r, q.qp, q.r)) & 0xff);
-}
-
-// one output element (the generic kernel): `at` in elements of y
-__device__ __forceinline__ void dw_store1(void* y, int64_t at, float r, const DwQ& q) {
-    if (q.levels_out) static_cast<uint8_t*>(y)[at] = dw_byte(r, q);
-    else if (q.mid == LSQ_F32) static_cast<float*>(y)[at] = r;
-    else if (q.mid == LSQ_BF16) static_cast<__bf16*>(y)[at] = io_bf16::passthrough(r);
-    else static_cast<_Float16*>(y)[at] = static_cast<_Float16>(r);        // r is a float16 value: exact
+    return dw_act(w8o_round_mid(v, q.mid), q.lo, q.hi);
 }
 
 // four floating outputs: `at` in elements of y (a multiple of 4), y 16-byte aligned
@@ -185,8 +162,7 @@ __device__ __forceinline__ uint32_t dw_group(const uint32_t (&ab)[4], const uint
         r[k] = dw_value(I, __uint_as_float(sw4[k]), dw_bias(q, c0 + k), q);
     }
     if (q.levels_out)
-        return static_cast<uint32_t>(dw_byte(r[0], q)) | static_cast<uint32_t>(dw_byte(r[1], q)) << 8 |
-               static_cast<uint32_t>(dw_byte(r[2], q)) << 16 | static_cast<uint32_t>(dw_byte(r[3], q)) << 24;
+        return w8o_byte(r[0], q) | w8o_byte(r[1], q) << 8 | w8o_byte(r[2], q) << 16 | w8o_byte(r[3], q) << 24;
     dw_store4(y, at, r, q);
     return 0u;
 }
@@ -346,41 +322,6 @@ __global__ __launch_bounds__(kBlock, 4) void dwconv_w8_packets_dot_kernel(DwGeom
 
 #if !LSQ_DWCONV_W8_DOT4
 // ---- what the experiment's variant alone needs ----
-// a packet of 16 outputs: `at` in elements of y (a multiple of 16), y 16-byte aligned
-__device__ __forceinline__ void dw_store16(void* y, int64_t at, const float (&r)[16], const DwQ& q) {
-    if (q.levels_out) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = static_cast<uint32_t>(dw_byte(r[4 * i], q)) | static_cast<uint32_t>(dw_byte(r[4 * i + 1], q)) << 8 |
-                   static_cast<uint32_t>(dw_byte(r[4 * i + 2], q)) << 16 | static_cast<uint32_t>(dw_byte(r[4 * i + 3], q)) << 24;
-        *reinterpret_cast<u32x4*>(static_cast<uint8_t*>(y) + at) = u32x4{w[0], w[1], w[2], w[3]};
-    } else if (q.mid == LSQ_F32) {
-        u32x4* out = reinterpret_cast<u32x4*>(static_cast<float*>(y) + at);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            out[i] = u32x4{__float_as_uint(r[4 * i]), __float_as_uint(r[4 * i + 1]), __float_as_uint(r[4 * i + 2]), __float_as_uint(r[4 * i + 3])};
-    } else {
-        uint32_t w[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            unsigned short lo, hi;
-            if (q.mid == LSQ_BF16) {
-                lo = static_cast<unsigned short>(__float_as_uint(r[2 * i]) >> 16);          // r is a bfloat16 value: its high half
-                hi = static_cast<unsigned short>(__float_as_uint(r[2 * i + 1]) >> 16);
-            } else {
-                const _Float16 a = static_cast<_Float16>(r[2 * i]), b = static_cast<_Float16>(r[2 * i + 1]);
-                __builtin_memcpy(&lo, &a, 2);
-                __builtin_memcpy(&hi, &b, 2);
-            }
-            w[i] = static_cast<uint32_t>(lo) | static_cast<uint32_t>(hi) << 16;
-        }
-        u32x4* out = reinterpret_cast<u32x4*>(static_cast<uint8_t*>(y) + at * 2);
-        out[0] = u32x4{w[0], w[1], w[2], w[3]};
-        out[1] = u32x4{w[4], w[5], w[6], w[7]};
-    }
-}
-
 // the per-channel constants of a lane's packet, loaded once and reused over its pixels
 struct DwChan {
     float s_w[16], bias[16];
@@ -513,7 +454,7 @@ __global__ __launch_bounds__(kBlock) void dwconv_w8_packets_kernel(DwGeom g, DwA
                 const int I = acc[p][c] + za * (T * ch.zb[c] - dw_pair_at(sb, c)) - ch.zb[c] * dw_pair_at(sa[p], c);
                 r[c] = dw_value(I, ch.s_w[c], ch.bias[c], q);
             }
-            dw_store16(y, at0 + static_cast<int64_t>(p) * g.C, r, q);
+            w8o_store16(y, at0 + static_cast<int64_t>(p) * g.C, r, q);
         }
     }
 }
@@ -600,7 +541,7 @@ __global__ __launch_bounds__(kBlock) void dwconv_w8_generic_kernel(DwGeom g, DwA
             I += av * bv;
         }
     }
-    dw_store1(y, item, dw_value(I, a.w_scale[c], dw_bias(q, c), q), q);
+    w8o_store1(y, item, dw_value(I, a.w_scale[c], dw_bias(q, c), q), q);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -615,8 +556,6 @@ struct DwPlan {
     int family, block, pix, unrolled, ustride;
     int64_t grid;
 };
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b ? 1 : 0); }
 
 inline int64_t dw_items(const DwShape& s, int pix) { return s.pixels / s.OW * ceil_div(s.OW, pix) * s.g.CP; }
 
@@ -682,8 +621,6 @@ static hipError_t dw_launch(const DwPlan& pl, const DwShape& s, const DwArg& a, 
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-typedef long long ll;
-
 // the geometry's checks: those of lsq_hip_qconv_w8.h's convolution, then Cout == Cin and the tap limit; fills `s`
 int check_geom(const char* what, const lsq_qconv_w8_geom* g, lsq::DwShape& s) {
     if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
@@ -734,25 +671,13 @@ int check_level_dtype(const char* what, const char* name, int code) {
     return LSQ_OK;
 }
 
-// the output's checks; the bytes of one element of y into `y_elem`
-int check_out(const char* what, const lsq_dwconv_w8_out* o, int64_t& y_elem) {
+// the output's checks, which fill the output side and `act` of `a`; the bytes of one element of y into `y_elem`
+int check_out(const char* what, const lsq_dwconv_w8_out* o, lsq::DwArg& a, int64_t& y_elem) {
     if (!o) return fail(LSQ_EINVAL, "%s: NULL output description", what);
-    if (o->mid_dtype != LSQ_F32 && o->mid_dtype != LSQ_BF16 && o->mid_dtype != LSQ_F16)
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(o->mid_dtype));
+    if (int rc = check_out_side(what, *o, a, y_elem)) return rc;
     if (o->act < LSQ_DWCONV_W8_ACT_NONE || o->act > LSQ_DWCONV_W8_ACT_RELU6)
         return fail(LSQ_EINVAL, "%s: act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got %lld", what, static_cast<ll>(o->act));
-    if ((o->out_scale == nullptr) != (o->out_shift == nullptr))
-        return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift: they come together", what);
-    if (o->out_scale) {
-        if (!aligned_to(o->out_scale, 4) || !aligned_to(o->out_shift, 4))
-            return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
-        const ll lo = std::min(o->quant_min, o->type_min), hi = std::max(o->quant_max, o->type_max);
-        if (o->quant_min > o->quant_max || o->type_min > o->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-            return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                        "lie within 0..255 or within -128..127", what, static_cast<ll>(o->quant_min), static_cast<ll>(o->quant_max),
-                        static_cast<ll>(o->type_min), static_cast<ll>(o->type_max));
-    }
-    y_elem = o->out_scale ? 1 : static_cast<int64_t>(elem_bytes(static_cast<int>(o->mid_dtype)));
+    a.act = static_cast<int>(o->act);
     return LSQ_OK;
 }
 
@@ -774,43 +699,33 @@ int lsq_dwconv_w8_forward_levels(int level_dtype, const void* x_levels, const vo
                                  int bias_dtype, const lsq_dwconv_w8_out* out, void* y, void* stream) {
     const char* what = "lsq_dwconv_w8_forward_levels";
     lsq::DwShape s;
+    lsq::DwArg a{};
     int64_t y_elem = 1;
-    if (int rc = check_out(what, out, y_elem)) return rc;
+    if (int rc = check_out(what, out, a, y_elem)) return rc;
     if (int rc = check_geom(what, geom, s)) return rc;
     if (int rc = check_level_dtype(what, "level_dtype", level_dtype)) return rc;
     if (int rc = check_level_dtype(what, "w_level_dtype", w_level_dtype)) return rc;
     if (!x_levels || !s_x || !zx || !w_levels || !w_scale || !w_zero || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (!aligned_to(s_x, 4) || !aligned_to(zx, 4)) return fail(LSQ_EINVAL, "%s: s_x and zx must be element-aligned", what);
-    const int mid = static_cast<int>(out->mid_dtype);
-    if (bias && bias_dtype != LSQ_F32 && bias_dtype != mid)
+    if (bias && bias_dtype != LSQ_F32 && bias_dtype != a.mid)
         return fail(LSQ_EINVAL, "%s: the bias must be float32 or of mid_dtype, got dtype code %d", what, bias_dtype);
     if (!aligned_to(w_scale, 4) || !aligned_to(w_zero, 4) || (bias && !aligned_to(bias, elem_bytes(bias_dtype))))
         return fail(LSQ_EINVAL, "%s: w_scale, w_zero and bias must be element-aligned", what);
     if (!aligned_to(y, static_cast<uintptr_t>(y_elem))) return fail(LSQ_EINVAL, "%s: a floating y must be element-aligned", what);
-    const uintptr_t xa = reinterpret_cast<uintptr_t>(x_levels), ya = reinterpret_cast<uintptr_t>(y);
     const int64_t y_bytes = s.y_elems * y_elem;
-    if (xa < ya + static_cast<uintptr_t>(y_bytes) && ya < xa + static_cast<uintptr_t>(s.x_bytes))
+    if (overlap(y, y_bytes, x_levels, s.x_bytes))
         return fail(LSQ_EINVAL, "%s: y's %lld bytes overlap x's %lld: a convolution in place is not served", what, static_cast<ll>(y_bytes),
                     static_cast<ll>(s.x_bytes));
     // (the packet kernels read w_scale and w_zero in 16-byte packets from channel c0, c0 % 16 == 0: both must then be aligned too)
     const bool aligned = aligned_to(x_levels, 16) && aligned_to(w_levels, 16) && aligned_to(w_scale, 16) && aligned_to(w_zero, 16);
     const lsq::DwPlan pl = lsq::plan_dwconv(s, aligned, aligned_to(y, 16));
     if (int rc = check_grid(what, pl)) return rc;
-    lsq::DwArg a{};
     a.s_x = static_cast<const float*>(s_x);
     a.zx = static_cast<const int32_t*>(zx);
     a.w_scale = static_cast<const float*>(w_scale);
     a.w_zero = static_cast<const int32_t*>(w_zero);
     a.bias = bias;
-    a.scale = static_cast<const float*>(out->out_scale);
-    a.shift = static_cast<const float*>(out->out_shift);
-    a.qmin = static_cast<float>(out->quant_min);
-    a.qmax = static_cast<float>(out->quant_max);
-    a.tmin = static_cast<float>(out->type_min);
-    a.tmax = static_cast<float>(out->type_max);
     a.bias_dtype = bias_dtype;
-    a.act = static_cast<int>(out->act);
-    a.mid = mid;
     a.offx = level_dtype == LSQ_DWCONV_W8_I8 ? 128 : 0;
     a.offw = w_level_dtype == LSQ_DWCONV_W8_I8 ? 128 : 0;
     return hip_status(lsq::dw_launch(pl, s, a, static_cast<const uint8_t*>(x_levels), static_cast<const uint8_t*>(w_levels), y,

@@ -22,6 +22,8 @@
 
 #include "../lsq_kernels.hpp"
 #include "../lsq_companion_abi.hpp"
+#include "../lsq_w8_out_side.hpp"
+#include "../lsq_w8_out_side_host.hpp"
 #include "../../../include/lsq_hip_eltwise_w8.h"
 
 #ifndef LSQ_ELTWISE_W8_LUT_P
@@ -32,8 +34,6 @@
 #endif
 
 namespace lsq {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int elt_u32x4;
 
 constexpr int kEltLutMaxP = LSQ_ELTWISE_W8_LUT_P;
 constexpr int kEltLutCopies = LSQ_ELTWISE_W8_LUT_COPIES;
@@ -60,9 +60,9 @@ __global__ __launch_bounds__(kBlock) void eltwise_w8_lut_packets_kernel(const ui
     __shared__ alignas(256) uint8_t tab[256 * kEltLutCopies];
     const int tid = static_cast<int>(threadIdx.x);
     const int64_t first = static_cast<int64_t>(blockIdx.x) * (kBlock * P) + tid;
-    const elt_u32x4* __restrict__ src = reinterpret_cast<const elt_u32x4*>(x);
+    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(x);
     const uint8_t e = table[tid];                                   // issued first: it is waited for first
-    elt_u32x4 v[P];
+    u32x4 v[P];
 #pragma unroll
     for (int j = 0; j < P; ++j) v[j] = src[elt_min(first + j * kBlock, packets - 1)];         // clamped: always a packet of x
 #pragma unroll
@@ -73,11 +73,11 @@ __global__ __launch_bounds__(kBlock) void eltwise_w8_lut_packets_kernel(const ui
 #pragma unroll
     for (int j = 0; j < P; ++j) asm volatile("" : "+v"(v[j]));
     const uint8_t* mine = tab + ((tid >> 5) & (kEltLutCopies - 1)) * 256;
-    elt_u32x4* __restrict__ dst = reinterpret_cast<elt_u32x4*>(y);
+    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(y);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
         const int64_t q = first + j * kBlock;
-        const elt_u32x4 r = elt_u32x4{elt_lookup4(mine, v[j][0]), elt_lookup4(mine, v[j][1]), elt_lookup4(mine, v[j][2]),
+        const u32x4 r = u32x4{elt_lookup4(mine, v[j][0]), elt_lookup4(mine, v[j][1]), elt_lookup4(mine, v[j][2]),
                                       elt_lookup4(mine, v[j][3])};
         if (q < packets) dst[q] = r;
     }
@@ -114,34 +114,21 @@ struct EltMulGeom {         // kernel argument; the host has checked that every 
     int small;              // every item index of the launch fits 32 bits
 };
 
-struct EltMulQ {            // the constants, read once per thread
-    QParams<float> qp;
-    Range<float> r;
+struct EltMulQ : W8OutSide {        // the constants, read once per thread
     float s_x, zx, s_g, zg;
     float off_x, off_g;     // 128.0f for int8 levels, what the flipped byte carries too much; 0.0f for uint8
-    int levels_out, mid;
 };
 
 __device__ __forceinline__ EltMulQ elt_mul_constants(const EltMulArg& a) {
     EltMulQ q;
-    q.r = Range<float>{a.qmin, a.qmax, a.tmin, a.tmax};
-    q.levels_out = a.scale != nullptr;
-    if (q.levels_out) q.qp = make_qparams<float>(sanitize_scale_per_tensor<float>(a.scale[0]), a.shift[0], q.r);
-    else q.qp = QParams<float>{1.0f, 1.0f, 0.0f};
+    w8o_constants(q, a);
     q.s_x = a.s_x[0];
     q.zx = static_cast<float>(a.zx[0]);
     q.s_g = a.s_g[0];
     q.zg = static_cast<float>(a.zg[0]);
     q.off_x = a.flip_x ? 128.0f : 0.0f;
     q.off_g = a.flip_g ? 128.0f : 0.0f;
-    q.mid = a.mid;
     return q;
-}
-
-// both roundings are formed and one is selected: no branch stands between a packet's loads and its arithmetic
-__device__ __forceinline__ float elt_round_mid(float v, int mid) {
-    const float b = static_cast<float>(io_bf16::to_elem(v)), h = static_cast<float>(io_f16::to_elem(v));
-    return mid == LSQ_BF16 ? b : (mid == LSQ_F16 ? h : v);
 }
 
 // LevelsTensor.dequantize(mid) of byte `i` of a packet's word `w`, which was flipped by 0x80 per byte for int8 levels so that
@@ -150,7 +137,7 @@ __device__ __forceinline__ float elt_round_mid(float v, int mid) {
 template <int I>
 __device__ __forceinline__ float elt_dequant(uint32_t w, float off, float zero, float scale, int mid) {
     const float l = __fsub_rn(static_cast<float>((w >> (8 * I)) & 0xffu), off);
-    return elt_round_mid(__fmul_rn(__fsub_rn(l, zero), scale), mid);
+    return w8o_round_mid(__fmul_rn(__fsub_rn(l, zero), scale), mid);
 }
 
 // the four bytes of a word
@@ -162,52 +149,7 @@ __device__ __forceinline__ void elt_dequant4(float* out, uint32_t w, float off, 
 }
 
 // t of the contract: one rounded fp32 multiply (never an fma), one rounding to mid
-__device__ __forceinline__ float elt_product(float a, float g, int mid) { return elt_round_mid(__fmul_rn(a, g), mid); }
-
-__device__ __forceinline__ uint8_t elt_byte(float t, const EltMulQ& q) {
-    return static_cast<uint8_t>(static_cast<int>(level<float>(t, q.qp, q.r)) & 0xff);
-}
-
-__device__ __forceinline__ void elt_store1(void* y, int64_t at, float t, const EltMulQ& q) {
-    if (q.levels_out) static_cast<uint8_t*>(y)[at] = elt_byte(t, q);
-    else if (q.mid == LSQ_F32) static_cast<float*>(y)[at] = t;
-    else if (q.mid == LSQ_BF16) static_cast<__bf16*>(y)[at] = io_bf16::passthrough(t);
-    else static_cast<_Float16*>(y)[at] = static_cast<_Float16>(t);        // t is a float16 value: exact
-}
-
-// a packet of 16 outputs: `at` in elements of y, y 16-byte aligned
-__device__ __forceinline__ void elt_store16(void* y, int64_t at, const float (&t)[16], const EltMulQ& q) {
-    if (q.levels_out) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = static_cast<uint32_t>(elt_byte(t[4 * i], q)) | static_cast<uint32_t>(elt_byte(t[4 * i + 1], q)) << 8 |
-                   static_cast<uint32_t>(elt_byte(t[4 * i + 2], q)) << 16 | static_cast<uint32_t>(elt_byte(t[4 * i + 3], q)) << 24;
-        *reinterpret_cast<elt_u32x4*>(static_cast<uint8_t*>(y) + at) = elt_u32x4{w[0], w[1], w[2], w[3]};
-    } else if (q.mid == LSQ_F32) {
-        elt_u32x4* out = reinterpret_cast<elt_u32x4*>(static_cast<float*>(y) + at);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            out[i] = elt_u32x4{__float_as_uint(t[4 * i]), __float_as_uint(t[4 * i + 1]), __float_as_uint(t[4 * i + 2]),
-                               __float_as_uint(t[4 * i + 3])};
-    } else {
-        uint32_t w[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const _Float16 a = static_cast<_Float16>(t[2 * i]), b = static_cast<_Float16>(t[2 * i + 1]);
-            unsigned short ha, hb;
-            __builtin_memcpy(&ha, &a, 2);
-            __builtin_memcpy(&hb, &b, 2);
-            // t is a value of mid: a bfloat16 is its high half, a float16 converts exactly
-            const uint32_t lo = q.mid == LSQ_BF16 ? __float_as_uint(t[2 * i]) >> 16 : static_cast<uint32_t>(ha);
-            const uint32_t hi = q.mid == LSQ_BF16 ? __float_as_uint(t[2 * i + 1]) >> 16 : static_cast<uint32_t>(hb);
-            w[i] = lo | hi << 16;
-        }
-        elt_u32x4* out = reinterpret_cast<elt_u32x4*>(static_cast<uint8_t*>(y) + at * 2);
-        out[0] = elt_u32x4{w[0], w[1], w[2], w[3]};
-        out[1] = elt_u32x4{w[4], w[5], w[6], w[7]};
-    }
-}
+__device__ __forceinline__ float elt_product(float a, float g, int mid) { return w8o_round_mid(__fmul_rn(a, g), mid); }
 
 // (b, l) of item = b L + l; `small`: the items fit 32 bits, where the division is a handful of instructions without a branch
 __device__ __forceinline__ void elt_split(int64_t item, int64_t L, int small, int64_t& b, int64_t& l) {
@@ -231,9 +173,9 @@ __global__ __launch_bounds__(kBlock) void eltwise_w8_mul_packets_kernel(EltMulGe
     elt_split(item, g.lanes, g.small, b, l);
     // L is a multiple of P: the lane's packet position along C is l mod P at every step
     const int cp = g.small ? static_cast<int>(static_cast<uint32_t>(l) % static_cast<uint32_t>(g.P)) : static_cast<int>(l % g.P);
-    const elt_u32x4* __restrict__ src = reinterpret_cast<const elt_u32x4*>(x + b * g.image);
-    elt_u32x4 gv = *reinterpret_cast<const elt_u32x4*>(gate + (b * g.P + cp) * 16);
-    elt_u32x4 v[PIX];
+    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(x + b * g.image);
+    u32x4 gv = *reinterpret_cast<const u32x4*>(gate + (b * g.P + cp) * 16);
+    u32x4 v[PIX];
 #pragma unroll
     for (int k = 0; k < PIX; ++k) v[k] = src[elt_min(l + k * g.lanes, g.image_packets - 1)];      // clamped: always a packet of the image
     const EltMulQ q = elt_mul_constants(a);
@@ -252,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void eltwise_w8_mul_packets_kernel(EltMulGe
         for (int i = 0; i < 4; ++i) elt_dequant4(t + 4 * i, v[k][i] ^ a.flip_x, q.off_x, q.zx, q.s_x, q.mid);
 #pragma unroll
         for (int i = 0; i < 16; ++i) t[i] = elt_product(t[i], gf[i], q.mid);
-        if (p < g.image_packets) elt_store16(y, (b * g.image_packets + p) * 16, t, q);
+        if (p < g.image_packets) w8o_store16(y, (b * g.image_packets + p) * 16, t, q);
     }
 }
 
@@ -267,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void eltwise_w8_mul_generic_kernel(EltMulGe
     const int c = g.small ? static_cast<int>(static_cast<uint32_t>(r) % static_cast<uint32_t>(g.C)) : static_cast<int>(r % g.C);
     const float av = elt_dequant<0>(static_cast<uint32_t>(x[item]) ^ (a.flip_x & 0xffu), q.off_x, q.zx, q.s_x, q.mid);
     const float gv = elt_dequant<0>(static_cast<uint32_t>(gate[b * g.C + c]) ^ (a.flip_g & 0xffu), q.off_g, q.zg, q.s_g, q.mid);
-    elt_store1(y, item, elt_product(av, gv, q.mid), q);
+    w8o_store1(y, item, elt_product(av, gv, q.mid), q);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -277,8 +219,6 @@ struct EltPlan {
     int family, block, per, lds;
     int64_t grid, aux0, aux1;       // lut: packets, tail bytes; mul: lanes per image, 0
 };
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b ? 1 : 0); }
 
 inline EltPlan plan_lut(int64_t n, bool aligned) {
     EltPlan pl = {};
@@ -334,13 +274,6 @@ inline EltPlan plan_mul(EltMulShape& s, bool aligned) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-typedef long long ll;
-
-bool overlap(const void* p, int64_t p_bytes, const void* r, int64_t r_bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(r);
-    return a < b + static_cast<uintptr_t>(r_bytes) && b < a + static_cast<uintptr_t>(p_bytes);
-}
-
 int check_grid(const char* what, const lsq::EltPlan& pl) {
     if (pl.grid > INT32_MAX) return fail(LSQ_EINVAL, "%s: %lld workgroups are beyond a 31-bit grid", what, static_cast<ll>(pl.grid));
     return LSQ_OK;
@@ -375,31 +308,19 @@ int check_level_dtype(const char* what, const char* name, int code) {
     return LSQ_OK;
 }
 
-// the constants; the bytes of one element of y into `y_elem`
+// the constants, into `arg` (the caller's, zeroed); the bytes of one element of y into `y_elem`
 int check_mul(const char* what, const lsq_eltwise_w8_mul* m, int x_dtype, int g_dtype, lsq::EltMulArg& arg, int64_t& y_elem) {
     if (!m) return fail(LSQ_EINVAL, "%s: NULL constants", what);
-    if (m->mid_dtype != LSQ_F32 && m->mid_dtype != LSQ_BF16 && m->mid_dtype != LSQ_F16)
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(m->mid_dtype));
     if (!m->s_x || !m->zx || !m->s_g || !m->zg) return fail(LSQ_EINVAL, "%s: NULL s_x, zx, s_g or zg", what);
     if (!aligned_to(m->s_x, 4) || !aligned_to(m->zx, 4) || !aligned_to(m->s_g, 4) || !aligned_to(m->zg, 4))
         return fail(LSQ_EINVAL, "%s: s_x, zx, s_g and zg must be element-aligned", what);
-    if ((m->out_scale == nullptr) != (m->out_shift == nullptr))
-        return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift: they come together", what);
-    if (m->out_scale && (!aligned_to(m->out_scale, 4) || !aligned_to(m->out_shift, 4)))
-        return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
-    if (m->out_scale) {
-        const ll lo = std::min(m->quant_min, m->type_min), hi = std::max(m->quant_max, m->type_max);
-        if (m->quant_min > m->quant_max || m->type_min > m->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-            return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                        "lie within 0..255 or within -128..127", what, static_cast<ll>(m->quant_min), static_cast<ll>(m->quant_max),
-                        static_cast<ll>(m->type_min), static_cast<ll>(m->type_max));
-    }
-    y_elem = m->out_scale ? 1 : static_cast<int64_t>(elem_bytes(static_cast<int>(m->mid_dtype)));
-    arg = lsq::EltMulArg{static_cast<const float*>(m->s_x), static_cast<const int32_t*>(m->zx), static_cast<const float*>(m->s_g),
-                         static_cast<const int32_t*>(m->zg), static_cast<const float*>(m->out_scale), static_cast<const float*>(m->out_shift),
-                         static_cast<float>(m->quant_min), static_cast<float>(m->quant_max), static_cast<float>(m->type_min),
-                         static_cast<float>(m->type_max), static_cast<int>(m->mid_dtype), x_dtype == LSQ_ELTWISE_W8_I8 ? 0x80808080u : 0u,
-                         g_dtype == LSQ_ELTWISE_W8_I8 ? 0x80808080u : 0u};
+    if (int rc = check_out_side(what, *m, arg, y_elem)) return rc;
+    arg.s_x = static_cast<const float*>(m->s_x);
+    arg.zx = static_cast<const int32_t*>(m->zx);
+    arg.s_g = static_cast<const float*>(m->s_g);
+    arg.zg = static_cast<const int32_t*>(m->zg);
+    arg.flip_x = x_dtype == LSQ_ELTWISE_W8_I8 ? 0x80808080u : 0u;
+    arg.flip_g = g_dtype == LSQ_ELTWISE_W8_I8 ? 0x80808080u : 0u;
     return LSQ_OK;
 }
 

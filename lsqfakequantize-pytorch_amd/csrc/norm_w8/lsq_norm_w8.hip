@@ -21,6 +21,8 @@
 
 #include "../lsq_kernels.hpp"
 #include "../lsq_companion_abi.hpp"
+#include "../lsq_w8_out_side.hpp"
+#include "../lsq_w8_out_side_host.hpp"
 #include "../../../include/lsq_hip_norm_w8.h"
 
 #ifndef LSQ_NORM_W8_MAX_ROWS
@@ -31,8 +33,6 @@
 #endif
 
 namespace lsq {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int norm_u32x4;
 
 constexpr int kNormMaxP = 8;                    // packets per lane
 constexpr int kNormMaxRows = LSQ_NORM_W8_MAX_ROWS;      // rows a group walks
@@ -61,6 +61,9 @@ struct NormGeom {           // kernel argument
     int C, packets, K;      // channels, C / 16, rows per group
 };
 
+// The output side's four fields are W8OutSide's by name, and lsq_w8_out_side.hpp's helpers read them; they are formed here and
+// not by w8o_constants(): the order in which these constants are formed is what the compiler reacts to, and through the shared
+// function 40 of the 41 kernels came out with their row-statistics loop reordered.
 struct NormQ {              // the constants, read once per thread
     QParams<float> qp;
     Range<float> r;
@@ -91,12 +94,6 @@ __device__ __forceinline__ float norm_param(const void* p, int pdt, int i) {
     if (pdt == LSQ_F32) return static_cast<const float*>(p)[i];
     if (pdt == LSQ_BF16) return __uint_as_float(static_cast<uint32_t>(static_cast<const unsigned short*>(p)[i]) << 16);
     return static_cast<float>(static_cast<const _Float16*>(p)[i]);
-}
-
-// both roundings are formed and one is selected: no branch in the epilogue
-__device__ __forceinline__ float norm_round_mid(float v, int mid) {
-    const float b = static_cast<float>(io_bf16::to_elem(v)), h = static_cast<float>(io_f16::to_elem(v));
-    return mid == LSQ_BF16 ? b : (mid == LSQ_F16 ? h : v);
 }
 
 // A row's two per-row numbers from its exact sums (of the bytes as loaded): t_i = float(mul_i) * rc with
@@ -137,51 +134,7 @@ __device__ __forceinline__ float norm_finish(uint32_t b, const NormRow& row, flo
     const float t = __fmul_rn(static_cast<float>(static_cast<int>(b) * row.cmul - row.sub), row.rc);
     const float tw = q.has_w ? __fmul_rn(t, w) : t;
     const float a = q.has_b ? __fadd_rn(tw, bias) : tw;
-    return norm_round_mid(a, q.mid);
-}
-
-__device__ __forceinline__ uint32_t norm_byte(float u, const NormQ& q) {
-    return static_cast<uint32_t>(static_cast<int>(level<float>(u, q.qp, q.r)) & 0xff);
-}
-
-__device__ __forceinline__ void norm_store1(void* y, int64_t at, float u, const NormQ& q) {
-    if (q.levels_out) static_cast<uint8_t*>(y)[at] = static_cast<uint8_t>(norm_byte(u, q));
-    else if (q.mid == LSQ_F32) static_cast<float*>(y)[at] = u;
-    else if (q.mid == LSQ_BF16) static_cast<__bf16*>(y)[at] = io_bf16::passthrough(u);
-    else static_cast<_Float16*>(y)[at] = static_cast<_Float16>(u);        // u is a float16 value: exact
-}
-
-// a packet of 16 outputs: `at` in elements of y, y 16-byte aligned
-__device__ __forceinline__ void norm_store16(void* y, int64_t at, const float (&u)[16], const NormQ& q) {
-    if (q.levels_out) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = norm_byte(u[4 * i], q) | norm_byte(u[4 * i + 1], q) << 8 | norm_byte(u[4 * i + 2], q) << 16 | norm_byte(u[4 * i + 3], q) << 24;
-        *reinterpret_cast<norm_u32x4*>(static_cast<uint8_t*>(y) + at) = norm_u32x4{w[0], w[1], w[2], w[3]};
-    } else if (q.mid == LSQ_F32) {
-        norm_u32x4* out = reinterpret_cast<norm_u32x4*>(static_cast<float*>(y) + at);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            out[i] = norm_u32x4{__float_as_uint(u[4 * i]), __float_as_uint(u[4 * i + 1]), __float_as_uint(u[4 * i + 2]),
-                                __float_as_uint(u[4 * i + 3])};
-    } else {
-        uint32_t w[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const _Float16 a = static_cast<_Float16>(u[2 * i]), b = static_cast<_Float16>(u[2 * i + 1]);
-            unsigned short ha, hb;
-            __builtin_memcpy(&ha, &a, 2);
-            __builtin_memcpy(&hb, &b, 2);
-            // u is a value of mid: a bfloat16 is its high half, a float16 converts exactly
-            const uint32_t lo = q.mid == LSQ_BF16 ? __float_as_uint(u[2 * i]) >> 16 : static_cast<uint32_t>(ha);
-            const uint32_t hi = q.mid == LSQ_BF16 ? __float_as_uint(u[2 * i + 1]) >> 16 : static_cast<uint32_t>(hb);
-            w[i] = lo | hi << 16;
-        }
-        norm_u32x4* out = reinterpret_cast<norm_u32x4*>(static_cast<uint8_t*>(y) + at * 2);
-        out[0] = norm_u32x4{w[0], w[1], w[2], w[3]};
-        out[1] = norm_u32x4{w[4], w[5], w[6], w[7]};
-    }
+    return w8o_round_mid(a, q.mid);
 }
 
 // Workgroup b serves the rows [b G K, (b + 1) G K), G = kBlock / L groups: group g takes b G K + g + k G, k < K.  Lane l of a
@@ -223,8 +176,8 @@ __global__ __launch_bounds__(kBlock) void norm_w8_packets_kernel(NormGeom g, Nor
         const int64_t row = first + static_cast<int64_t>(k) * G;
         const bool live = row < g.R;
         const int64_t base = (live ? row : g.R - 1) * g.packets;
-        const norm_u32x4* __restrict__ src = reinterpret_cast<const norm_u32x4*>(x) + base;
-        norm_u32x4 v[P];
+        const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(x) + base;
+        u32x4 v[P];
 #pragma unroll
         for (int j = 0; j < P; ++j) v[j] = src[min(lane + j * L, g.packets - 1)];       // clamped: always a packet of the row
         // the P packets are wanted as loaded, all in flight at once (the compiler would sink a load to its first use)
@@ -267,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void norm_w8_packets_kernel(NormGeom g, Nor
                 }
                 u[i] = norm_finish((v[j][i / 4] >> (8 * (i % 4))) & 0xffu, r, w, b, q);
             }
-            if (live && p < g.packets) norm_store16(y, (base + p) * 16, u, q);
+            if (live && p < g.packets) w8o_store16(y, (base + p) * 16, u, q);
         }
     }
 }
@@ -295,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void norm_w8_generic_kernel(NormGeom g, Nor
     for (int i = lane; i < g.C; i += kNormWave) {
         const float w = q.has_w ? norm_param(a.w, a.pdt, i) : 1.0f;
         const float b = q.has_b ? norm_param(a.b, a.pdt, i) : 0.0f;
-        norm_store1(y, row * g.C + i, norm_finish(static_cast<uint32_t>(src[i]) ^ flip, r, w, b, q), q);
+        w8o_store1(y, row * g.C + i, norm_finish(static_cast<uint32_t>(src[i]) ^ flip, r, w, b, q), q);
     }
 }
 
@@ -307,8 +260,6 @@ struct NormPlan {
     int64_t grid;
     NormGeom g;
 };
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b ? 1 : 0); }
 
 inline NormPlan plan_norm(int64_t R, int64_t C, bool aligned, bool has_w, bool has_b) {
     NormPlan pl = {};
@@ -382,13 +333,6 @@ inline NormKernel packets_kernel(int L, int P) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-typedef long long ll;
-
-bool overlap(const void* p, int64_t p_bytes, const void* r, int64_t r_bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(r);
-    return a < b + static_cast<uintptr_t>(r_bytes) && b < a + static_cast<uintptr_t>(p_bytes);
-}
-
 int check_geom(const char* what, const lsq_norm_w8_geom* g) {
     if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
     if (g->kind != LSQ_NORM_W8_LAYER && g->kind != LSQ_NORM_W8_RMS)
@@ -404,13 +348,9 @@ int check_geom(const char* what, const lsq_norm_w8_geom* g) {
     return LSQ_OK;
 }
 
-bool float_dtype(int64_t code) { return code == LSQ_F32 || code == LSQ_BF16 || code == LSQ_F16; }
-
-// the constants; the bytes of one element of y into `y_elem`
+// the constants, into `arg` (the caller's, zeroed); the bytes of one element of y into `y_elem`
 int check_consts(const char* what, const lsq_norm_w8_geom* g, const lsq_norm_w8_consts* c, lsq::NormArg& arg, int64_t& y_elem) {
     if (!c) return fail(LSQ_EINVAL, "%s: NULL constants", what);
-    if (!float_dtype(c->mid_dtype))
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(c->mid_dtype));
     if ((c->weight || c->bias) && !float_dtype(c->param_dtype))
         return fail(LSQ_EINVAL, "%s: param_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(c->param_dtype));
     if (!c->s_x || !c->zx) return fail(LSQ_EINVAL, "%s: NULL s_x or zx", what);
@@ -418,24 +358,16 @@ int check_consts(const char* what, const lsq_norm_w8_geom* g, const lsq_norm_w8_
     const uintptr_t pb = (c->weight || c->bias) ? elem_bytes(static_cast<int>(c->param_dtype)) : 1;
     if ((c->weight && !aligned_to(c->weight, pb)) || (c->bias && !aligned_to(c->bias, pb)))
         return fail(LSQ_EINVAL, "%s: weight and bias must be element-aligned", what);
-    if ((c->out_scale == nullptr) != (c->out_shift == nullptr))
-        return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift: they come together", what);
-    if (c->out_scale && (!aligned_to(c->out_scale, 4) || !aligned_to(c->out_shift, 4)))
-        return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
+    if (int rc = check_out_side(what, *c, arg, y_elem)) return rc;
     if (!(c->eps >= 0.0f)) return fail(LSQ_EINVAL, "%s: eps = %g must be a number that is not negative", what, static_cast<double>(c->eps));
-    if (c->out_scale) {
-        const ll lo = std::min(c->quant_min, c->type_min), hi = std::max(c->quant_max, c->type_max);
-        if (c->quant_min > c->quant_max || c->type_min > c->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-            return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                        "lie within 0..255 or within -128..127", what, static_cast<ll>(c->quant_min), static_cast<ll>(c->quant_max),
-                        static_cast<ll>(c->type_min), static_cast<ll>(c->type_max));
-    }
-    y_elem = c->out_scale ? 1 : static_cast<int64_t>(elem_bytes(static_cast<int>(c->mid_dtype)));
-    arg = lsq::NormArg{static_cast<const float*>(c->s_x), static_cast<const int32_t*>(c->zx), c->weight, c->bias,
-                       static_cast<const float*>(c->out_scale), static_cast<const float*>(c->out_shift),
-                       static_cast<float>(c->quant_min), static_cast<float>(c->quant_max), static_cast<float>(c->type_min),
-                       static_cast<float>(c->type_max), c->eps, static_cast<int>(c->param_dtype), static_cast<int>(c->mid_dtype),
-                       g->kind == LSQ_NORM_W8_RMS ? 1 : 0, g->x_dtype == LSQ_NORM_W8_I8 ? 0x80808080u : 0u};
+    arg.s_x = static_cast<const float*>(c->s_x);
+    arg.zx = static_cast<const int32_t*>(c->zx);
+    arg.w = c->weight;
+    arg.b = c->bias;
+    arg.eps = c->eps;
+    arg.pdt = static_cast<int>(c->param_dtype);
+    arg.rms = g->kind == LSQ_NORM_W8_RMS ? 1 : 0;
+    arg.flip = g->x_dtype == LSQ_NORM_W8_I8 ? 0x80808080u : 0u;
     return LSQ_OK;
 }
 

@@ -25,6 +25,8 @@
 
 #include "../lsq_kernels.hpp"
 #include "../lsq_companion_abi.hpp"
+#include "../lsq_w8_out_side.hpp"
+#include "../lsq_w8_out_side_host.hpp"
 #include "../../../include/lsq_hip_pool_w8.h"
 
 #ifndef LSQ_POOL_W8_MAX_PIX
@@ -33,7 +35,6 @@
 
 namespace lsq {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int pool_u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned short pool_u16x2;
 
 constexpr int kPoolMaxPix = LSQ_POOL_W8_MAX_PIX;
@@ -59,23 +60,16 @@ struct PoolAvgArg {         // kernel argument: the average pool's constants
     int off;                // 128 for int8 levels (biased on load), 0 for uint8
 };
 
-struct PoolAvgQ {           // the same, read once per thread
-    QParams<float> qp;
-    Range<float> r;
+struct PoolAvgQ : W8OutSide {       // the same, read once per thread
     float s_x;
     int zz;                 // z_x + off: what one tap's biased byte carries too much
-    int levels_out, mid;
 };
 
 __device__ __forceinline__ PoolAvgQ pool_avg_constants(const PoolAvgArg& a) {
     PoolAvgQ q;
-    q.r = Range<float>{a.qmin, a.qmax, a.tmin, a.tmax};
-    q.levels_out = a.scale != nullptr;
-    if (q.levels_out) q.qp = make_qparams<float>(sanitize_scale_per_tensor<float>(a.scale[0]), a.shift[0], q.r);
-    else q.qp = QParams<float>{1.0f, 1.0f, 0.0f};
+    w8o_constants(q, a);
     q.s_x = a.s_x[0];
     q.zz = a.zx[0] + a.off;
-    q.mid = a.mid;
     return q;
 }
 
@@ -98,7 +92,9 @@ __device__ __forceinline__ PoolWindow pool_window(const PoolGeom& g, const PoolA
     return w;
 }
 
-// the fp32 steps of the contract on the exact integer S and the rounding to mid_dtype
+// the fp32 steps of the contract on the exact integer S and the rounding to mid_dtype.  The rounding is w8o_round_mid's, written
+// out as branches: with the select form pool_w8_avg_lane_kernel<2> held 45 VGPRs for 32 and measured 3-4 % slower on the 2 x 2
+// average pool in both GPU calls that timed it (profiles/r25_w8_out_side_ab.txt)
 __device__ __forceinline__ float pool_avg_value(int64_t S, float D, const PoolAvgQ& q) {
     const float v = __fdiv_rn(__fmul_rn(static_cast<float>(S), q.s_x), D);
     if (q.mid == LSQ_BF16) return static_cast<float>(io_bf16::to_elem(v));
@@ -106,59 +102,16 @@ __device__ __forceinline__ float pool_avg_value(int64_t S, float D, const PoolAv
     return v;
 }
 
-__device__ __forceinline__ uint8_t pool_avg_byte(float u, const PoolAvgQ& q) {
-    return static_cast<uint8_t>(static_cast<int>(level<float>(u, q.qp, q.r)) & 0xff);
-}
-
-// one output element (the generic kernel): `at` in elements of y
-__device__ __forceinline__ void pool_avg_store1(void* y, int64_t at, float u, const PoolAvgQ& q) {
-    if (q.levels_out) static_cast<uint8_t*>(y)[at] = pool_avg_byte(u, q);
-    else if (q.mid == LSQ_F32) static_cast<float*>(y)[at] = u;
-    else if (q.mid == LSQ_BF16) static_cast<__bf16*>(y)[at] = io_bf16::passthrough(u);
-    else static_cast<_Float16*>(y)[at] = static_cast<_Float16>(u);        // u is a float16 value: exact
-}
-
 // a packet of 16 outputs from their biased sums: `at` in elements of y, y 16-byte aligned
 __device__ __forceinline__ void pool_avg_store16(void* y, int64_t at, const uint32_t (&sum)[16], int64_t taps, float D, const PoolAvgQ& q) {
     float u[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) u[i] = pool_avg_value(static_cast<int64_t>(sum[i]) - taps * q.zz, D, q);
-    if (q.levels_out) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = static_cast<uint32_t>(pool_avg_byte(u[4 * i], q)) | static_cast<uint32_t>(pool_avg_byte(u[4 * i + 1], q)) << 8 |
-                   static_cast<uint32_t>(pool_avg_byte(u[4 * i + 2], q)) << 16 | static_cast<uint32_t>(pool_avg_byte(u[4 * i + 3], q)) << 24;
-        *reinterpret_cast<pool_u32x4*>(static_cast<uint8_t*>(y) + at) = pool_u32x4{w[0], w[1], w[2], w[3]};
-    } else if (q.mid == LSQ_F32) {
-        pool_u32x4* out = reinterpret_cast<pool_u32x4*>(static_cast<float*>(y) + at);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            out[i] = pool_u32x4{__float_as_uint(u[4 * i]), __float_as_uint(u[4 * i + 1]), __float_as_uint(u[4 * i + 2]),
-                                __float_as_uint(u[4 * i + 3])};
-    } else {
-        uint32_t w[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            unsigned short lo, hi;
-            if (q.mid == LSQ_BF16) {
-                lo = static_cast<unsigned short>(__float_as_uint(u[2 * i]) >> 16);          // u is a bfloat16 value: its high half
-                hi = static_cast<unsigned short>(__float_as_uint(u[2 * i + 1]) >> 16);
-            } else {
-                const _Float16 a = static_cast<_Float16>(u[2 * i]), b = static_cast<_Float16>(u[2 * i + 1]);
-                __builtin_memcpy(&lo, &a, 2);
-                __builtin_memcpy(&hi, &b, 2);
-            }
-            w[i] = static_cast<uint32_t>(lo) | static_cast<uint32_t>(hi) << 16;
-        }
-        pool_u32x4* out = reinterpret_cast<pool_u32x4*>(static_cast<uint8_t*>(y) + at * 2);
-        out[0] = pool_u32x4{w[0], w[1], w[2], w[3]};
-        out[1] = pool_u32x4{w[4], w[5], w[6], w[7]};
-    }
+    w8o_store16(y, at, u, q);
 }
 
 // sum[16] += the 16 biased bytes of a packet
-__device__ __forceinline__ void pool_add_packet(uint32_t (&sum)[16], pool_u32x4 v, uint32_t flip) {
+__device__ __forceinline__ void pool_add_packet(uint32_t (&sum)[16], u32x4 v, uint32_t flip) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t w = v[i] ^ flip;
@@ -176,7 +129,7 @@ struct PoolWide {           // 16 bytes as eight pairs of 16-bit lanes: e[i] the
     pool_u16x2 e[4], o[4];
 };
 
-__device__ __forceinline__ void pool_wide_max(PoolWide& acc, pool_u32x4 v, uint32_t flip) {
+__device__ __forceinline__ void pool_wide_max(PoolWide& acc, u32x4 v, uint32_t flip) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t w = v[i] ^ flip;
@@ -193,8 +146,8 @@ __device__ __forceinline__ void pool_wide_fold(PoolWide& acc, const PoolWide& co
     }
 }
 
-__device__ __forceinline__ pool_u32x4 pool_narrow(const PoolWide& a, uint32_t flip) {
-    pool_u32x4 v;
+__device__ __forceinline__ u32x4 pool_narrow(const PoolWide& a, uint32_t flip) {
+    u32x4 v;
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = (__builtin_bit_cast(uint32_t, a.e[i]) | __builtin_bit_cast(uint32_t, a.o[i]) << 8) ^ flip;
     return v;
@@ -232,19 +185,19 @@ __global__ __launch_bounds__(kBlock) void pool_w8_max_packets_kernel(PoolGeom g,
         for (int i = 0; i < 4; ++i) acc[p].e[i] = acc[p].o[i] = pool_u16x2{0, 0};
     if constexpr (K > 0) {
         static_assert(PIX == 1, "the unrolled window is the one-pixel kernel's");
-        pool_u32x4 v[K * K];
+        u32x4 v[K * K];
 #pragma unroll
         for (int i = 0; i < K; ++i)
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 bool inside = true;
                 const int ih = pool_clamp(ih0 + i, g.H, inside), iw = pool_clamp(iw0 + j, g.W, inside);
-                const pool_u32x4 t = *reinterpret_cast<const pool_u32x4*>(src + (static_cast<int64_t>(ih) * g.W + iw) * g.C);
-                v[i * K + j] = inside ? t : pool_u32x4{flip, flip, flip, flip};
+                const u32x4 t = *reinterpret_cast<const u32x4*>(src + (static_cast<int64_t>(ih) * g.W + iw) * g.C);
+                v[i * K + j] = inside ? t : u32x4{flip, flip, flip, flip};
             }
 #pragma unroll
         for (int t = 0; t < K * K; ++t) pool_wide_max(acc[0], v[t], flip);
-        *reinterpret_cast<pool_u32x4*>(y + ((b * g.OH + oh) * g.OW + ow0) * g.C + cp * 16) = pool_narrow(acc[0], flip);
+        *reinterpret_cast<u32x4*>(y + ((b * g.OH + oh) * g.OW + ow0) * g.C + cp * 16) = pool_narrow(acc[0], flip);
         return;
     }
     const int span = PIX == 1 ? g.kw : (PIX - 1) * g.sw + (g.kw - 1) * g.dw + 1;          // input columns the lane's windows cover
@@ -267,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void pool_w8_max_packets_kernel(PoolGeom g,
         for (int i = 0; i < g.kh; ++i) {
             const unsigned ih = static_cast<unsigned>(ih0 + i * g.dh);
             if (ih < static_cast<unsigned>(g.H))
-                pool_wide_max(col, *reinterpret_cast<const pool_u32x4*>(src + (static_cast<int64_t>(ih) * g.W + iw) * g.C), flip);
+                pool_wide_max(col, *reinterpret_cast<const u32x4*>(src + (static_cast<int64_t>(ih) * g.W + iw) * g.C), flip);
         }
 #pragma unroll
         for (int p = 0; p < PIX; ++p)
@@ -276,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void pool_w8_max_packets_kernel(PoolGeom g,
     uint8_t* __restrict__ dst = y + ((b * g.OH + oh) * g.OW + ow0) * g.C + cp * 16;
 #pragma unroll
     for (int p = 0; p < PIX; ++p)
-        if (ow0 + p < g.OW) *reinterpret_cast<pool_u32x4*>(dst + static_cast<int64_t>(p) * g.C) = pool_narrow(acc[p], flip);
+        if (ow0 + p < g.OW) *reinterpret_cast<u32x4*>(dst + static_cast<int64_t>(p) * g.C) = pool_narrow(acc[p], flip);
 }
 
 // one lane per output byte
@@ -329,14 +282,14 @@ __global__ __launch_bounds__(kBlock) void pool_w8_avg_lane_kernel(PoolGeom g, Po
 #pragma unroll
     for (int i = 0; i < 16; ++i) sum[i] = 0u;
     if constexpr (K > 0) {
-        pool_u32x4 v[K * K];
+        u32x4 v[K * K];
 #pragma unroll
         for (int i = 0; i < K; ++i)
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 const int ih = w.hs + min(i, w.nh - 1), iw = w.ws + min(j, w.nw - 1);
-                const pool_u32x4 t = *reinterpret_cast<const pool_u32x4*>(src + (static_cast<int64_t>(ih) * g.W + iw) * g.C);
-                v[i * K + j] = (i < w.nh && j < w.nw) ? t : pool_u32x4{flip, flip, flip, flip};
+                const u32x4 t = *reinterpret_cast<const u32x4*>(src + (static_cast<int64_t>(ih) * g.W + iw) * g.C);
+                v[i * K + j] = (i < w.nh && j < w.nw) ? t : u32x4{flip, flip, flip, flip};
             }
 #pragma unroll
         for (int t = 0; t < K * K; ++t) pool_add_packet(sum, v[t], flip);
@@ -344,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void pool_w8_avg_lane_kernel(PoolGeom g, Po
         for (int i = 0; i < w.nh; ++i) {
             const uint8_t* __restrict__ row = src + (static_cast<int64_t>(w.hs + i) * g.W + w.ws) * g.C;
             for (int j = 0; j < w.nw; ++j)
-                pool_add_packet(sum, *reinterpret_cast<const pool_u32x4*>(row + static_cast<int64_t>(j) * g.C), flip);
+                pool_add_packet(sum, *reinterpret_cast<const u32x4*>(row + static_cast<int64_t>(j) * g.C), flip);
         }
     }
     pool_avg_store16(y, item * 16, sum, static_cast<int64_t>(w.nh) * w.nw, w.D, q);
@@ -374,21 +327,21 @@ __global__ __launch_bounds__(kBlock) void pool_w8_avg_shared_kernel(PoolGeom g, 
         const unsigned taps = static_cast<unsigned>(w.nh) * static_cast<unsigned>(w.nw), nw = static_cast<unsigned>(w.nw);
         for (unsigned k = static_cast<unsigned>(slot); k < taps; k += static_cast<unsigned>(L)) {
             const unsigned i = k / nw, j = k - i * nw;
-            pool_add_packet(sum, *reinterpret_cast<const pool_u32x4*>(src + (static_cast<int64_t>(w.hs + i) * g.W + (w.ws + j)) * g.C), flip);
+            pool_add_packet(sum, *reinterpret_cast<const u32x4*>(src + (static_cast<int64_t>(w.hs + i) * g.W + (w.ws + j)) * g.C), flip);
         }
     }
-    pool_u32x4* mine = reinterpret_cast<pool_u32x4*>(part + tid * 16);
+    u32x4* mine = reinterpret_cast<u32x4*>(part + tid * 16);
     for (int s = L >> 1; s >= 1; s >>= 1) {                  // integers: any order
         if (slot >= s && slot < 2 * s) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) mine[i] = pool_u32x4{sum[4 * i], sum[4 * i + 1], sum[4 * i + 2], sum[4 * i + 3]};
+            for (int i = 0; i < 4; ++i) mine[i] = u32x4{sum[4 * i], sum[4 * i + 1], sum[4 * i + 2], sum[4 * i + 3]};
         }
         __syncthreads();
         if (slot < s) {
-            const pool_u32x4* other = reinterpret_cast<const pool_u32x4*>(part + (tid + s * cpw) * 16);
+            const u32x4* other = reinterpret_cast<const u32x4*>(part + (tid + s * cpw) * 16);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const pool_u32x4 v = other[i];
+                const u32x4 v = other[i];
                 sum[4 * i] += v[0];
                 sum[4 * i + 1] += v[1];
                 sum[4 * i + 2] += v[2];
@@ -421,7 +374,7 @@ __global__ __launch_bounds__(kBlock) void pool_w8_avg_generic_kernel(PoolGeom g,
     for (int i = 0; i < w.nh; ++i)
         for (int j = 0; j < w.nw; ++j) sum += static_cast<uint8_t>(src[(static_cast<int64_t>(w.hs + i) * g.W + (w.ws + j)) * g.C] ^ f);
     const int64_t taps = static_cast<int64_t>(w.nh) * w.nw;
-    pool_avg_store1(y, item, pool_avg_value(static_cast<int64_t>(sum) - taps * q.zz, w.D, q), q);
+    w8o_store1(y, item, pool_avg_value(static_cast<int64_t>(sum) - taps * q.zz, w.D, q), q);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -436,8 +389,6 @@ struct PoolPlan {
     int family, block, per, lds, cpw, unrolled;     // per: pixels per lane (max) / lanes per window (average); unrolled: K or 0
     int64_t grid;
 };
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + (a % b ? 1 : 0); }
 
 // K of a K x K window without dilation that the packet kernels have unrolled (2, 3), else 0
 inline int pool_unrolled(const PoolGeom& g) {
@@ -496,8 +447,6 @@ inline PoolPlan plan_pool_avg(const PoolShape& s, bool aligned) {
 // the C ABI of include/lsq_hip_pool_w8.h: validation, error bookkeeping
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-typedef long long ll;
 
 // torch.nn.functional's output extent; 0: empty
 int64_t out_extent(int64_t in, int64_t k, int64_t s, int64_t p, int64_t d, bool ceil_mode) {
@@ -561,8 +510,7 @@ int check_level_dtype(const char* what, int code) {
 
 int check_buffers(const char* what, const void* x, int64_t x_bytes, const void* y, int64_t y_bytes) {
     if (!x || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
-    if (a < b + static_cast<uintptr_t>(y_bytes) && b < a + static_cast<uintptr_t>(x_bytes))
+    if (overlap(y, y_bytes, x, x_bytes))
         return fail(LSQ_EINVAL, "%s: y's %lld bytes overlap x's %lld: pooling in place is not served", what, static_cast<ll>(y_bytes),
                     static_cast<ll>(x_bytes));
     return LSQ_OK;
@@ -573,32 +521,20 @@ int check_grid(const char* what, const lsq::PoolPlan& pl) {
     return LSQ_OK;
 }
 
-// the average pool's constants; the bytes of one element of y into `y_elem`
+// the average pool's constants, into `arg` (the caller's, zeroed); the bytes of one element of y into `y_elem`
 int check_avg(const char* what, const lsq_pool_w8_avg* a, int level_dtype, lsq::PoolAvgArg& arg, int64_t& y_elem) {
     if (!a) return fail(LSQ_EINVAL, "%s: NULL constants", what);
-    if (a->mid_dtype != LSQ_F32 && a->mid_dtype != LSQ_BF16 && a->mid_dtype != LSQ_F16)
-        return fail(LSQ_EINVAL, "%s: mid_dtype must be LSQ_F32, LSQ_BF16 or LSQ_F16, got code %lld", what, static_cast<ll>(a->mid_dtype));
     if (!a->s_x || !a->zx) return fail(LSQ_EINVAL, "%s: NULL s_x or zx", what);
     if (!aligned_to(a->s_x, 4) || !aligned_to(a->zx, 4)) return fail(LSQ_EINVAL, "%s: s_x and zx must be element-aligned", what);
-    if ((a->out_scale == nullptr) != (a->out_shift == nullptr))
-        return fail(LSQ_EINVAL, "%s: NULL out_scale or out_shift: they come together", what);
-    if (a->out_scale && (!aligned_to(a->out_scale, 4) || !aligned_to(a->out_shift, 4)))
-        return fail(LSQ_EINVAL, "%s: out_scale and out_shift must be element-aligned", what);
+    if (int rc = check_out_side(what, *a, arg, y_elem)) return rc;
     if (a->has_divisor && a->divisor_override < 1)
         return fail(LSQ_EINVAL, "%s: divisor_override = %lld, at least 1 is needed", what, static_cast<ll>(a->divisor_override));
-    if (a->out_scale) {
-        const ll lo = std::min(a->quant_min, a->type_min), hi = std::max(a->quant_max, a->type_max);
-        if (a->quant_min > a->quant_max || a->type_min > a->type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-            return fail(LSQ_EINVAL, "%s: the output's [quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must "
-                        "lie within 0..255 or within -128..127", what, static_cast<ll>(a->quant_min), static_cast<ll>(a->quant_max),
-                        static_cast<ll>(a->type_min), static_cast<ll>(a->type_max));
-    }
-    y_elem = a->out_scale ? 1 : static_cast<int64_t>(elem_bytes(static_cast<int>(a->mid_dtype)));
-    arg = lsq::PoolAvgArg{static_cast<const float*>(a->s_x), static_cast<const int32_t*>(a->zx), static_cast<const float*>(a->out_scale),
-                          static_cast<const float*>(a->out_shift), static_cast<float>(a->quant_min), static_cast<float>(a->quant_max),
-                          static_cast<float>(a->type_min), static_cast<float>(a->type_max),
-                          a->has_divisor ? static_cast<float>(a->divisor_override) : 0.0f, a->has_divisor ? 1 : 0,
-                          a->count_include_pad ? 1 : 0, static_cast<int>(a->mid_dtype), level_dtype == LSQ_POOL_W8_I8 ? 128 : 0};
+    arg.s_x = static_cast<const float*>(a->s_x);
+    arg.zx = static_cast<const int32_t*>(a->zx);
+    arg.divisor = a->has_divisor ? static_cast<float>(a->divisor_override) : 0.0f;
+    arg.has_divisor = a->has_divisor ? 1 : 0;
+    arg.include_pad = a->count_include_pad ? 1 : 0;
+    arg.off = level_dtype == LSQ_POOL_W8_I8 ? 128 : 0;
     return LSQ_OK;
 }
 
@@ -634,7 +570,7 @@ int lsq_pool_w8_max(int level_dtype, const void* x_levels, const lsq_pool_w8_geo
     const uint8_t* x = static_cast<const uint8_t*>(x_levels);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (pl.family == LSQ_POOL_W8_PACKETS) {
-        const int64_t items = s.windows / s.OW * lsq::ceil_div(s.OW, lsq::kPoolMaxPix) * s.g.P;
+        const int64_t items = s.windows / s.OW * ceil_div(s.OW, lsq::kPoolMaxPix) * s.g.P;
         uint8_t* yb = static_cast<uint8_t*>(y);
         if constexpr (lsq::kPoolMaxPix == 1) {
             if (pl.unrolled == 3) hipLaunchKernelGGL((lsq::pool_w8_max_packets_kernel<1, 3>), grid, block, 0, st, s.g, x, yb, flip, items);

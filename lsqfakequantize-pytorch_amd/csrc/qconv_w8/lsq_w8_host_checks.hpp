@@ -1,30 +1,20 @@
 // lsq_w8_host_checks.hpp -- the argument checks and kernel arguments that the C ABIs of csrc/qconv_w8/, csrc/requant_w8/ and
-// csrc/resadd_w8/ share.  Host code only, and like lsq_companion_abi.hpp everything is in an ANONYMOUS namespace: each library
-// is one translation unit, includes this once and so reports into an error buffer of its own.
+// csrc/resadd_w8/ share; check_byte_range is ../lsq_w8_out_side_host.hpp's, which the level ops' libraries include too.  Host code only,
+// and like lsq_companion_abi.hpp everything is in an ANONYMOUS namespace: each library is one translation unit, includes this once
+// and so reports into an error buffer of its own.
 //
 // `codes` is the prefix of the including library's level type codes in a message ("LSQ_REQUANT_W8": LSQ_REQUANT_W8_U8 / _I8);
 // the codes of every W8A8 header have the values of LSQ_QCONV_W8_U8 / _I8.
 #pragma once
 #include "lsq_w8_conv_src.hpp"
+#include "../lsq_w8_out_side_host.hpp"
 #include "../../../include/lsq_hip_qconv_w8.h"
 
 namespace {
 
-typedef long long ll;
-
 int check_dtype(const char* what, int dtype) {
     if (dtype == LSQ_F64) return fail(LSQ_EINVAL, "%s: float64 is not supported (the kernel computes in integers and float32)", what);
     if (dtype != LSQ_F32 && dtype != LSQ_BF16 && dtype != LSQ_F16) return fail(LSQ_EINVAL, "%s: unknown dtype code %d", what, dtype);
-    return LSQ_OK;
-}
-
-// a quantizer's levels fit a byte; `whose`: "" or the quantizer's name with a trailing blank ("the output's ")
-int check_byte_range(const char* what, const char* whose, int64_t quant_min, int64_t quant_max, int64_t type_min, int64_t type_max) {
-    const ll lo = std::min(quant_min, type_min), hi = std::max(quant_max, type_max);
-    if (quant_min > quant_max || type_min > type_max || !((lo >= 0 && hi <= 255) || (lo >= -128 && hi <= 127)))
-        return fail(LSQ_EINVAL, "%s: %s[quant_min, quant_max] = [%lld, %lld] and [type_min, type_max] = [%lld, %lld] must lie within "
-                    "0..255 or within -128..127", what, whose, static_cast<ll>(quant_min), static_cast<ll>(quant_max),
-                    static_cast<ll>(type_min), static_cast<ll>(type_max));
     return LSQ_OK;
 }
 

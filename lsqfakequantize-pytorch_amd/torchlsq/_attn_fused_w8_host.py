@@ -17,12 +17,9 @@ import ctypes
 import torch
 
 from ._abi import LsqAttnFusedW8Consts, LsqAttnFusedW8Geom, LsqAttnW8Strides, _assert_has_ops, attn_fused_w8_library
-from ._attn_w8_host import (_LEVEL_CODE, _STORES, _check_out_q, _in_place, _name, _one, _out_struct, _rows_apart, _strides4,
-                            attn_w8_bmm_q, attn_w8_softmax_q)
-from ._cpu_host import _require_cpu
-from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _act_constants
-from ._qlinear_host import _status
+from ._attn_w8_host import _STORES, _in_place, _out_struct, _rows_apart, _strides4, attn_w8_bmm_q, attn_w8_softmax_q
+from ._hip_host import _check, _on_device, _stream_of
+from ._w8_host_common import _LEVEL_CODE, _act_constants, _check_out_q, _name, _on_one_device, _one, _status
 
 _FAMILIES = ("three_launches", "fused")
 _ERR = "lsq_attn_fused_w8_last_error"
@@ -78,11 +75,7 @@ def attn_fused_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_leve
     ydt, o_rng, _ = _check_out_q(what + " (context)", o_side, mid_dtype)
     tensors = (q, k, v, q_scale, q_zero, k_scale, k_zero, v_scale, v_zero, table) + s_side[:2] + p_side[:2] + o_side[:2] + \
         (() if out is None else (out,))
-    on_gpu = any(t.is_cuda for t in tensors)
-    if on_gpu:
-        _require_gpu(what, *tensors)
-    else:
-        _require_cpu(what, *tensors)
+    on_gpu = _on_one_device(what, tensors)
     B, H, Tq, D = (int(n) for n in q.shape)
     Tk = int(k.shape[2])
     if out is None:

@@ -22,13 +22,10 @@ import torch
 
 from ._abi import (_DTYPE_CODE, LsqAttnW8Out, LsqAttnW8Strides, LsqBmmW8Consts, LsqBmmW8Geom, LsqSoftmaxW8Geom, _assert_has_ops,
                    attn_w8_library)
-from ._cpu_host import _require_cpu, cpu_levels
+from ._cpu_host import _require_cpu
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _check_range
-from ._qlinear_host import _status
+from ._w8_host_common import _LEVEL_CODE, _check_out_q, _cpu_finish, _name, _one, _status
 
-_LEVEL_CODE = {torch.uint8: 0, torch.int8: 1}
-_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
 _FAMILIES_BMM = ("generic", "mfma")
 _FAMILIES_SOFTMAX = ("generic", "packets")
 _FORMS = ("nn", "nt")
@@ -36,37 +33,9 @@ _STORES = ("elements", "packets")
 _ERR = "lsq_attn_w8_last_error"
 
 
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
-
-
-def _one(t, dtype):
-    return t.dtype == dtype and t.numel() == 1
-
-
-def _check_out_q(what, out_q, mid_dtype):
-    """(y's dtype, the range, the tensors of the output quantizer) after its checks"""
-    _check(mid_dtype in _FLOATS, "%s: %s must be float32, bfloat16 or float16, got '%s'"
-           % (what, "mid_dtype" if out_q else "out_dtype", _name(mid_dtype)))
-    if not out_q:
-        return mid_dtype, (0, 0, 0, 0), ()
-    out_scale, out_shift, rng = out_q[0], out_q[1], tuple(int(v) for v in out_q[2:])
-    unsigned = _check_range(what + " (output quantizer)", *rng)
-    _check(_one(out_scale, torch.float32) and _one(out_shift, torch.float32),
-           "%s: out_scale and out_shift must be float32 tensors of one value (a per-tensor quantizer) on the levels' device" % what)
-    return (torch.uint8 if unsigned else torch.int8), rng, (out_scale, out_shift)
-
-
 def _out_struct(out_q, rng, mid_dtype):
     return LsqAttnW8Out(out_q[0].data_ptr() if out_q else None, out_q[1].data_ptr() if out_q else None, rng[0], rng[1], rng[2], rng[3],
                         _DTYPE_CODE[mid_dtype])
-
-
-def _cpu_finish(u, out_q, rng, ydt):
-    if out_q:
-        lv = cpu_levels(u.contiguous(), out_q[0].detach().reshape(-1), out_q[1].detach().reshape(-1), 0, False, *rng, 0)
-        u = lv.view(torch.uint8) if ydt == torch.uint8 else lv
-    return u
 
 
 def _readable(t):

@@ -24,28 +24,13 @@ import torch
 import torch.nn.functional as F
 
 from ._abi import _DTYPE_CODE, LsqDwconvW8Out, LsqQconvW8Geom, _assert_has_ops, dwconv_w8_library
-from ._cpu_host import _require_cpu, cpu_levels
-from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _check_range
-from ._qlinear_host import _status
-from ._requant_w8_host import _take_out
+from ._hip_host import _check, _on_device, _stream_of
+from ._w8_host_common import _LEVEL_CODE, _check_out_q, _cpu_finish, _name, _on_one_device, _pair, _status, _take_out
 
 _CL = torch.channels_last
-_LEVEL_CODE = {torch.uint8: 0, torch.int8: 1}
-_MID_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _FAMILIES = ("generic", "packets")
 _ERR = "lsq_dwconv_w8_last_error"
 ACTS = {"none": 0, "relu": 1, "relu6": 2}
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
-
-
-def _pair(what, name, v):
-    v = tuple(int(e) for e in v) if isinstance(v, (tuple, list)) else (int(v),)
-    _check(len(v) in (1, 2), "%s: %s must be one int or a pair of ints" % (what, name))
-    return v * 2 if len(v) == 1 else v
 
 
 def _plan_call(what, geom, aligned, y_aligned):
@@ -92,8 +77,7 @@ def _dwconv(what, x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, pa
     _check(x_levels.dtype in _LEVEL_CODE, "%s: the levels must be uint8 (0..255) or int8 (-128..127), got '%s'" % (what, _name(x_levels.dtype)))
     _check(w_levels.dtype in _LEVEL_CODE, "%s: the weight levels must be int8 (-128..127) or uint8 (0..255), got '%s'"
            % (what, _name(w_levels.dtype)))
-    _check(mid_dtype in _MID_DTYPES, "%s: %s must be float32, bfloat16 or float16, got '%s'"
-           % (what, "mid_dtype" if out_q else "out_dtype", _name(mid_dtype)))
+    ydt, rng, qt = _check_out_q(what, out_q, mid_dtype, "x's device")
     act = int(act)
     _check(act in (0, 1, 2), "%s: act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got %d" % (what, act))
     _check(s_x.dtype == torch.float32 and s_x.numel() == 1 and zx.dtype == torch.int32 and zx.numel() == 1,
@@ -108,32 +92,17 @@ def _dwconv(what, x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, stride, pa
         _check(bias.dim() == 1 and bias.numel() == C, "%s: the bias needs %d values, got shape %s" % (what, C, tuple(bias.shape)))
         _check(bias.dtype in (torch.float32, mid_dtype), "%s: the bias must be float32 or of %s" % (what, "mid_dtype" if out_q else "out_dtype"))
     tensors = (x_levels, s_x, zx, w_levels, w_scale, w_zero) + ((bias,) if bias is not None else ())
-    ydt, rng = mid_dtype, (0, 0, 0, 0)
-    if out_q:
-        out_scale, out_shift, rng = out_q[0], out_q[1], tuple(int(v) for v in out_q[2:])
-        unsigned = _check_range(what + " (output quantizer)", *rng)
-        _check(out_scale.dtype == torch.float32 and out_shift.dtype == torch.float32 and out_scale.numel() == 1 and out_shift.numel() == 1,
-               "%s: out_scale and out_shift must be float32 tensors of one value (a per-tensor quantizer) on x's device" % what)
-        ydt = torch.uint8 if unsigned else torch.int8
-        tensors += (out_scale, out_shift)
-    on_gpu = any(t.is_cuda for t in tensors)
-    if on_gpu:
-        _require_gpu(what, *tensors)
-    else:
-        _require_cpu(what, *tensors)
+    on_gpu = _on_one_device(what, tensors + qt)
     if B == 0:
         return torch.empty((B, C, OH, OW), dtype=ydt, device=x_levels.device, memory_format=_CL)
     if not on_gpu:
         u = _cpu_value(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias, geom, act, mid_dtype)
-        if out_q:
-            lv = cpu_levels(u, out_scale.detach().reshape(-1), out_shift.detach().reshape(-1), 0, False, *rng, 0)
-            u = lv.view(torch.uint8) if ydt == torch.uint8 else lv
-        return u.contiguous(memory_format=_CL)
+        return _cpu_finish(u, out_q, rng, ydt).contiguous(memory_format=_CL)
     lib = dwconv_w8_library()
     lx, wl, ws, wz = x_levels.contiguous(memory_format=_CL), w_levels.contiguous(), w_scale.contiguous(), w_zero.contiguous()
     bd = None if bias is None else bias.contiguous()
     y = _take_out(what, out, (B, C, OH, OW), ydt, lx.device, _CL)
-    oq = LsqDwconvW8Out(out_scale.data_ptr() if out_q else None, out_shift.data_ptr() if out_q else None, rng[0], rng[1], rng[2], rng[3],
+    oq = LsqDwconvW8Out(qt[0].data_ptr() if out_q else None, qt[1].data_ptr() if out_q else None, rng[0], rng[1], rng[2], rng[3],
                         act, _DTYPE_CODE[mid_dtype])
     idx = lx.device.index
     rc = _on_device(idx, lib.lsq_dwconv_w8_forward_levels, _LEVEL_CODE[lx.dtype], lx.data_ptr(), s_x.data_ptr(), zx.data_ptr(),

@@ -21,21 +21,13 @@ import ctypes
 import torch
 
 from ._abi import _DTYPE_CODE, LsqEltwiseW8Mul, LsqEltwiseW8Shape, _assert_has_ops, eltwise_w8_library
-from ._cpu_host import _require_cpu, cpu_levels
+from ._cpu_host import _require_cpu
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _check_range
-from ._qlinear_host import _status
-from ._requant_w8_host import _take_out
+from ._w8_host_common import _LEVEL_CODE, _check_out_q, _cpu_finish, _name, _on_one_device, _one, _status, _take_out
 
 _CL = torch.channels_last
-_LEVEL_CODE = {torch.uint8: 0, torch.int8: 1}
-_MID_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _FAMILIES = ("generic", "packets")
 _ERR = "lsq_eltwise_w8_last_error"
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
 
 
 def _check_levels(what, name, levels):
@@ -105,10 +97,6 @@ def _mul_shape(what, x_levels, g_levels):
     return B, C, H, W
 
 
-def _one(t, dtype):
-    return t.dtype == dtype and t.numel() == 1
-
-
 def cpu_mul_gate_value(x_levels, s_x, zx, g_levels, s_g, zg, mid_dtype):
     """t of the definition, a `mid_dtype` tensor of x's shape: the two `LevelsTensor.dequantize(mid_dtype)` and torch's multiply"""
     a = ((x_levels.to(torch.float32) - zx.to(torch.float32).reshape(())) * s_x.reshape(())).to(mid_dtype)
@@ -120,41 +108,24 @@ def _mul(what, x_levels, s_x, zx, g_levels, s_g, zg, out_q, mid_dtype, out):
     _assert_has_ops()
     _check_levels(what, "x_levels", x_levels)
     _check_levels(what, "g_levels", g_levels)
-    _check(mid_dtype in _MID_DTYPES, "%s: %s must be float32, bfloat16 or float16, got '%s'"
-           % (what, "mid_dtype" if out_q else "out_dtype", _name(mid_dtype)))
     _check(_one(s_x, torch.float32) and _one(zx, torch.int32) and _one(s_g, torch.float32) and _one(zg, torch.int32),
            "%s: x_scale and g_scale must be one float32 value and x_zero and g_zero one int32 value (tensors on the levels' device)" % what)
-    tensors = (x_levels, s_x, zx, g_levels, s_g, zg)
-    ydt, rng = mid_dtype, (0, 0, 0, 0)
-    if out_q:
-        out_scale, out_shift, rng = out_q[0], out_q[1], tuple(int(v) for v in out_q[2:])
-        unsigned = _check_range(what + " (output quantizer)", *rng)
-        _check(_one(out_scale, torch.float32) and _one(out_shift, torch.float32),
-               "%s: out_scale and out_shift must be float32 tensors of one value (a per-tensor quantizer) on the levels' device" % what)
-        ydt = torch.uint8 if unsigned else torch.int8
-        tensors += (out_scale, out_shift)
+    ydt, rng, qt = _check_out_q(what, out_q, mid_dtype)
     B, C, H, W = _mul_shape(what, x_levels, g_levels)
-    on_gpu = any(t.is_cuda for t in tensors)
-    if on_gpu:
-        _require_gpu(what, *tensors)
-    else:
-        _require_cpu(what, *tensors)
+    on_gpu = _on_one_device(what, (x_levels, s_x, zx, g_levels, s_g, zg) + qt)
     four = x_levels.dim() == 4
     fmt = _CL if four else torch.contiguous_format
     if B == 0:
         return torch.empty(x_levels.shape, dtype=ydt, device=x_levels.device, memory_format=fmt)
     if not on_gpu:
         t = cpu_mul_gate_value(x_levels, s_x, zx, g_levels, s_g, zg, mid_dtype)
-        if out_q:
-            lv = cpu_levels(t, out_scale.detach().reshape(-1), out_shift.detach().reshape(-1), 0, False, *rng, 0)
-            t = lv.view(torch.uint8) if ydt == torch.uint8 else lv
-        return t.contiguous(memory_format=fmt)
+        return _cpu_finish(t, out_q, rng, ydt).contiguous(memory_format=fmt)
     lib = eltwise_w8_library()
     lx = x_levels.contiguous(memory_format=fmt)
     lg = g_levels.reshape(B, C).contiguous()
     y = _take_out(what, out, tuple(x_levels.shape), ydt, lx.device, fmt)
-    mul = LsqEltwiseW8Mul(s_x.data_ptr(), zx.data_ptr(), s_g.data_ptr(), zg.data_ptr(), out_scale.data_ptr() if out_q else None,
-                          out_shift.data_ptr() if out_q else None, rng[0], rng[1], rng[2], rng[3], _DTYPE_CODE[mid_dtype])
+    mul = LsqEltwiseW8Mul(s_x.data_ptr(), zx.data_ptr(), s_g.data_ptr(), zg.data_ptr(), qt[0].data_ptr() if out_q else None,
+                          qt[1].data_ptr() if out_q else None, rng[0], rng[1], rng[2], rng[3], _DTYPE_CODE[mid_dtype])
     idx = lx.device.index
     rc = _on_device(idx, lib.lsq_eltwise_w8_mul_gate, _LEVEL_CODE[lx.dtype], lx.data_ptr(), _LEVEL_CODE[lg.dtype], lg.data_ptr(),
                     ctypes.byref(LsqEltwiseW8Shape(B, C, H, W)), ctypes.byref(mul), y.data_ptr(), _stream_of(idx))

@@ -26,26 +26,14 @@ import math
 import torch
 
 from ._abi import _DTYPE_CODE, LsqNormW8Consts, LsqNormW8Geom, _assert_has_ops, norm_w8_library
-from ._cpu_host import _require_cpu, cpu_levels
-from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _check_range
-from ._qlinear_host import _status
-from ._requant_w8_host import _take_out
+from ._hip_host import _check, _on_device, _stream_of
+from ._w8_host_common import (_FLOATS, _LEVEL_CODE, _check_out_q, _check_x_constants, _cpu_finish, _name, _on_one_device, _status,
+                              _take_out)
 
-_LEVEL_CODE = {torch.uint8: 0, torch.int8: 1}
 _KINDS = {"layer": 0, "rms": 1}
-_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
 _FAMILIES = ("generic", "packets")
 _PARAMS = ("none", "registers", "lds")
 _ERR = "lsq_norm_w8_last_error"
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
-
-
-def _one(t, dtype):
-    return t.dtype == dtype and t.numel() == 1
 
 
 def _plan(lib, what, R, C, kind, x_dtype, aligned, has_w, has_b):
@@ -89,10 +77,7 @@ def _norm(kind, what, x_levels, s_x, zx, weight, bias, eps, out_q, mid_dtype, ou
     _assert_has_ops()
     _check(x_levels.dtype in _LEVEL_CODE, "%s: the levels must be uint8 (0..255) or int8 (-128..127), got '%s'" % (what, _name(x_levels.dtype)))
     _check(x_levels.dim() >= 1, "%s: the levels need at least one axis" % what)
-    _check(mid_dtype in _FLOATS, "%s: %s must be float32, bfloat16 or float16, got '%s'"
-           % (what, "mid_dtype" if out_q else "out_dtype", _name(mid_dtype)))
-    _check(_one(s_x, torch.float32) and _one(zx, torch.int32),
-           "%s: x_scale must be one float32 value and x_zero one int32 value (tensors on the levels' device)" % what)
+    _check_x_constants(what, s_x, zx)
     eps = float(eps)
     _check(eps >= 0.0 and not math.isnan(eps), "%s: eps = %r must be a number that is not negative" % (what, eps))
     C = int(x_levels.shape[-1])
@@ -106,30 +91,15 @@ def _norm(kind, what, x_levels, s_x, zx, weight, bias, eps, out_q, mid_dtype, ou
         _check(pdt is None or p.dtype == pdt, "%s: weight and bias must have one dtype, got '%s' and '%s'" % (what, _name(pdt), _name(p.dtype)))
         pdt = p.dtype
         tensors += (p,)
-    ydt, rng = mid_dtype, (0, 0, 0, 0)
-    if out_q:
-        out_scale, out_shift, rng = out_q[0], out_q[1], tuple(int(v) for v in out_q[2:])
-        unsigned = _check_range(what + " (output quantizer)", *rng)
-        _check(_one(out_scale, torch.float32) and _one(out_shift, torch.float32),
-               "%s: out_scale and out_shift must be float32 tensors of one value (a per-tensor quantizer) on the levels' device" % what)
-        ydt = torch.uint8 if unsigned else torch.int8
-        tensors += (out_scale, out_shift)
+    ydt, rng, qt = _check_out_q(what, out_q, mid_dtype)
     R = x_levels.numel() // max(C, 1)
     lib = norm_w8_library()
     _plan(lib, what, max(R, 1), C, kind, x_levels.dtype, True, weight is not None, bias is not None)       # the shape's checks
-    on_gpu = any(t.is_cuda for t in tensors)
-    if on_gpu:
-        _require_gpu(what, *tensors)
-    else:
-        _require_cpu(what, *tensors)
+    on_gpu = _on_one_device(what, tensors + qt)
     if R == 0:
         return torch.empty(x_levels.shape, dtype=ydt, device=x_levels.device)
     if not on_gpu:
-        u = cpu_norm_value(kind, x_levels, s_x, zx, weight, bias, eps, mid_dtype)
-        if out_q:
-            lv = cpu_levels(u, out_scale.detach().reshape(-1), out_shift.detach().reshape(-1), 0, False, *rng, 0)
-            u = lv.view(torch.uint8) if ydt == torch.uint8 else lv
-        u = u.contiguous()
+        u = _cpu_finish(cpu_norm_value(kind, x_levels, s_x, zx, weight, bias, eps, mid_dtype), out_q, rng, ydt).contiguous()
         if out is not None:
             _take_out(what, out, tuple(x_levels.shape), ydt, x_levels.device).copy_(u)
             return out
@@ -139,7 +109,7 @@ def _norm(kind, what, x_levels, s_x, zx, weight, bias, eps, out_q, mid_dtype, ou
     b = None if bias is None else bias.detach().contiguous()
     y = _take_out(what, out, tuple(x_levels.shape), ydt, lx.device)
     consts = LsqNormW8Consts(s_x.data_ptr(), zx.data_ptr(), None if w is None else w.data_ptr(), None if b is None else b.data_ptr(),
-                             out_scale.data_ptr() if out_q else None, out_shift.data_ptr() if out_q else None,
+                             qt[0].data_ptr() if out_q else None, qt[1].data_ptr() if out_q else None,
                              _DTYPE_CODE[pdt] if pdt is not None else _DTYPE_CODE[torch.float32], rng[0], rng[1], rng[2], rng[3],
                              _DTYPE_CODE[mid_dtype], eps)
     idx = lx.device.index

@@ -25,27 +25,14 @@ import torch
 import torch.nn.functional as F
 
 from ._abi import _DTYPE_CODE, LsqPoolW8Avg, LsqPoolW8Geom, _assert_has_ops, pool_w8_library
-from ._cpu_host import _require_cpu, cpu_levels
+from ._cpu_host import _require_cpu
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _check_range
-from ._qlinear_host import _status
-from ._requant_w8_host import _take_out
+from ._w8_host_common import (_LEVEL_CODE, _check_out_q, _check_x_constants, _cpu_finish, _name, _on_one_device, _pair, _status,
+                              _take_out)
 
 _CL = torch.channels_last
-_LEVEL_CODE = {torch.uint8: 0, torch.int8: 1}
-_MID_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _FAMILIES = ("generic", "packets", "packets_shared")
 _ERR = "lsq_pool_w8_last_error"
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
-
-
-def _pair(what, name, v):
-    v = tuple(int(e) for e in v) if isinstance(v, (tuple, list)) else (int(v),)
-    _check(len(v) in (1, 2), "%s: %s must be one int or a pair of ints" % (what, name))
-    return v * 2 if len(v) == 1 else v
 
 
 def _geometry(what, shape, kernel, stride, padding, dilation, ceil_mode, average):
@@ -128,39 +115,21 @@ def _cpu_avg_value(levels, s_x, zx, geom, OH, OW, count_include_pad, divisor_ove
 def _avg(what, levels, s_x, zx, kernel_size, stride, padding, ceil_mode, count_include_pad, divisor_override, out_q, mid_dtype, out):
     _assert_has_ops()
     _check_levels(what, levels)
-    _check(mid_dtype in _MID_DTYPES, "%s: %s must be float32, bfloat16 or float16, got '%s'"
-           % (what, "mid_dtype" if out_q else "out_dtype", _name(mid_dtype)))
-    _check(s_x.dtype == torch.float32 and s_x.numel() == 1 and zx.dtype == torch.int32 and zx.numel() == 1,
-           "%s: x_scale must be one float32 value and x_zero one int32 value (tensors on the levels' device)" % what)
+    _check_x_constants(what, s_x, zx)
     _check(divisor_override is None or int(divisor_override) >= 1, "%s: divisor_override must be at least 1, got %s" % (what, divisor_override))
-    tensors = (levels, s_x, zx)
-    ydt, rng = mid_dtype, (0, 0, 0, 0)
-    if out_q:
-        out_scale, out_shift, rng = out_q[0], out_q[1], tuple(int(v) for v in out_q[2:])
-        unsigned = _check_range(what + " (output quantizer)", *rng)
-        _check(out_scale.dtype == torch.float32 and out_shift.dtype == torch.float32 and out_scale.numel() == 1 and out_shift.numel() == 1,
-               "%s: out_scale and out_shift must be float32 tensors of one value (a per-tensor quantizer) on the levels' device" % what)
-        ydt = torch.uint8 if unsigned else torch.int8
-        tensors += (out_scale, out_shift)
+    ydt, rng, qt = _check_out_q(what, out_q, mid_dtype)
     geom, OH, OW = _geometry(what, levels.shape, kernel_size, stride, padding, 1, ceil_mode, True)
     B, C = geom.B, geom.C
-    on_gpu = any(t.is_cuda for t in tensors)
-    if on_gpu:
-        _require_gpu(what, *tensors)
-    else:
-        _require_cpu(what, *tensors)
+    on_gpu = _on_one_device(what, (levels, s_x, zx) + qt)
     if B == 0:
         return torch.empty((B, C, OH, OW), dtype=ydt, device=levels.device, memory_format=_CL)
     if not on_gpu:
         u = _cpu_avg_value(levels, s_x, zx, geom, OH, OW, count_include_pad, divisor_override, mid_dtype)
-        if out_q:
-            lv = cpu_levels(u, out_scale.detach().reshape(-1), out_shift.detach().reshape(-1), 0, False, *rng, 0)
-            u = lv.view(torch.uint8) if ydt == torch.uint8 else lv
-        return u.contiguous(memory_format=_CL)
+        return _cpu_finish(u, out_q, rng, ydt).contiguous(memory_format=_CL)
     lib = pool_w8_library()
     lx = levels.contiguous(memory_format=_CL)
     y = _take_out(what, out, (B, C, OH, OW), ydt, lx.device, _CL)
-    avg = LsqPoolW8Avg(s_x.data_ptr(), zx.data_ptr(), out_scale.data_ptr() if out_q else None, out_shift.data_ptr() if out_q else None,
+    avg = LsqPoolW8Avg(s_x.data_ptr(), zx.data_ptr(), qt[0].data_ptr() if out_q else None, qt[1].data_ptr() if out_q else None,
                        rng[0], rng[1], rng[2], rng[3], _DTYPE_CODE[mid_dtype], 1 if count_include_pad else 0,
                        0 if divisor_override is None else 1, 0 if divisor_override is None else int(divisor_override))
     idx = lx.device.index

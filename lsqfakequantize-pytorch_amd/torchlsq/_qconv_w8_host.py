@@ -30,9 +30,8 @@ import torch.nn.functional as F
 from ._abi import _DTYPE_CODE, LSQ_W8_I8, LSQ_W8_U8, LsqQconvW8Geom, _assert_has_ops, qconv_w8_library
 from ._cpu_host import _require_cpu, cpu_levels
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _act_constants, _check_range
-from ._qlinear_host import _status
-from ._qlinear_w8_host import _Y_DTYPES, _name
+from ._qlinear_w8_host import _Y_DTYPES
+from ._w8_host_common import _act_constants, _check_range, _name, _status
 
 _LEVEL_CODE = {torch.uint8: LSQ_W8_U8, torch.int8: LSQ_W8_I8}      # LSQ_QCONV_W8_U8 / _I8 have the same values
 _SHAPES = ("generic", "tiles", "tiles_split_k")

@@ -30,7 +30,8 @@ from ._cpu_host import _require_cpu, cpu_levels
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
 from ._pack_host import _unpack_bytes
 from ._qgemm_a8_host import qgemm_a8_forward, qgemm_a8_forward_levels, qgemm_a8_min_rows, qgemm_a8_serves
-from ._qlinear_host import _plan_dict, _status, check_packed_linear_args
+from ._qlinear_host import _plan_dict, check_packed_linear_args
+from ._w8_host_common import _act_constants, _check_range, _status
 
 _Y_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _LEVEL_CODE = {torch.uint8: LSQ_A8_U8, torch.int8: LSQ_A8_I8}
@@ -43,23 +44,6 @@ def _check_a8_args(what, x, codes, qscale, qzero, bias, group_size, bits, y_dtyp
     _check(qscale.dtype == torch.float32,
            "%s: a packed weight with a float64 scale has no 8-bit-activation linear (the op computes in integers and float32)" % what)
     return N, K
-
-
-def _check_range(what, qmin, qmax, tmin, tmax):
-    lo, hi = min(qmin, tmin), max(qmax, tmax)
-    _check(qmin <= qmax and tmin <= tmax and ((lo >= 0 and hi <= 255) or (lo >= -128 and hi <= 127)),
-           "%s: [quant_min, quant_max] = [%d, %d] and [type_min, type_max] = [%d, %d] must lie within 0..255 or within -128..127"
-           % (what, qmin, qmax, tmin, tmax))
-    return hi > 127
-
-
-def _act_constants(scale, shift, tmin, tmax):
-    """(s_x float32 [1], zx int32 [1]) as the per-tensor kernels derive them: max(|scale|, eps) and
-    round(clamp(-shift * (1 / s), type range)) -- tensor ops on scale's device, nothing is read back"""
-    s = scale.detach().reshape(-1)[:1].to(torch.float32).abs().clamp_min(torch.finfo(torch.float32).eps)
-    b = shift.detach().reshape(-1)[:1].to(torch.float32)
-    zp = torch.fmin(torch.full_like(s, tmax), torch.fmax(torch.full_like(s, tmin), -b * (1.0 / s))).round()
-    return s, zp.to(torch.int32)
 
 
 def _cpu_levels_linear(lx, s_x, zx, codes, qscale, qzero, bias, group_size, bits, y_dtype, N, K):

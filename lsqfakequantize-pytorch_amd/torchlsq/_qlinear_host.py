@@ -20,14 +20,9 @@ from ._cpu_host import _require_cpu
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
 from ._pack_host import _check_packed, pack_dequantize
 from ._qgemm_host import qgemm_forward, qgemm_serves
+from ._w8_host_common import _status
 
 _X_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
-
-
-def _status(rc, what, lib, last_error):
-    """raise for the non-zero status `rc` of the call `what` into `lib`, with the message its `last_error` entry point holds"""
-    if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (what, rc, getattr(lib, last_error)().decode("utf-8", "replace")))
 
 
 def check_packed_linear_args(what, x, codes, qscale, qzero, bias, group_size, bits, y_dtype=None):

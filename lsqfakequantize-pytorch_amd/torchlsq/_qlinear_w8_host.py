@@ -21,16 +21,11 @@ import torch
 from ._abi import _DTYPE_CODE, LSQ_W8_I8, LSQ_W8_U8, _assert_has_ops, qlinear_w8_library
 from ._cpu_host import _require_cpu, cpu_levels
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
-from ._qlinear_a8_host import _act_constants, _check_range
-from ._qlinear_host import _status
+from ._w8_host_common import _act_constants, _check_range, _name, _status
 
 _Y_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _LEVEL_CODE = {torch.uint8: LSQ_W8_U8, torch.int8: LSQ_W8_I8}
 _SHAPES = ("generic", "decode", "tiles", "tiles_split_k")
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
 
 
 def _check_w8_args(what, x, w_levels, w_scale, w_zero, bias, y_dtype):

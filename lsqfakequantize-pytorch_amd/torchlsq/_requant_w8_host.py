@@ -24,10 +24,9 @@ from ._cpu_host import _require_cpu, cpu_levels
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
 from ._qconv_w8_host import _CL, _check_conv_args, _cpu_levels_conv, _geometry, _pair
 from ._qconv_w8_host import _weight_args as _conv_weight_args
-from ._qlinear_a8_host import _act_constants, _check_range
-from ._qlinear_host import _status
-from ._qlinear_w8_host import _LEVEL_CODE, _Y_DTYPES, _check_w8_args, _cpu_levels_linear, _name
+from ._qlinear_w8_host import _LEVEL_CODE, _Y_DTYPES, _check_w8_args, _cpu_levels_linear
 from ._qlinear_w8_host import _weight_args as _linear_weight_args
+from ._w8_host_common import _act_constants, _check_range, _name, _status, _take_out
 
 _SHAPES = ("generic", "tiles", "tiles_split_k")
 _STORES = ("bytes", "packets")
@@ -54,14 +53,6 @@ def _cpu_requant(y, out_scale, out_shift, rng, relu, level_dtype):
         y = torch.where(y < 0, torch.zeros_like(y), y)
     lv = cpu_levels(y, out_scale.detach().reshape(-1), out_shift.detach().reshape(-1), 0, False, rng[0], rng[1], rng[2], rng[3], 0)
     return lv.view(torch.uint8) if level_dtype == torch.uint8 else lv
-
-
-def _take_out(what, out, shape, dtype, device, memory_format=torch.contiguous_format):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device, memory_format=memory_format)
-    _check(out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.device == device and out.is_contiguous(memory_format=memory_format),
-           "%s: `out` must be a dense %s tensor of shape %s on x's device" % (what, _name(dtype), tuple(shape)))
-    return out
 
 
 def _input_levels(what, x, act_scale, act_shift, rng):

@@ -23,11 +23,10 @@ from ._cpu_host import _require_cpu, cpu_forward
 from ._hip_host import _check, _on_device, _require_gpu, _stream_of
 from ._qconv_w8_host import _CL, _check_conv_args, _cpu_levels_conv, _geometry, _pair
 from ._qconv_w8_host import _weight_args as _conv_weight_args
-from ._qlinear_a8_host import _check_range
-from ._qlinear_host import _status
-from ._qlinear_w8_host import _LEVEL_CODE, _check_w8_args, _cpu_levels_linear, _name
+from ._qlinear_w8_host import _LEVEL_CODE, _check_w8_args, _cpu_levels_linear
 from ._qlinear_w8_host import _weight_args as _linear_weight_args
-from ._requant_w8_host import _SHAPES, _STORES, _check_out, _cpu_requant, _out_struct, _take_out
+from ._requant_w8_host import _SHAPES, _STORES, _check_out, _cpu_requant, _out_struct
+from ._w8_host_common import _check_range, _name, _status, _take_out
 
 _LOADS = ("bytes", "packets")
 _ERR = "lsq_resadd_w8_last_error"

@@ -9,7 +9,7 @@ from torch.autograd.function import once_differentiable
 
 from . import extension as _E
 from .extension import _assert_has_ops
-from ._qlinear_a8_host import _act_constants
+from ._w8_host_common import _act_constants
 
 Tensor = torch.Tensor
 
