@@ -628,6 +628,31 @@ def attn_fused_w8_library():
     return _require_companion(_ATTN_FUSED_W8_LIB, "attn_fused_w8", "the fused attention core on 8-bit levels needs", attn_fused_w8_error_str)
 
 
+# The masked softmax on 8-bit levels: the integer-table softmax over a prefix of every row, causal and key-length masks
+# (include/lsq_hip_attn_mask_w8.h): an eighteenth companion library; the ABIs above stay as they are.
+class LsqSoftmaxMaskW8Geom(ctypes.Structure):
+    """lsq_softmax_mask_w8_geom (include/lsq_hip_attn_mask_w8.h): x and y [R, C] with their row strides, the level dtype, and what
+    makes a row's prefix length: Tq, the rows that share one entry of key_lengths, causal and its offset"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("R", "C", "ldx", "ldy", "x_dtype", "Tq", "rows_per_length", "causal", "causal_offset")]
+
+
+ATTN_MASK_W8_ABI_VERSION = 1
+_SMGP = ctypes.POINTER(LsqSoftmaxMaskW8Geom)
+C_ABI_ATTN_MASK_W8 = {
+    "lsq_attn_mask_w8_abi_version": (_int, []),
+    "lsq_attn_mask_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_softmax_mask_w8": (_int, [_SMGP, _AOP, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_softmax_mask_w8_plan": (_int, [_SMGP, _int, _int, _PLAN8]),
+}
+_ATTN_MASK_W8_LIB, attn_mask_w8_error_str = _load_companion("liblsq_hip_attn_mask_w8.so", C_ABI_ATTN_MASK_W8,
+                                                            "lsq_attn_mask_w8_abi_version", ATTN_MASK_W8_ABI_VERSION)
+
+
+def attn_mask_w8_library():
+    """The ctypes handle of liblsq_hip_attn_mask_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_MASK_W8_LIB, "attn_mask_w8", "the masked softmax on 8-bit levels needs", attn_mask_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -183,6 +183,31 @@ def cpu_softmax_value(x_levels, table, mid_dtype):
     return (E.to(torch.float32) * r).to(mid_dtype)
 
 
+def _softmax_rows(what, x, ydt, row_pad, out, on_gpu):
+    """What the softmax and the masked softmax (_attn_mask_w8_host.py) do with x, `row_pad` and `out` before they plan: (y, the result
+    as the caller gets it -- `out`, or a new tensor whose rows are padded to a multiple of `row_pad` --; yr and xr, y and x as [R, C]
+    rows one stride apart, x made dense where it does not collapse or its padded packets are not readable; R; C; ldx; ldy).  With
+    R = 0 yr and xr are None and the strides those of one dense row."""
+    C = int(x.shape[-1])
+    R = x.numel() // max(C, 1)
+    if out is not None:
+        _check(out.dtype == ydt and tuple(out.shape) == tuple(x.shape) and _rows(out) is not None,
+               "%s: `out` must be a %s tensor of shape %s whose innermost stride is 1 and whose rows lie one row stride apart"
+               % (what, _name(ydt), tuple(x.shape)))
+        y, yr = out, _rows(out)
+    else:
+        Cp = (C + row_pad - 1) // row_pad * row_pad
+        full = torch.empty(tuple(x.shape[:-1]) + (Cp,), dtype=ydt, device=x.device)
+        y = full[..., :C] if Cp != C else full
+        yr = full.view(-1, Cp)[:, :C] if R else None
+    if not R:
+        return y, None, None, 0, C, C, C
+    xr = _rows(x)
+    if xr is None or (on_gpu and C % 16 and xr.stride(0) % 16 == 0 and not _readable(xr)):
+        xr = x.contiguous().view(-1, C)
+    return y, yr, xr, R, C, (max(int(xr.stride(0)), C) if R > 1 else C), (max(int(yr.stride(0)), C) if R > 1 else C)
+
+
 def _softmax(what, x, table, out_q, mid_dtype, row_pad, out):
     _assert_has_ops()
     _check(x.dtype in _LEVEL_CODE, "%s: the levels must be uint8 (0..255) or int8 (-128..127), got '%s'" % (what, _name(x.dtype)))
@@ -194,28 +219,10 @@ def _softmax(what, x, table, out_q, mid_dtype, row_pad, out):
     ydt, rng, qt = _check_out_q(what, out_q, mid_dtype)
     tensors = (x, table) + qt + (() if out is None else (out,))
     on_gpu = any(t.is_cuda for t in tensors)
-    C = int(x.shape[-1])
-    R = x.numel() // max(C, 1)
     lib = attn_w8_library()
-    if out is not None:
-        _check(out.dtype == ydt and tuple(out.shape) == tuple(x.shape) and _rows(out) is not None,
-               "%s: `out` must be a %s tensor of shape %s whose innermost stride is 1 and whose rows lie one row stride apart"
-               % (what, _name(ydt), tuple(x.shape)))
-        y, yr = out, _rows(out)
-    else:
-        Cp = (C + row_pad - 1) // row_pad * row_pad
-        full = torch.empty(tuple(x.shape[:-1]) + (Cp,), dtype=ydt, device=x.device)
-        y = full[..., :C] if Cp != C else full
-        yr = full.view(-1, Cp)[:, :C] if R else None
+    y, yr, xr, R, C, ldx, ldy = _softmax_rows(what, x, ydt, row_pad, out, on_gpu)
     plan = (ctypes.c_int32 * 8)()
-    xr = None
-    if R:
-        xr = _rows(x)
-        if xr is None or (on_gpu and C % 16 and xr.stride(0) % 16 == 0 and not _readable(xr)):
-            xr = x.contiguous().view(-1, C)
-        geom = LsqSoftmaxW8Geom(R, C, max(int(xr.stride(0)), C) if R > 1 else C, max(int(yr.stride(0)), C) if R > 1 else C, _LEVEL_CODE[x.dtype])
-    else:
-        geom = LsqSoftmaxW8Geom(1, C, C, C, _LEVEL_CODE[x.dtype])
+    geom = LsqSoftmaxW8Geom(max(R, 1), C, ldx, ldy, _LEVEL_CODE[x.dtype])
     _status(lib.lsq_softmax_w8_plan(ctypes.byref(geom), 1, ctypes.byref(plan)), what, lib, _ERR)       # the shape's checks
     if on_gpu:
         _require_gpu(what, *tensors)

@@ -53,12 +53,13 @@ from ._norm_w8_host import norm_w8_layer, norm_w8_layer_q, norm_w8_plan, norm_w8
 from ._attn_w8_host import (attn_w8_bmm, attn_w8_bmm_q, attn_w8_plan_bmm, attn_w8_plan_softmax, attn_w8_softmax,  # noqa: F401
                             attn_w8_softmax_q)
 from ._attn_fused_w8_host import attn_fused_w8_plan, attn_fused_w8_q  # noqa: F401
+from ._attn_mask_w8_host import attn_mask_w8_plan_softmax, attn_mask_w8_softmax, attn_mask_w8_softmax_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -236,6 +237,13 @@ _ATTN_SIDE = "Tensor %s_scale, Tensor %s_shift, int %s_quant_min, int %s_quant_m
 _lib_def.define("lsq_attention_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, Tensor k_zero, "
                 "Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype) -> Tensor"
                 % tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")))
+#  * the MASKED softmax on 8-bit LEVELS (liblsq_hip_attn_mask_w8.so, include/lsq_hip_attn_mask_w8.h): lsq_softmax_w8_q8(_q) over the
+#    first n keys of every row of x [.., Tq, Tk] -- `causal`: row t of a matrix sees t + 1 + `causal_offset` keys; `key_lengths`:
+#    int32 [x.shape[0]] on x's device, read in the kernel --, the output side's level of 0 (+0.0) beyond n; a row with n = 0 is all
+#    zeros (ATen: NaN).  A row's prefix equals lsq_softmax_w8_q8(_q) of that prefix bit for bit.  Inference only.
+_MASK = "bool causal=False, int causal_offset=0, Tensor? key_lengths=None"
+_lib_def.define("lsq_softmax_mask_w8_q8_q(Tensor x_levels, Tensor table, %s, %s, int row_pad=1) -> Tensor" % (_ATTN_OUT_Q, _MASK))
+_lib_def.define("lsq_softmax_mask_w8_q8(Tensor x_levels, Tensor table, ScalarType out_dtype, %s) -> Tensor" % _MASK)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1041,3 +1049,29 @@ def _fake_attention_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v
 
 torch.library.register_fake("torchlsq::lsq_attention_w8_q8_q", _fake_attention_w8_q, lib=_lib_def)
 _lib_def.impl("lsq_attention_w8_q8_q", _requant_no_grad("lsq_attention_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the masked softmax on 8-bit levels (_attn_mask_w8_host.py): GPU tensors -> liblsq_hip_attn_mask_w8.so (one call), CPU tensors -> the
+# definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_softmax_mask_w8_q8_q", attn_mask_w8_softmax_q)
+    _lib_key.impl("lsq_softmax_mask_w8_q8", attn_mask_w8_softmax)
+del _lib_key
+
+
+def _fake_softmax_mask_w8_q(x_levels, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype,
+                            causal=False, causal_offset=0, key_lengths=None, row_pad=1):
+    return _fake_softmax_w8_q(x_levels, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype,
+                              row_pad)
+
+
+def _fake_softmax_mask_w8(x_levels, table, out_dtype, causal=False, causal_offset=0, key_lengths=None):
+    return torch.empty(x_levels.shape, dtype=out_dtype, device=x_levels.device)
+
+
+torch.library.register_fake("torchlsq::lsq_softmax_mask_w8_q8_q", _fake_softmax_mask_w8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_softmax_mask_w8_q8", _fake_softmax_mask_w8, lib=_lib_def)
+_lib_def.impl("lsq_softmax_mask_w8_q8_q", _requant_no_grad("lsq_softmax_mask_w8_q8_q", (2, 3)), "Autograd")
+_lib_def.impl("lsq_softmax_mask_w8_q8", _requant_no_grad("lsq_softmax_mask_w8_q8", ()), "Autograd")

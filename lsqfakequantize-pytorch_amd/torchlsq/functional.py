@@ -1496,3 +1496,53 @@ def lsq_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float32) -> T
     Inference only."""
     _assert_has_ops()
     return torch.ops.torchlsq.lsq_softmax_w8_q8(_levels_in("lsq_softmax_w8", x).levels, table, out_dtype)
+
+
+def _causal_args(what, x, causal):
+    """(causal, causal_offset) of the ops from `causal`: None / False off, True the offset Tk - Tq, an int that offset"""
+    if causal is None or causal is False:
+        return False, 0
+    assert x.levels.dim() >= 2, "%s: causal needs levels of at least 2 axes [.., Tq, Tk], got %s" % (what, tuple(x.shape))
+    Tq, Tk = int(x.shape[-2]), int(x.shape[-1])
+    if causal is True:
+        assert Tk >= Tq, "%s: causal=True lets the last query see every key and needs Tk >= Tq, got Tq = %d and Tk = %d" % (what, Tq, Tk)
+        return True, Tk - Tq
+    assert isinstance(causal, int) and causal >= 0, "%s: causal must be None, a bool or an offset >= 0, got %r" % (what, causal)
+    return True, int(causal)
+
+
+def lsq_masked_softmax_w8_q(x: LevelsTensor, table: Tensor, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                            out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None, mid_dtype=torch.float32,
+                            causal=None, key_lengths: Tensor = None, out: Tensor = None, row_pad: int = 1) -> LevelsTensor:
+    """`lsq_softmax_w8_q` under a causal and / or a key-length mask, one launch (liblsq_hip_attn_mask_w8.so): x is [.., Tq, Tk]
+    levels and row t of each [Tq, Tk] matrix sees its first
+
+        n = min(Tk,  t + 1 + offset  where causal,  max(key_lengths[leading index], 0)  where key_lengths is given)
+
+    keys.  `causal=True`: offset = Tk - Tq, the KV-cache convention -- the last query sees every key; the diagonal for Tq == Tk; it
+    needs Tk >= Tq.  `causal=<int>`: that offset (>= 0).  `causal=None` / `False`: off.  `key_lengths`: an int32 tensor [x.shape[0]]
+    on x's device (x then has at least 3 axes), read in the kernel and never on the host, so a captured graph follows it; values
+    below 0 or above Tk are clamped.  The first n outputs of a row equal `lsq_softmax_w8_q` of that prefix BIT FOR BIT; the rest
+    are the output quantizer's level of 0.  A row with n = 0 is all level-of-0 (ATen gives NaN).  Bytes of x beyond n are never
+    looked at (unwritten KV-cache slots).  `out` and `row_pad` as in `lsq_softmax_w8_q`.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_masked_softmax_w8_q"
+    x = _levels_in(what, x)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    on, off = _causal_args(what, x, causal)
+    if out is None:
+        lv = torch.ops.torchlsq.lsq_softmax_mask_w8_q8_q(x.levels, table, *o[:6], mid_dtype, on, off, key_lengths, int(row_pad))
+    else:
+        from .extension import attn_mask_w8_softmax_q
+        lv = attn_mask_w8_softmax_q(x.levels, table, *o[:6], mid_dtype, on, off, key_lengths, 1, out=out)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_masked_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float32, causal=None, key_lengths: Tensor = None) -> Tensor:
+    """`lsq_masked_softmax_w8_q` without an output quantizer: the probabilities rounded once to `out_dtype`, +0.0 beyond a row's
+    prefix, in x's shape.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_masked_softmax_w8"
+    x = _levels_in(what, x)
+    on, off = _causal_args(what, x, causal)
+    return torch.ops.torchlsq.lsq_softmax_mask_w8_q8(x.levels, table, out_dtype, on, off, key_lengths)

@@ -7,12 +7,16 @@ blocks differ too much in how they spell the core, so a block is rewritten by ha
 
 The softmax is the package's own definition (include/lsq_hip_attn_w8.h), not ATen's: against the unfused
 `dequantize -> F.softmax -> levels` at most one level differs.
+
+MASKS: `SoftmaxW8Q` and `AttentionCoreW8Q` take `causal=` at construction and `key_lengths=` in the forward; a masked
+call goes through `torchlsq.functional.lsq_masked_softmax_w8_q` (liblsq_hip_attn_mask_w8.so), an unmasked one through exactly the ops
+it went through before.
 """
 import torch
 from torch import nn
 
-from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q, lsq_softmax_table,
-                                 lsq_softmax_w8, lsq_softmax_w8_q)
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q, lsq_masked_softmax_w8,
+                                 lsq_masked_softmax_w8_q, lsq_softmax_table, lsq_softmax_w8, lsq_softmax_w8_q)
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import _MID_DTYPES, _as_levels
 
@@ -72,11 +76,16 @@ class SoftmaxW8Q(_OutQ):
     """Softmax over the last axis of a `LevelsTensor` of `input_quantizer` (a trained per-tensor `LSQFakeQuantizer`, or the float32
     [1] scale of the incoming `LevelsTensor`): builds `lsq_softmax_table(s_x, alpha)` once, on the quantizer's device, and owns it
     as the buffer `table` (int32 [256]).  `alpha` carries attention's 1 / sqrt(D).  Returns a `LevelsTensor` of `output_quantizer`
-    (None: floats of `mid_dtype`); `row_pad` as in `lsq_softmax_w8_q`.  Inference only."""
+    (None: floats of `mid_dtype`); `row_pad` as in `lsq_softmax_w8_q`.  `causal` (an attribute, not a buffer: False / None, True or
+    an offset, as in `lsq_masked_softmax_w8_q`) and the forward's `key_lengths` (int32 [x.shape[0]] on x's device) mask a row to a
+    prefix of its keys; with neither, the unmasked op runs as before.  Inference only."""
 
-    def __init__(self, input_quantizer, output_quantizer=None, alpha=1.0, mid_dtype=torch.float32, row_pad=16):
+    causal = False          # (the default of a module pickled before the attribute existed)
+
+    def __init__(self, input_quantizer, output_quantizer=None, alpha=1.0, mid_dtype=torch.float32, row_pad=16, causal=False):
         super().__init__()
         self.alpha, self.mid_dtype, self.row_pad = float(alpha), _mid(mid_dtype), int(row_pad)
+        self.causal = causal
         if isinstance(input_quantizer, torch.Tensor):
             s_x = input_quantizer.detach().reshape(-1)[:1].to(torch.float32)
         else:
@@ -85,15 +94,21 @@ class SoftmaxW8Q(_OutQ):
         self.register_buffer("table", lsq_softmax_table(s_x, self.alpha))
         self._set_out("output", output_quantizer, "SoftmaxW8Q")
 
-    def forward(self, x, out=None):
+    def forward(self, x, out=None, key_lengths=None):
         x, = _levels("SoftmaxW8Q", x)
+        if key_lengths is not None or (self.causal is not None and self.causal is not False):
+            if self.output_range is None:
+                return lsq_masked_softmax_w8(x, self.table, self.mid_dtype, causal=self.causal, key_lengths=key_lengths)
+            return lsq_masked_softmax_w8_q(x, self.table, *self._out("output"), self.mid_dtype, causal=self.causal, key_lengths=key_lengths,
+                                           out=out, row_pad=self.row_pad)
         if self.output_range is None:
             return lsq_softmax_w8(x, self.table, self.mid_dtype)
         return lsq_softmax_w8_q(x, self.table, *self._out("output"), self.mid_dtype, out=out, row_pad=self.row_pad)
 
     def extra_repr(self):
-        return "alpha=%g, %s, mid_dtype=%s" % (self.alpha, "output levels %d..%d" % self.output_range[:2] if self.output_range
-                                               else "floats out", str(self.mid_dtype).replace("torch.", ""))
+        return "alpha=%g, %s, mid_dtype=%s%s" % (self.alpha, "output levels %d..%d" % self.output_range[:2] if self.output_range
+                                                 else "floats out", str(self.mid_dtype).replace("torch.", ""),
+                                                 "" if self.causal is None or self.causal is False else ", causal=%r" % (self.causal,))
 
 
 class AttentionCoreW8Q(nn.Module):
@@ -108,34 +123,56 @@ class AttentionCoreW8Q(nn.Module):
     `fused=True` (opt-in; an attribute, not a buffer: the `state_dict` is the same) sends the same constants and the same table
     through `torchlsq.functional.lsq_attention_w8_q` instead: ONE launch where liblsq_hip_attn_fused_w8.so serves the shape (the scores
     and probabilities stay in LDS), the three launches elsewhere -- the same bytes either way, and q and k, v may differ in T.
+
+    MASKS.  `causal` (an attribute, not a buffer; as in `lsq_masked_softmax_w8_q`: True lets the last query see every key) and the
+    forward's `key_lengths` (int32 [B] on q's device, read in the kernel) mask the softmax.  A masked call ALWAYS runs three
+    launches, also with `fused=True`, and accepts k and v of [B, H, Tk, D] with Tk != Tq (decode: Tq = 1): the scores matmul still
+    computes all Tk columns, the masked softmax writes the probability quantizer's level of 0 beyond a row's prefix, and p v is
+    the existing matmul on those bytes.  With neither, nothing changes in bytes or in the ops called.
     Inference only."""
 
-    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False):
+    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False, causal=False):
         super().__init__()
         self.fused = bool(fused)
         self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
-        self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16)
+        self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16, causal=causal)
         self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
         assert None not in (self.scores.output_range, self.softmax.output_range, self.context.output_range), \
             "AttentionCoreW8Q needs the three trained quantizers"
 
-    def forward(self, q, k, v):
+    @property
+    def causal(self):
+        return self.softmax.causal
+
+    @causal.setter
+    def causal(self, value):
+        self.softmax.causal = value
+
+    def forward(self, q, k, v, key_lengths=None):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
-        if self.fused:
+        masked = key_lengths is not None or (self.causal is not None and self.causal is not False)
+        if self.fused and not masked:
             return lsq_attention_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
                                       self.context._out("output"), self.scores.mid_dtype)
-        assert q.levels.dim() == 4 and q.shape == k.shape == v.shape, \
-            "AttentionCoreW8Q needs q, k and v of one shape [B, H, T, D], got %s, %s and %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape))
+        if masked:
+            assert q.levels.dim() == 4 and k.levels.dim() == 4 and k.shape == v.shape and q.shape[:2] == k.shape[:2] and q.shape[3] == k.shape[3], \
+                "AttentionCoreW8Q (masked) needs q [B, H, Tq, D] and k, v [B, H, Tk, D], got %s, %s and %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape))
+        else:
+            assert q.levels.dim() == 4 and q.shape == k.shape == v.shape, \
+                "AttentionCoreW8Q needs q, k and v of one shape [B, H, T, D], got %s, %s and %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape))
         B, H, T, D = (int(n) for n in q.shape)
+        Tk = int(k.shape[2])
         # the scores' rows are padded to 16 bytes like the probabilities': both are then stored and read as packets for any T
         rng = self.scores.output_range
-        scores = torch.empty((B, H, T, (T + 15) // 16 * 16), dtype=torch.uint8 if max(rng[1], rng[3]) > 127 else torch.int8, device=q.device)
-        p = self.softmax(self.scores(q, k, out=scores[..., :T]))
+        scores = torch.empty((B, H, T, (Tk + 15) // 16 * 16), dtype=torch.uint8 if max(rng[1], rng[3]) > 127 else torch.int8, device=q.device)
+        s = self.scores(q, k, out=scores[..., :Tk])
+        p = self.softmax(s, key_lengths=key_lengths) if masked else self.softmax(s)
         rng = self.context.output_range
         buf = torch.empty((B, T, H * D), dtype=torch.uint8 if max(rng[1], rng[3]) > 127 else torch.int8, device=q.device)
         y = self.context(p, v, out=buf.view(B, T, H, D).permute(0, 2, 1, 3))
         return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
 
     def extra_repr(self):
-        return "fused=%s (%s)" % (self.fused, "lsq_attention_w8_q: one launch where the fused kernel serves the shape" if self.fused
-                                  else "three launches")
+        return "fused=%s (%s)%s" % (self.fused, "lsq_attention_w8_q: one launch where the fused kernel serves the shape" if self.fused
+                                    else "three launches", "" if self.causal is None or self.causal is False
+                                    else ", causal=%r: masked calls run three launches" % (self.causal,))
