@@ -653,6 +653,42 @@ def attn_mask_w8_library():
     return _require_companion(_ATTN_MASK_W8_LIB, "attn_mask_w8", "the masked softmax on 8-bit levels needs", attn_mask_w8_error_str)
 
 
+# Rotary position embedding and the KV-cache append on 8-bit levels, positions on the device (include/lsq_hip_rope_w8.h): a
+# nineteenth companion library; the ABIs above stay as they are.
+class LsqRopeW8Geom(ctypes.Structure):
+    """lsq_rope_w8_geom (include/lsq_hip_rope_w8.h): x [B, T, H, D] and y [B, Tout, H, D] with their three strides each, the rotary
+    dimension, the tables' positions, the level dtype, the pairing style, scatter and the mode"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "T", "H", "D", "R", "P", "Tout", "x_sb", "x_st", "x_sh", "y_sb", "y_st", "y_sh",
+                                                    "x_dtype", "style", "scatter", "mode")]
+
+
+class LsqRopeW8In(ctypes.Structure):
+    """lsq_rope_w8_in (include/lsq_hip_rope_w8.h): x's scale and zero point on the device"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_x", "zx")]
+
+
+class LsqRopeW8Out(ctypes.Structure):
+    """lsq_rope_w8_out (include/lsq_hip_rope_w8.h): the output quantizer (or none: floats) and mid_dtype"""
+    _fields_ = [("out_scale", ctypes.c_void_p), ("out_shift", ctypes.c_void_p)] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "mid_dtype")]
+
+
+ROPE_W8_ABI_VERSION = 1
+_RGP = ctypes.POINTER(LsqRopeW8Geom)
+C_ABI_ROPE_W8 = {
+    "lsq_rope_w8_abi_version": (_int, []),
+    "lsq_rope_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_rope_w8": (_int, [_RGP, ctypes.POINTER(LsqRopeW8In), ctypes.POINTER(LsqRopeW8Out), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_rope_w8_plan": (_int, [_RGP, _int, _PLAN8]),
+}
+_ROPE_W8_LIB, rope_w8_error_str = _load_companion("liblsq_hip_rope_w8.so", C_ABI_ROPE_W8, "lsq_rope_w8_abi_version", ROPE_W8_ABI_VERSION)
+
+
+def rope_w8_library():
+    """The ctypes handle of liblsq_hip_rope_w8.so (raises if it is missing)."""
+    return _require_companion(_ROPE_W8_LIB, "rope_w8", "rotary embedding and the KV-cache append on 8-bit levels need", rope_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -54,12 +54,13 @@ from ._attn_w8_host import (attn_w8_bmm, attn_w8_bmm_q, attn_w8_plan_bmm, attn_w
                             attn_w8_softmax_q)
 from ._attn_fused_w8_host import attn_fused_w8_plan, attn_fused_w8_q  # noqa: F401
 from ._attn_mask_w8_host import attn_mask_w8_plan_softmax, attn_mask_w8_softmax, attn_mask_w8_softmax_q  # noqa: F401
+from ._rope_w8_host import rope_w8, rope_w8_kv_copy, rope_w8_plan, rope_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -244,6 +245,16 @@ _lib_def.define("lsq_attention_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q
 _MASK = "bool causal=False, int causal_offset=0, Tensor? key_lengths=None"
 _lib_def.define("lsq_softmax_mask_w8_q8_q(Tensor x_levels, Tensor table, %s, %s, int row_pad=1) -> Tensor" % (_ATTN_OUT_Q, _MASK))
 _lib_def.define("lsq_softmax_mask_w8_q8(Tensor x_levels, Tensor table, ScalarType out_dtype, %s) -> Tensor" % _MASK)
+#  * ROTARY POSITION EMBEDDING and the KV-CACHE APPEND on 8-bit LEVELS (liblsq_hip_rope_w8.so, include/lsq_hip_rope_w8.h): x
+#    [B, T, H, D] levels with one scale and zero point, `cos` and `sin` float32 [P, R / 2] holding values of `mid_dtype`, `positions`
+#    int32 [B] on x's device, read in the kernel: token (b, t) is rotated at the position positions[b] + t, every step rounded to
+#    `mid_dtype` -> levels or floats [B, T, H, D].  `lsq_kv_copy_w8` moves x's bytes into `out` [B, Tout, H, D] at those positions (or
+#    at t); a token outside `out` is not written.  Inference only.
+_ROPE = "Tensor x_levels, Tensor x_scale, Tensor x_zero, Tensor cos, Tensor sin"
+_ROPE_POS = "Tensor? positions=None, bool interleaved=False"
+_lib_def.define("lsq_rope_w8_q8_q(%s, %s, %s) -> Tensor" % (_ROPE, _ATTN_OUT_Q, _ROPE_POS))
+_lib_def.define("lsq_rope_w8_q8(%s, ScalarType out_dtype, %s) -> Tensor" % (_ROPE, _ROPE_POS))
+_lib_def.define("lsq_kv_copy_w8(Tensor x_levels, Tensor(a!) out, Tensor? positions=None, bool scatter=True) -> ()")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1075,3 +1086,35 @@ torch.library.register_fake("torchlsq::lsq_softmax_mask_w8_q8_q", _fake_softmax_
 torch.library.register_fake("torchlsq::lsq_softmax_mask_w8_q8", _fake_softmax_mask_w8, lib=_lib_def)
 _lib_def.impl("lsq_softmax_mask_w8_q8_q", _requant_no_grad("lsq_softmax_mask_w8_q8_q", (2, 3)), "Autograd")
 _lib_def.impl("lsq_softmax_mask_w8_q8", _requant_no_grad("lsq_softmax_mask_w8_q8", ()), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# rotary embedding and the KV-cache append on 8-bit levels (_rope_w8_host.py): GPU tensors -> liblsq_hip_rope_w8.so (one call), CPU
+# tensors -> the definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_rope_w8_q8_q", rope_w8_q)
+    _lib_key.impl("lsq_rope_w8_q8", rope_w8)
+    _lib_key.impl("lsq_kv_copy_w8", rope_w8_kv_copy)
+del _lib_key
+
+
+def _fake_rope_w8_q(x_levels, x_scale, x_zero, cos, sin, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max,
+                    mid_dtype, positions=None, interleaved=False):
+    return torch.empty(x_levels.shape, dtype=_fake_level_dtype(out_quant_max, out_type_max), device=x_levels.device)
+
+
+def _fake_rope_w8(x_levels, x_scale, x_zero, cos, sin, out_dtype, positions=None, interleaved=False):
+    return torch.empty(x_levels.shape, dtype=out_dtype, device=x_levels.device)
+
+
+def _fake_kv_copy_w8(x_levels, out, positions=None, scatter=True):
+    return None
+
+
+torch.library.register_fake("torchlsq::lsq_rope_w8_q8_q", _fake_rope_w8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_rope_w8_q8", _fake_rope_w8, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_kv_copy_w8", _fake_kv_copy_w8, lib=_lib_def)
+_lib_def.impl("lsq_rope_w8_q8_q", _requant_no_grad("lsq_rope_w8_q8_q", (1, 3, 4, 5, 6)), "Autograd")
+_lib_def.impl("lsq_rope_w8_q8", _requant_no_grad("lsq_rope_w8_q8", (1, 3, 4)), "Autograd")
+_lib_def.impl("lsq_kv_copy_w8", _requant_no_grad("lsq_kv_copy_w8", ()), "Autograd")

@@ -1546,3 +1546,72 @@ def lsq_masked_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float3
     x = _levels_in(what, x)
     on, off = _causal_args(what, x, causal)
     return torch.ops.torchlsq.lsq_softmax_mask_w8_q8(x.levels, table, out_dtype, on, off, key_lengths)
+
+
+def lsq_rope_tables(dim: int, max_positions: int, base: float = 10000.0, mid_dtype=torch.float32, device=None):
+    """The `(cos, sin)` tables of `lsq_rope_w8_q` for the rotary dimension `dim` (even) and the positions 0 .. `max_positions` - 1:
+    float32 [P, dim / 2] on `device`, built in float64 from torch ops -- angle[p, i] = p * base^(-2 i / dim) --, taken to float32,
+    rounded ONCE to `mid_dtype` and widened back, so that they hold values of `mid_dtype`.  Any other scheme (scaled, NTK, YaRN) is
+    a table of the caller's with the same layout and rounding."""
+    dim, P = int(dim), int(max_positions)
+    assert dim >= 2 and dim % 2 == 0 and P >= 1, "lsq_rope_tables: dim must be even and at least 2, max_positions at least 1"
+    assert mid_dtype in (torch.float32, torch.bfloat16, torch.float16), "lsq_rope_tables: mid_dtype must be float32, bfloat16 or float16"
+    inv = torch.pow(torch.tensor(float(base), dtype=torch.float64, device=device),
+                    -torch.arange(0, dim, 2, dtype=torch.float64, device=device) / dim)
+    ang = torch.arange(P, dtype=torch.float64, device=device).reshape(P, 1) * inv.reshape(1, -1)
+    return tuple(f(ang).to(torch.float32).to(mid_dtype).to(torch.float32).contiguous() for f in (torch.cos, torch.sin))
+
+
+def _rope_operand(x):
+    """x [B, T, H, D] as the ops take it"""
+    assert x.levels.dim() == 4, "rotary embedding needs levels of [B, T, H, D], got %s" % (tuple(x.shape),)
+    return x.levels, x.scale, x.zero_point
+
+
+def lsq_rope_w8_q(x: LevelsTensor, cos: Tensor, sin: Tensor, out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None,
+                  out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None, mid_dtype=torch.float32,
+                  positions: Tensor = None, interleaved: bool = False, out: Tensor = None, scatter: bool = False) -> LevelsTensor:
+    """Rotary position embedding on 8-bit levels with an 8-bit output, one launch (liblsq_hip_rope_w8.so): x [B, T, H, D] (a
+    `qkv.view(B, T, 3, H, D)[:, :, i]` view is read in place), `cos` and `sin` from `lsq_rope_tables` for the SAME `mid_dtype`
+    (float32 [P, R / 2]; R <= D: partial rotary, the features beyond R are only requantized), `positions` an int32 tensor [B] on x's
+    device (None: zeros) that is read in the kernel and never on the host, so a captured graph follows it: token (b, t) has the
+    position p = positions[b] + t.  Bit for bit HF's `x * cos + rotate_half(x) * sin` (`interleaved=True`: the pairs (2 i, 2 i + 1))
+    evaluated with torch ops on `x.dequantize(mid_dtype)`, every product and sum rounded to `mid_dtype`, then
+    `lsq_levels_per_tensor` of the output quantizer.  `out`: a uint8 / int8 tensor [B, Tout, H, D] with unit innermost stride to
+    write into -- the `.permute(0, 2, 1, 3)` view of a [B, H, Tmax, D] cache is one --, token t at output token t or, with
+    `scatter=True`, at output token p.  A TOKEN WITH p < 0 OR p >= P, OR WITH `scatter` p >= Tout, IS NOT WRITTEN AT ALL.  With
+    `out` the call goes to the host function directly, not through `torch.ops.torchlsq.lsq_rope_w8_q8_q`.  Returns a `LevelsTensor`
+    (with `out`: on that view).  Inference only."""
+    _assert_has_ops()
+    what = "lsq_rope_w8_q"
+    x = _levels_in(what, x)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    if out is None:
+        assert not scatter, "%s: scatter needs `out`" % what
+        lv = torch.ops.torchlsq.lsq_rope_w8_q8_q(*_rope_operand(x), cos, sin, *o[:6], mid_dtype, positions, bool(interleaved))
+    else:
+        from .extension import rope_w8_q
+        lv = rope_w8_q(*_rope_operand(x), cos, sin, *o[:6], mid_dtype, positions, bool(interleaved), out=out, scatter=scatter)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_rope_w8(x: LevelsTensor, cos: Tensor, sin: Tensor, out_dtype=torch.float32, positions: Tensor = None,
+                interleaved: bool = False) -> Tensor:
+    """`lsq_rope_w8_q` without an output quantizer: the rotated values as `out_dtype` floats [B, T, H, D] (the tables hold values of
+    `out_dtype`).  Inference only."""
+    _assert_has_ops()
+    x = _levels_in("lsq_rope_w8", x)
+    return torch.ops.torchlsq.lsq_rope_w8_q8(*_rope_operand(x), cos, sin, out_dtype, positions, bool(interleaved))
+
+
+def lsq_kv_append_w8(x: LevelsTensor, out: Tensor, positions: Tensor = None, scatter: bool = True) -> LevelsTensor:
+    """The KV-cache append on 8-bit levels, one launch and no arithmetic (liblsq_hip_rope_w8.so, COPY): x's levels [B, T, H, D] (v,
+    or a k that is rotated already) into `out` [B, Tout, H, D] of the same dtype -- the `.permute(0, 2, 1, 3)` view of a
+    [B, H, Tmax, D] cache --, token t at output token `positions[b] + t` (`scatter=False`: at t).  `positions` is int32 [B] on x's
+    device and read in the kernel.  A token whose position lies outside 0 .. Tout - 1 is not written.  Returns `out` as a
+    `LevelsTensor` with x's constants.  Inference only."""
+    _assert_has_ops()
+    x = _levels_in("lsq_kv_append_w8", x)
+    assert x.levels.dim() == 4, "lsq_kv_append_w8 needs levels of [B, T, H, D], got %s" % (tuple(x.shape),)
+    torch.ops.torchlsq.lsq_kv_copy_w8(x.levels, out, positions, bool(scatter))
+    return LevelsTensor(out, x.scale, x.zero_point, x.quant_min, x.quant_max, x.type_min, x.type_max)
