@@ -689,6 +689,39 @@ def rope_w8_library():
     return _require_companion(_ROPE_W8_LIB, "rope_w8", "rotary embedding and the KV-cache append on 8-bit levels need", rope_w8_error_str)
 
 
+# Decode attention on 8-bit levels against a grouped-query KV cache in one launch (include/lsq_hip_attn_decode_w8.h): a twentieth
+# companion library; the ABIs above stay as they are.
+class LsqAttnDecodeW8Geom(ctypes.Structure):
+    """lsq_attn_decode_w8_geom (include/lsq_hip_attn_decode_w8.h): the extents, the level dtypes, the mask and the strides of q, k, v
+    and y"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "H", "Hkv", "Tq", "Tk", "D", "q_dtype", "k_dtype", "v_dtype", "causal",
+                                                    "causal_offset", "has_lengths")] + \
+               [(name, LsqAttnW8Strides) for name in ("q", "k", "v", "y")]
+
+
+class LsqAttnDecodeW8Consts(ctypes.Structure):
+    """lsq_attn_decode_w8_consts (include/lsq_hip_attn_decode_w8.h): the scale and zero point of q, k, v and of the probabilities as an
+    operand, on the device"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_q", "z_q", "s_k", "z_k", "s_v", "z_v", "s_p", "z_p")]
+
+
+ATTN_DECODE_W8_ABI_VERSION = 1
+_ADGP = ctypes.POINTER(LsqAttnDecodeW8Geom)
+C_ABI_ATTN_DECODE_W8 = {
+    "lsq_attn_decode_w8_abi_version": (_int, []),
+    "lsq_attn_decode_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_attn_decode_w8": (_int, [_ADGP, ctypes.POINTER(LsqAttnDecodeW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_attn_decode_w8_plan": (_int, [_ADGP, _int, _int, _PLAN8]),
+}
+_ATTN_DECODE_W8_LIB, attn_decode_w8_error_str = _load_companion("liblsq_hip_attn_decode_w8.so", C_ABI_ATTN_DECODE_W8,
+                                                                "lsq_attn_decode_w8_abi_version", ATTN_DECODE_W8_ABI_VERSION)
+
+
+def attn_decode_w8_library():
+    """The ctypes handle of liblsq_hip_attn_decode_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_DECODE_W8_LIB, "attn_decode_w8", "decode attention on 8-bit levels needs", attn_decode_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -55,12 +55,13 @@ from ._attn_w8_host import (attn_w8_bmm, attn_w8_bmm_q, attn_w8_plan_bmm, attn_w
 from ._attn_fused_w8_host import attn_fused_w8_plan, attn_fused_w8_q  # noqa: F401
 from ._attn_mask_w8_host import attn_mask_w8_plan_softmax, attn_mask_w8_softmax, attn_mask_w8_softmax_q  # noqa: F401
 from ._rope_w8_host import rope_w8, rope_w8_kv_copy, rope_w8_plan, rope_w8_q  # noqa: F401
+from ._attn_decode_w8_host import attn_decode_w8_plan, attn_decode_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -255,6 +256,15 @@ _ROPE_POS = "Tensor? positions=None, bool interleaved=False"
 _lib_def.define("lsq_rope_w8_q8_q(%s, %s, %s) -> Tensor" % (_ROPE, _ATTN_OUT_Q, _ROPE_POS))
 _lib_def.define("lsq_rope_w8_q8(%s, ScalarType out_dtype, %s) -> Tensor" % (_ROPE, _ROPE_POS))
 _lib_def.define("lsq_kv_copy_w8(Tensor x_levels, Tensor(a!) out, Tensor? positions=None, bool scatter=True) -> ()")
+#  * DECODE ATTENTION on 8-bit LEVELS against a grouped-query KV cache (liblsq_hip_attn_decode_w8.so, include/lsq_hip_attn_decode_w8.h):
+#    q [B, H, Tq, D] against k, v [B, Hkv, Tk, D] with Hkv dividing H (query head h reads kv head h // G), the operands and sides of
+#    lsq_attention_w8_q8_q and the mask of lsq_softmax_mask_w8_q8_q (`key_lengths`: int32 [B]) -> the context's levels [B, Tq, H D].
+#    Keys at or beyond a row's count n take no part and are never read.  One launch where G Tq <= 16, D % 16 == 0, D <= 128,
+#    Tk <= 8192 and q, k, v are 16-byte aligned with strides that are multiples of 16; the existing ops composed elsewhere, with
+#    the same bytes.  Inference only.
+_lib_def.define("lsq_attention_decode_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
+                "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s) -> Tensor"
+                % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1118,3 +1128,25 @@ torch.library.register_fake("torchlsq::lsq_kv_copy_w8", _fake_kv_copy_w8, lib=_l
 _lib_def.impl("lsq_rope_w8_q8_q", _requant_no_grad("lsq_rope_w8_q8_q", (1, 3, 4, 5, 6)), "Autograd")
 _lib_def.impl("lsq_rope_w8_q8", _requant_no_grad("lsq_rope_w8_q8", (1, 3, 4)), "Autograd")
 _lib_def.impl("lsq_kv_copy_w8", _requant_no_grad("lsq_kv_copy_w8", ()), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# decode attention on 8-bit levels against a grouped-query KV cache (_attn_decode_w8_host.py): GPU tensors ->
+# liblsq_hip_attn_decode_w8.so (one call; the existing ops composed where the decode kernel does not serve the shape), CPU tensors ->
+# that composition; a shape-only kernel.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_attention_decode_w8_q8_q", attn_decode_w8_q)
+del _lib_key
+
+
+def _fake_attention_decode_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table, scores_scale,
+                                scores_shift, scores_quant_min, scores_quant_max, scores_type_min, scores_type_max, probs_scale, probs_shift,
+                                probs_quant_min, probs_quant_max, probs_type_min, probs_type_max, out_scale, out_shift, out_quant_min,
+                                out_quant_max, out_type_min, out_type_max, mid_dtype, causal=False, causal_offset=0, key_lengths=None):
+    B, H, Tq, D = q_levels.shape
+    return torch.empty((B, Tq, H * D), dtype=_fake_level_dtype(out_quant_max, out_type_max), device=q_levels.device)
+
+
+torch.library.register_fake("torchlsq::lsq_attention_decode_w8_q8_q", _fake_attention_decode_w8_q, lib=_lib_def)
+_lib_def.impl("lsq_attention_decode_w8_q8_q", _requant_no_grad("lsq_attention_decode_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")

@@ -1538,6 +1538,50 @@ def lsq_masked_softmax_w8_q(x: LevelsTensor, table: Tensor, out_scale: Tensor = 
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 
+def lsq_attention_decode_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor, table: Tensor, scores_out, probs_out, out,
+                              mid_dtype=torch.float32, causal=None, key_lengths: Tensor = None) -> LevelsTensor:
+    """DECODE attention on 8-bit levels against a grouped-query KV cache, one launch (liblsq_hip_attn_decode_w8.so): q
+    [B, H, Tq, D] `LevelsTensor` (a view of a qkv buffer is read in place) against k and v [B, Hkv, Tk, D] `LevelsTensor`s -- the
+    cache buffers of `KVCacheW8`, read in place -- with Hkv dividing H: query head h reads kv head h // (H / Hkv), HF's `repeat_kv`.
+    `table`, `scores_out`, `probs_out`, `out` and `mid_dtype` as in `lsq_attention_w8_q`; `causal` (None / False, True: the offset
+    Tk - Tq, or an int offset >= 0) and `key_lengths` (int32 [B] on q's device, read in the kernel and never on the host, so a
+    captured graph follows it) as in `lsq_masked_softmax_w8_q`.  Row (b, h, t) sees its first
+
+        n = min(Tk,  t + 1 + offset  where causal,  max(key_lengths[b], 0)  where key_lengths is given)
+
+    keys: its scores are `lsq_bmm_w8_q`'s bytes, its probabilities `lsq_masked_softmax_w8_q`'s bytes for that prefix, and the
+    context sums (p_j - z_p)(lv_j - z_v) over j < n ALONE -- keys at or beyond n take no part and their bytes are never read; a
+    row with n = 0 is `out`'s level of 0.0.  The result equals `AttentionCoreW8Q(causal=...)(q, k.repeat_interleave(G, 1),
+    v.repeat_interleave(G, 1), key_lengths)` BIT FOR BIT whenever the probabilities quantizer's level of 0.0 equals its zero point
+    as an operand (every quantizer with shift 0); where they differ, that route reads cache slots nobody wrote and this op does
+    not.  On the GPU one workgroup takes a (b, kv head) and the H / Hkv heads share its k and v reads where (H / Hkv) Tq <= 16,
+    D % 16 == 0, 16 <= D <= 128, Tk <= 8192 and q, k, v have 16-byte aligned bases and strides that are multiples of 16
+    (`torchlsq.extension.attn_decode_w8_plan` says which); every other input runs the existing ops composed, with the same bytes.
+    The CPU path is that composition and the GPU equals it bit for bit.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only."""
+    _assert_has_ops()
+    what = "lsq_attention_decode_w8_q"
+    q, k, v = _levels_in(what, q), _levels_in(what, k), _levels_in(what, v)
+    sides = []
+    for name, side in (("scores_out", scores_out), ("probs_out", probs_out), ("out", out)):
+        assert side is not None and len(side) == 6, "%s: %s must be (scale, shift, quant_min, quant_max, type_min, type_max)" % (what, name)
+        sides.append(_out_args("%s (%s)" % (what, name), *side, False))
+    on, off = False, 0
+    if causal is not None and causal is not False:
+        assert q.levels.dim() == 4 and k.levels.dim() == 4, "%s: q and k must have 4 axes, got %s and %s" % (what, tuple(q.shape), tuple(k.shape))
+        Tq, Tk = int(q.shape[2]), int(k.shape[2])
+        if causal is True:
+            assert Tk >= Tq, "%s: causal=True lets the last query see every key and needs Tk >= Tq, got Tq = %d and Tk = %d" % (what, Tq, Tk)
+            on, off = True, Tk - Tq
+        else:
+            assert isinstance(causal, int) and causal >= 0, "%s: causal must be None, a bool or an offset >= 0, got %r" % (what, causal)
+            on, off = True, int(causal)
+    lv = torch.ops.torchlsq.lsq_attention_decode_w8_q8_q(q.levels, q.scale, q.zero_point, k.levels, k.scale, k.zero_point, v.levels,
+                                                         v.scale, v.zero_point, table, *sides[0][:6], *sides[1][:6], *sides[2][:6],
+                                                         mid_dtype, on, off, key_lengths)
+    o = sides[2]
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
 def lsq_masked_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float32, causal=None, key_lengths: Tensor = None) -> Tensor:
     """`lsq_masked_softmax_w8_q` without an output quantizer: the probabilities rounded once to `out_dtype`, +0.0 beyond a row's
     prefix, in x's shape.  Inference only."""

@@ -11,12 +11,16 @@ The softmax is the package's own definition (include/lsq_hip_attn_w8.h), not ATe
 MASKS: `SoftmaxW8Q` and `AttentionCoreW8Q` take `causal=` at construction and `key_lengths=` in the forward; a masked
 call goes through `torchlsq.functional.lsq_masked_softmax_w8_q` (liblsq_hip_attn_mask_w8.so), an unmasked one through exactly the ops
 it went through before.
+
+DECODE: `AttentionCoreW8Q(decode=True)` sends every forward through `torchlsq.functional.lsq_attention_decode_w8_q`
+(liblsq_hip_attn_decode_w8.so): k and v may have fewer heads than q (grouped-query attention, read from the cache in place), one
+launch, and nothing at or beyond a row's key count is read.
 """
 import torch
 from torch import nn
 
-from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q, lsq_masked_softmax_w8,
-                                 lsq_masked_softmax_w8_q, lsq_softmax_table, lsq_softmax_w8, lsq_softmax_w8_q)
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_decode_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
+                                 lsq_masked_softmax_w8, lsq_masked_softmax_w8_q, lsq_softmax_table, lsq_softmax_w8, lsq_softmax_w8_q)
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import _MID_DTYPES, _as_levels
 
@@ -129,11 +133,22 @@ class AttentionCoreW8Q(nn.Module):
     launches, also with `fused=True`, and accepts k and v of [B, H, Tk, D] with Tk != Tq (decode: Tq = 1): the scores matmul still
     computes all Tk columns, the masked softmax writes the probability quantizer's level of 0 beyond a row's prefix, and p v is
     the existing matmul on those bytes.  With neither, nothing changes in bytes or in the ops called.
+
+    DECODE.  `decode=True` (opt-in; an attribute, not a buffer: the `state_dict` is the same) sends EVERY forward, masked or not,
+    through `torchlsq.functional.lsq_attention_decode_w8_q` with the same constants, the same table, `causal` and `key_lengths`:
+    k and v are [B, Hkv, Tk, D] with Hkv dividing H (query head h reads kv head h // (H / Hkv); the buffers of `KVCacheW8` as they
+    are), one launch where liblsq_hip_attn_decode_w8.so serves the shape, and keys at or beyond a row's count are never read.  The
+    bytes are those of `decode=False` on `repeat_interleave`d k and v whenever the probabilities quantizer's level of 0.0 equals its
+    zero point (shift 0).  With `decode=False` nothing changes, including the assertion that refuses Hkv != H.
     Inference only."""
 
-    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False, causal=False):
+    decode = False          # (the default of a module pickled before the attribute existed)
+
+    def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False, causal=False,
+                 decode=False):
         super().__init__()
         self.fused = bool(fused)
+        self.decode = bool(decode)
         self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
         self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16, causal=causal)
         self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
@@ -150,6 +165,9 @@ class AttentionCoreW8Q(nn.Module):
 
     def forward(self, q, k, v, key_lengths=None):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        if self.decode:
+            return lsq_attention_decode_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
+                                             self.context._out("output"), self.scores.mid_dtype, causal=self.causal, key_lengths=key_lengths)
         masked = key_lengths is not None or (self.causal is not None and self.causal is not False)
         if self.fused and not masked:
             return lsq_attention_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
@@ -173,6 +191,9 @@ class AttentionCoreW8Q(nn.Module):
         return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
 
     def extra_repr(self):
+        if self.decode:
+            return "decode=True (lsq_attention_decode_w8_q: one launch where the decode kernel serves the shape, grouped-query k and v)%s" \
+                % ("" if self.causal is None or self.causal is False else ", causal=%r" % (self.causal,))
         return "fused=%s (%s)%s" % (self.fused, "lsq_attention_w8_q: one launch where the fused kernel serves the shape" if self.fused
                                     else "three launches", "" if self.causal is None or self.causal is False
                                     else ", causal=%r: masked calls run three launches" % (self.causal,))
