@@ -722,6 +722,25 @@ def attn_decode_w8_library():
     return _require_companion(_ATTN_DECODE_W8_LIB, "attn_decode_w8", "decode attention on 8-bit levels needs", attn_decode_w8_error_str)
 
 
+# Prefill attention on 8-bit levels in one launch: causal and key-length masked, grouped-query, any number of query rows
+# (include/lsq_hip_attn_prefill_w8.h): a twenty-first companion library; the ABIs above stay as they are.  Its geometry and constants
+# are lsq_attn_decode_w8's structs.
+ATTN_PREFILL_W8_ABI_VERSION = 1
+C_ABI_ATTN_PREFILL_W8 = {
+    "lsq_attn_prefill_w8_abi_version": (_int, []),
+    "lsq_attn_prefill_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_attn_prefill_w8": (_int, [_ADGP, ctypes.POINTER(LsqAttnDecodeW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_attn_prefill_w8_plan": (_int, [_ADGP, _int, _int, _PLAN8]),
+}
+_ATTN_PREFILL_W8_LIB, attn_prefill_w8_error_str = _load_companion("liblsq_hip_attn_prefill_w8.so", C_ABI_ATTN_PREFILL_W8,
+                                                                  "lsq_attn_prefill_w8_abi_version", ATTN_PREFILL_W8_ABI_VERSION)
+
+
+def attn_prefill_w8_library():
+    """The ctypes handle of liblsq_hip_attn_prefill_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_PREFILL_W8_LIB, "attn_prefill_w8", "prefill attention on 8-bit levels needs", attn_prefill_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

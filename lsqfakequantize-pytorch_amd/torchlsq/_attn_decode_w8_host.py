@@ -37,8 +37,8 @@ _FAMILIES = ("composition", "decode")
 _ERR = "lsq_attn_decode_w8_last_error"
 
 
-def _plan_dict(out):
-    return dict(family=_FAMILIES[out[0]], grid=out[1], threads=out[2], rows=out[3], lds_row_stride=out[4], lds_bytes=out[5],
+def _plan_dict(out, families=_FAMILIES):
+    return dict(family=families[out[0]], grid=out[1], threads=out[2], rows=out[3], lds_row_stride=out[4], lds_bytes=out[5],
                 lds_dynamic=bool(out[6]), store=_STORES[out[7]])
 
 
@@ -73,16 +73,14 @@ def _compose(q, q_s, q_z, k, k_s, k_z, v, v_s, v_z, table, s_side, p_side, o_sid
     attn_w8_bmm_q(p, p_s, p_z, v, v_s, v_z, False, *o_side, mid_dtype, out=yv)
 
 
-def attn_decode_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table, scores_scale, scores_shift,
-                     scores_quant_min, scores_quant_max, scores_type_min, scores_type_max, probs_scale, probs_shift, probs_quant_min,
-                     probs_quant_max, probs_type_min, probs_type_max, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
-                     out_type_max, mid_dtype, causal=False, causal_offset=0, key_lengths=None, out=None):
-    """q [B, H, Tq, D], k and v [B, Hkv, Tk, D] levels (Hkv divides H) with their constants, the softmax `table`, the three output
-    quantizers and the mask -> the context's levels [B, Tq, H D] (uint8 or int8), written through their [B, H, Tq, D] view.  `out`
-    (not an argument of the op): a tensor [B, H, Tq, D] with unit innermost stride and rows that do not overlap to write into and
-    return instead; bytes outside it are not written."""
-    _assert_has_ops()
-    what = "lsq_attention_decode_w8_q8_q"
+class _Call:
+    """one checked call: the operands as the kernels read them, the sides, the mask, the geometry and where the result goes"""
+
+
+def _checked(what, q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table, s_side, p_side, o_side,
+             mid_dtype, causal, causal_offset, key_lengths, out):
+    """the operand checks of `attn_decode_w8_q`, which `_attn_prefill_w8_host.attn_prefill_w8_q` makes too (`what` names the op in
+    the messages), and the result's buffer -> a `_Call`; its `geom` is None where the result is empty"""
     q, k, v = q_levels, k_levels, v_levels
     for name, t in (("q", q), ("k", k), ("v", v)):
         _check(t.dtype in _LEVEL_CODE, "%s: the levels of %s must be uint8 (0..255) or int8 (-128..127), got '%s'" % (what, name, _name(t.dtype)))
@@ -104,47 +102,88 @@ def attn_decode_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_lev
         _check(key_lengths.dtype == torch.int32 and tuple(key_lengths.shape) == (B,) and key_lengths.is_contiguous(),
                "%s: key_lengths must be a dense int32 tensor of [%d], one entry per batch index, got '%s' %s"
                % (what, B, _name(key_lengths.dtype), tuple(key_lengths.shape)))
-    s_side = (scores_scale, scores_shift, int(scores_quant_min), int(scores_quant_max), int(scores_type_min), int(scores_type_max))
-    p_side = (probs_scale, probs_shift, int(probs_quant_min), int(probs_quant_max), int(probs_type_min), int(probs_type_max))
-    o_side = (out_scale, out_shift, int(out_quant_min), int(out_quant_max), int(out_type_min), int(out_type_max))
-    sdt, s_rng, _ = _check_out_q(what + " (scores)", s_side, mid_dtype)
-    _, p_rng, _ = _check_out_q(what + " (probabilities)", p_side, mid_dtype)
-    ydt, o_rng, _ = _check_out_q(what + " (context)", o_side, mid_dtype)
-    tensors = (q, k, v, q_scale, q_zero, k_scale, k_zero, v_scale, v_zero, table) + s_side[:2] + p_side[:2] + o_side[:2] + \
+    st = _Call()
+    st.s_side, st.p_side, st.o_side = (tuple(side[:2]) + tuple(int(n) for n in side[2:]) for side in (s_side, p_side, o_side))
+    st.sdt, st.s_rng, _ = _check_out_q(what + " (scores)", st.s_side, mid_dtype)
+    _, st.p_rng, _ = _check_out_q(what + " (probabilities)", st.p_side, mid_dtype)
+    ydt, st.o_rng, _ = _check_out_q(what + " (context)", st.o_side, mid_dtype)
+    tensors = (q, k, v, q_scale, q_zero, k_scale, k_zero, v_scale, v_zero, table) + st.s_side[:2] + st.p_side[:2] + st.o_side[:2] + \
         (() if key_lengths is None else (key_lengths,)) + (() if out is None else (out,))
-    on_gpu = _on_one_device(what, tensors)
+    st.on_gpu = _on_one_device(what, tensors)
     if out is None:
-        buf = torch.empty((B, Tq, H * D), dtype=ydt, device=q.device)
-        yv = buf.view(B, Tq, H, D).permute(0, 2, 1, 3)
+        st.buf = torch.empty((B, Tq, H * D), dtype=ydt, device=q.device)
+        st.yv = st.buf.view(B, Tq, H, D).permute(0, 2, 1, 3)
     else:
         _check(out.dtype == ydt and tuple(out.shape) == (B, H, Tq, D) and (D == 1 or out.stride(-1) == 1) and _rows_apart(out),
                "%s: `out` must be a %s tensor of shape %s whose innermost stride is 1 and whose rows do not overlap"
                % (what, _name(ydt), (B, H, Tq, D)))
-        buf = yv = out
-    if buf.numel() == 0:
-        return buf
+        st.buf = st.yv = out
+    st.geom = None
+    if st.buf.numel() == 0:
+        return st
     _check(Tk > 0, "%s: Tk = 0 is not served" % what)
-    q, k, v = _in_place(q, on_gpu), _in_place(k, on_gpu), _in_place(v, on_gpu)
-    geom = LsqAttnDecodeW8Geom(B, H, Hkv, Tq, Tk, D, _LEVEL_CODE[q.dtype], _LEVEL_CODE[k.dtype], _LEVEL_CODE[v.dtype], 1 if causal else 0,
-                               causal_offset, 0 if key_lengths is None else 1, _strides4(q), _strides4(k), _strides4(v), _strides4(yv))
-    lib = attn_decode_w8_library()
+    st.q, st.k, st.v = _in_place(q, st.on_gpu), _in_place(k, st.on_gpu), _in_place(v, st.on_gpu)
+    st.consts = (q_scale, q_zero, k_scale, k_zero, v_scale, v_zero)
+    st.table, st.mid_dtype, st.causal, st.causal_offset, st.key_lengths = table, mid_dtype, causal, causal_offset, key_lengths
+    st.geom = LsqAttnDecodeW8Geom(B, H, Hkv, Tq, Tk, D, _LEVEL_CODE[st.q.dtype], _LEVEL_CODE[st.k.dtype], _LEVEL_CODE[st.v.dtype],
+                                  1 if causal else 0, causal_offset, 0 if key_lengths is None else 1, _strides4(st.q), _strides4(st.k),
+                                  _strides4(st.v), _strides4(st.yv))
+    return st
+
+
+def _family(st, lib, plan_entry, families, what, err):
+    """the family the library's plan function names for a checked call (host only; it refuses an illegal shape with its message)"""
     plan = (ctypes.c_int32 * 8)()
-    _status(lib.lsq_attn_decode_w8_plan(ctypes.byref(geom), _aligned(q, k, v) if on_gpu else 1, _aligned(yv) if on_gpu else 1,
-                                        ctypes.byref(plan)), what, lib, _ERR)      # the shape's checks, and the family
-    if not on_gpu or _FAMILIES[plan[0]] != "decode":
-        _compose(q, q_scale, q_zero, k, k_scale, k_zero, v, v_scale, v_zero, table, s_side, p_side, o_side, mid_dtype, sdt, causal,
-                 causal_offset, key_lengths, yv)
-        return buf
-    p_s, p_z = _act_constants(probs_scale, probs_shift, p_rng[2], p_rng[3])
+    _status(getattr(lib, plan_entry)(ctypes.byref(st.geom), _aligned(st.q, st.k, st.v) if st.on_gpu else 1,
+                                     _aligned(st.yv) if st.on_gpu else 1, ctypes.byref(plan)), what, lib, err)
+    return families[plan[0]]
+
+
+def _launch(st, lib, entry, err):
+    """ONE ctypes call of a library's entry with lsq_attn_decode_w8's argument list on a checked call"""
+    p_s, p_z = _act_constants(st.p_side[0], st.p_side[1], st.p_rng[2], st.p_rng[3])
+    q_scale, q_zero, k_scale, k_zero, v_scale, v_zero = st.consts
     consts = LsqAttnDecodeW8Consts(q_scale.data_ptr(), q_zero.data_ptr(), k_scale.data_ptr(), k_zero.data_ptr(), v_scale.data_ptr(),
                                    v_zero.data_ptr(), p_s.data_ptr(), p_z.data_ptr())
-    idx = q.device.index
-    rc = _on_device(idx, lib.lsq_attn_decode_w8, ctypes.byref(geom), ctypes.byref(consts), ctypes.byref(_out_struct(s_side, s_rng, mid_dtype)),
-                    ctypes.byref(_out_struct(p_side, p_rng, mid_dtype)), ctypes.byref(_out_struct(o_side, o_rng, mid_dtype)),
-                    table.data_ptr(), None if key_lengths is None else key_lengths.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                    yv.data_ptr(), _stream_of(idx))
-    _status(rc, "lsq_attn_decode_w8", lib, _ERR)
-    return buf
+    idx = st.q.device.index
+    rc = _on_device(idx, getattr(lib, entry), ctypes.byref(st.geom), ctypes.byref(consts),
+                    ctypes.byref(_out_struct(st.s_side, st.s_rng, st.mid_dtype)), ctypes.byref(_out_struct(st.p_side, st.p_rng, st.mid_dtype)),
+                    ctypes.byref(_out_struct(st.o_side, st.o_rng, st.mid_dtype)), st.table.data_ptr(),
+                    None if st.key_lengths is None else st.key_lengths.data_ptr(), st.q.data_ptr(), st.k.data_ptr(), st.v.data_ptr(),
+                    st.yv.data_ptr(), _stream_of(idx))
+    _status(rc, entry, lib, err)
+
+
+def attn_decode_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table, scores_scale, scores_shift,
+                     scores_quant_min, scores_quant_max, scores_type_min, scores_type_max, probs_scale, probs_shift, probs_quant_min,
+                     probs_quant_max, probs_type_min, probs_type_max, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
+                     out_type_max, mid_dtype, causal=False, causal_offset=0, key_lengths=None, out=None, what="lsq_attention_decode_w8_q8_q"):
+    """q [B, H, Tq, D], k and v [B, Hkv, Tk, D] levels (Hkv divides H) with their constants, the softmax `table`, the three output
+    quantizers and the mask -> the context's levels [B, Tq, H D] (uint8 or int8), written through their [B, H, Tq, D] view.  `out`
+    (not an argument of the op): a tensor [B, H, Tq, D] with unit innermost stride and rows that do not overlap to write into and
+    return instead; bytes outside it are not written.  `what` (not an argument of the op): the op named in the messages."""
+    _assert_has_ops()
+    st = _checked(what, q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table,
+                  (scores_scale, scores_shift, scores_quant_min, scores_quant_max, scores_type_min, scores_type_max),
+                  (probs_scale, probs_shift, probs_quant_min, probs_quant_max, probs_type_min, probs_type_max),
+                  (out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max), mid_dtype, causal, causal_offset,
+                  key_lengths, out)
+    return _run(st, what)
+
+
+def _run(st, what):
+    """a checked call through the decode library: its kernel where its plan says "decode" on the GPU, the composition elsewhere"""
+    if st.geom is None:
+        return st.buf
+    lib = attn_decode_w8_library()
+    family = _family(st, lib, "lsq_attn_decode_w8_plan", _FAMILIES, what, _ERR)      # the shape's checks, and the family
+    if not st.on_gpu or family != "decode":
+        q_scale, q_zero, k_scale, k_zero, v_scale, v_zero = st.consts
+        _compose(st.q, q_scale, q_zero, st.k, k_scale, k_zero, st.v, v_scale, v_zero, st.table, st.s_side, st.p_side, st.o_side,
+                 st.mid_dtype, st.sdt, st.causal, st.causal_offset, st.key_lengths, st.yv)
+        return st.buf
+    _launch(st, lib, "lsq_attn_decode_w8", _ERR)
+    return st.buf
 
 
 def attn_decode_w8_plan(B, H, Hkv, Tq, Tk, D, q_strides=None, k_strides=None, v_strides=None, y_strides=None, qkv_aligned=True,

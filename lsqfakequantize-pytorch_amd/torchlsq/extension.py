@@ -56,12 +56,13 @@ from ._attn_fused_w8_host import attn_fused_w8_plan, attn_fused_w8_q  # noqa: F4
 from ._attn_mask_w8_host import attn_mask_w8_plan_softmax, attn_mask_w8_softmax, attn_mask_w8_softmax_q  # noqa: F401
 from ._rope_w8_host import rope_w8, rope_w8_kv_copy, rope_w8_plan, rope_w8_q  # noqa: F401
 from ._attn_decode_w8_host import attn_decode_w8_plan, attn_decode_w8_q  # noqa: F401
+from ._attn_prefill_w8_host import attn_prefill_w8_plan, attn_prefill_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -263,6 +264,14 @@ _lib_def.define("lsq_kv_copy_w8(Tensor x_levels, Tensor(a!) out, Tensor? positio
 #    Tk <= 8192 and q, k, v are 16-byte aligned with strides that are multiples of 16; the existing ops composed elsewhere, with
 #    the same bytes.  Inference only.
 _lib_def.define("lsq_attention_decode_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
+                "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s) -> Tensor"
+                % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
+#  * PREFILL ATTENTION on 8-bit LEVELS (liblsq_hip_attn_prefill_w8.so, include/lsq_hip_attn_prefill_w8.h): the arguments, the definition
+#    and the result of lsq_attention_decode_w8_q8_q for ANY number of query rows.  One launch of the decode kernel where G Tq <= 16; one
+#    launch of the prefill kernel -- a workgroup per (b, h, 64 rows), nothing above the diagonal computed -- where D % 16 == 0, D <= 128,
+#    min(Tk, Tq + causal_offset) (causal; else Tk) <= 2048 and q, k, v are 16-byte aligned with strides that are multiples of 16; the
+#    existing ops composed elsewhere, with the same bytes.  Inference only.
+_lib_def.define("lsq_attention_prefill_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
                 "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s) -> Tensor"
                 % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
 
@@ -1150,3 +1159,15 @@ def _fake_attention_decode_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_
 
 torch.library.register_fake("torchlsq::lsq_attention_decode_w8_q8_q", _fake_attention_decode_w8_q, lib=_lib_def)
 _lib_def.impl("lsq_attention_decode_w8_q8_q", _requant_no_grad("lsq_attention_decode_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# prefill attention on 8-bit levels (_attn_prefill_w8_host.py): GPU tensors -> liblsq_hip_attn_decode_w8.so where G Tq <= 16, else
+# liblsq_hip_attn_prefill_w8.so (one call each), else the existing ops composed; CPU tensors -> that composition; the decode op's
+# shape-only kernel.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_attention_prefill_w8_q8_q", attn_prefill_w8_q)
+del _lib_key
+torch.library.register_fake("torchlsq::lsq_attention_prefill_w8_q8_q", _fake_attention_decode_w8_q, lib=_lib_def)
+_lib_def.impl("lsq_attention_prefill_w8_q8_q", _requant_no_grad("lsq_attention_prefill_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")

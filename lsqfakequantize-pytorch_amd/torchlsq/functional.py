@@ -1558,8 +1558,13 @@ def lsq_attention_decode_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor,
     D % 16 == 0, 16 <= D <= 128, Tk <= 8192 and q, k, v have 16-byte aligned bases and strides that are multiples of 16
     (`torchlsq.extension.attn_decode_w8_plan` says which); every other input runs the existing ops composed, with the same bytes.
     The CPU path is that composition and the GPU equals it bit for bit.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only."""
+    return _attention_gqa_w8_q("lsq_attention_decode_w8_q", torch.ops.torchlsq.lsq_attention_decode_w8_q8_q, q, k, v, table, scores_out,
+                               probs_out, out, mid_dtype, causal, key_lengths)
+
+
+def _attention_gqa_w8_q(what, op, q, k, v, table, scores_out, probs_out, out, mid_dtype, causal, key_lengths):
+    """the argument handling `lsq_attention_decode_w8_q` and `lsq_attention_prefill_w8_q` share, and the call of their op"""
     _assert_has_ops()
-    what = "lsq_attention_decode_w8_q"
     q, k, v = _levels_in(what, q), _levels_in(what, k), _levels_in(what, v)
     sides = []
     for name, side in (("scores_out", scores_out), ("probs_out", probs_out), ("out", out)):
@@ -1575,11 +1580,27 @@ def lsq_attention_decode_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor,
         else:
             assert isinstance(causal, int) and causal >= 0, "%s: causal must be None, a bool or an offset >= 0, got %r" % (what, causal)
             on, off = True, int(causal)
-    lv = torch.ops.torchlsq.lsq_attention_decode_w8_q8_q(q.levels, q.scale, q.zero_point, k.levels, k.scale, k.zero_point, v.levels,
-                                                         v.scale, v.zero_point, table, *sides[0][:6], *sides[1][:6], *sides[2][:6],
-                                                         mid_dtype, on, off, key_lengths)
+    lv = op(q.levels, q.scale, q.zero_point, k.levels, k.scale, k.zero_point, v.levels, v.scale, v.zero_point, table, *sides[0][:6],
+            *sides[1][:6], *sides[2][:6], mid_dtype, on, off, key_lengths)
     o = sides[2]
     return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_attention_prefill_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor, table: Tensor, scores_out, probs_out, out,
+                               mid_dtype=torch.float32, causal=None, key_lengths: Tensor = None) -> LevelsTensor:
+    """PREFILL attention on 8-bit levels, one launch (liblsq_hip_attn_prefill_w8.so): the arguments, the `causal` conventions, the
+    definition and the result of `lsq_attention_decode_w8_q` -- q [B, H, Tq, D] against k and v [B, Hkv, Tk, D] with Hkv dividing H,
+    row (b, h, t) sees its first n = min(Tk, t + 1 + offset where causal, max(key_lengths[b], 0) where given) keys and nothing at or
+    beyond n is read -- for ANY number of query rows.  On the GPU, in this order: where (H / Hkv) Tq <= 16 and the decode kernel
+    serves the shape, that kernel (`lsq_attention_decode_w8_q` unchanged); else one launch of the prefill kernel -- a workgroup per
+    (b, h, 64 query rows), the scores and the probabilities in LDS, every key loop ended at the largest n of its rows, so the work
+    above the diagonal is not done and k and v are not repeated -- where D % 16 == 0, 16 <= D <= 128, q, k, v have 16-byte aligned
+    bases and strides that are multiples of 16 and min(Tk, Tq + offset) (causal; else Tk) <= 2048
+    (`torchlsq.extension.attn_prefill_w8_plan` says which; a long cache is served in place); every other input runs the existing
+    ops composed.  The bytes are the same on every route: the CPU path is `lsq_attention_decode_w8_q`'s and the GPU equals it bit
+    for bit.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only."""
+    return _attention_gqa_w8_q("lsq_attention_prefill_w8_q", torch.ops.torchlsq.lsq_attention_prefill_w8_q8_q, q, k, v, table, scores_out,
+                               probs_out, out, mid_dtype, causal, key_lengths)
 
 
 def lsq_masked_softmax_w8(x: LevelsTensor, table: Tensor, out_dtype=torch.float32, causal=None, key_lengths: Tensor = None) -> Tensor:

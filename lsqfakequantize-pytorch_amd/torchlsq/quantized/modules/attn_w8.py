@@ -15,11 +15,15 @@ it went through before.
 DECODE: `AttentionCoreW8Q(decode=True)` sends every forward through `torchlsq.functional.lsq_attention_decode_w8_q`
 (liblsq_hip_attn_decode_w8.so): k and v may have fewer heads than q (grouped-query attention, read from the cache in place), one
 launch, and nothing at or beyond a row's key count is read.
+
+PREFILL: `AttentionCoreW8Q(prefill=True)` sends every forward through `torchlsq.functional.lsq_attention_prefill_w8_q`
+(liblsq_hip_attn_prefill_w8.so): the same definition for any number of query rows -- the prompt in one launch of the prefill kernel,
+the steps in one launch of the decode kernel, through one module instance.
 """
 import torch
 from torch import nn
 
-from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_decode_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_decode_w8_q, lsq_attention_prefill_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
                                  lsq_masked_softmax_w8, lsq_masked_softmax_w8_q, lsq_softmax_table, lsq_softmax_w8, lsq_softmax_w8_q)
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import _MID_DTYPES, _as_levels
@@ -140,15 +144,24 @@ class AttentionCoreW8Q(nn.Module):
     are), one launch where liblsq_hip_attn_decode_w8.so serves the shape, and keys at or beyond a row's count are never read.  The
     bytes are those of `decode=False` on `repeat_interleave`d k and v whenever the probabilities quantizer's level of 0.0 equals its
     zero point (shift 0).  With `decode=False` nothing changes, including the assertion that refuses Hkv != H.
+
+    PREFILL.  `prefill=True` (opt-in; an attribute, not a buffer: the `state_dict` is the same) sends EVERY forward through
+    `torchlsq.functional.lsq_attention_prefill_w8_q` instead, with the same constants, table, `causal` and `key_lengths`: the
+    definition, the operands and the bytes of `decode=True` for any number of query rows.  On the GPU a prompt takes ONE launch of
+    liblsq_hip_attn_prefill_w8.so (no `repeat_interleave`, no score tensor in memory, nothing above the diagonal computed) and a
+    step with (H / Hkv) Tq <= 16 one launch of the decode kernel, so one module instance serves both (set `causal` per call: an
+    offset for the prompt, True for the steps).  With `prefill=False` nothing changes, for any combination of `fused` and `decode`.
     Inference only."""
 
     decode = False          # (the default of a module pickled before the attribute existed)
+    prefill = False         # (likewise)
 
     def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False, causal=False,
-                 decode=False):
+                 decode=False, prefill=False):
         super().__init__()
         self.fused = bool(fused)
         self.decode = bool(decode)
+        self.prefill = bool(prefill)
         self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
         self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16, causal=causal)
         self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
@@ -165,6 +178,9 @@ class AttentionCoreW8Q(nn.Module):
 
     def forward(self, q, k, v, key_lengths=None):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        if self.prefill:
+            return lsq_attention_prefill_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
+                                              self.context._out("output"), self.scores.mid_dtype, causal=self.causal, key_lengths=key_lengths)
         if self.decode:
             return lsq_attention_decode_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
                                              self.context._out("output"), self.scores.mid_dtype, causal=self.causal, key_lengths=key_lengths)
@@ -191,6 +207,9 @@ class AttentionCoreW8Q(nn.Module):
         return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
 
     def extra_repr(self):
+        if self.prefill:
+            return "prefill=True (lsq_attention_prefill_w8_q: one launch of the prefill or the decode kernel where they serve the shape, " \
+                "grouped-query k and v)%s" % ("" if self.causal is None or self.causal is False else ", causal=%r" % (self.causal,))
         if self.decode:
             return "decode=True (lsq_attention_decode_w8_q: one launch where the decode kernel serves the shape, grouped-query k and v)%s" \
                 % ("" if self.causal is None or self.causal is False else ", causal=%r" % (self.causal,))
