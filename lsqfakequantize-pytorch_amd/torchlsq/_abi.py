@@ -741,6 +741,29 @@ def attn_prefill_w8_library():
     return _require_companion(_ATTN_PREFILL_W8_LIB, "attn_prefill_w8", "prefill attention on 8-bit levels needs", attn_prefill_w8_error_str)
 
 
+# Split-key decode attention on 8-bit levels: one kv head's keys dealt to several workgroups, three launches and a caller-owned
+# workspace (include/lsq_hip_attn_decode_split_w8.h): a twenty-second companion library; the ABIs above stay as they are.  Its geometry
+# and constants are lsq_attn_decode_w8's structs.
+ATTN_DECODE_SPLIT_W8_ABI_VERSION = 1
+C_ABI_ATTN_DECODE_SPLIT_W8 = {
+    "lsq_attn_decode_split_w8_abi_version": (_int, []),
+    "lsq_attn_decode_split_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_attn_decode_split_w8_workspace": (_int, [_ADGP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "lsq_attn_decode_split_w8": (_int, [_ADGP, ctypes.POINTER(LsqAttnDecodeW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        ctypes.c_int64, ctypes.c_int64, _vp]),
+    "lsq_attn_decode_split_w8_plan": (_int, [_ADGP, _int, _int, ctypes.c_int64, _PLAN8]),
+}
+_ATTN_DECODE_SPLIT_W8_LIB, attn_decode_split_w8_error_str = _load_companion("liblsq_hip_attn_decode_split_w8.so", C_ABI_ATTN_DECODE_SPLIT_W8,
+                                                                            "lsq_attn_decode_split_w8_abi_version",
+                                                                            ATTN_DECODE_SPLIT_W8_ABI_VERSION)
+
+
+def attn_decode_split_w8_library():
+    """The ctypes handle of liblsq_hip_attn_decode_split_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_DECODE_SPLIT_W8_LIB, "attn_decode_split_w8", "split-key decode attention on 8-bit levels needs",
+                              attn_decode_split_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

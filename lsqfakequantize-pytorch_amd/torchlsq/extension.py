@@ -57,12 +57,13 @@ from ._attn_mask_w8_host import attn_mask_w8_plan_softmax, attn_mask_w8_softmax,
 from ._rope_w8_host import rope_w8, rope_w8_kv_copy, rope_w8_plan, rope_w8_q  # noqa: F401
 from ._attn_decode_w8_host import attn_decode_w8_plan, attn_decode_w8_q  # noqa: F401
 from ._attn_prefill_w8_host import attn_prefill_w8_plan, attn_prefill_w8_q  # noqa: F401
+from ._attn_decode_split_w8_host import attn_decode_split_w8_plan, attn_decode_split_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -274,6 +275,14 @@ _lib_def.define("lsq_attention_decode_w8_q8_q(Tensor q_levels, Tensor q_scale, T
 _lib_def.define("lsq_attention_prefill_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
                 "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s) -> Tensor"
                 % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
+#  * SPLIT-KEY DECODE ATTENTION on 8-bit LEVELS (liblsq_hip_attn_decode_split_w8.so, include/lsq_hip_attn_decode_split_w8.h): the arguments,
+#    the definition and the result of lsq_attention_decode_w8_q8_q plus `splits` -- 0: the library's choice; s >= 1: at most s splits --:
+#    one kv head's keys dealt to several workgroups, three launches and a workspace allocated per call, the SAME BYTES for every
+#    `splits`.  Served where G Tq <= 16, D % 16 == 0, D <= 128, Tk <= 65536 and q, k, v are 16-byte aligned with strides that are
+#    multiples of 16; the existing ops composed elsewhere.  Inference only.
+_lib_def.define("lsq_attention_decode_split_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
+                "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s, "
+                "int splits=0) -> Tensor" % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1171,3 +1180,27 @@ for _lib_key in (_lib_hip, _lib_cpu):
 del _lib_key
 torch.library.register_fake("torchlsq::lsq_attention_prefill_w8_q8_q", _fake_attention_decode_w8_q, lib=_lib_def)
 _lib_def.impl("lsq_attention_prefill_w8_q8_q", _requant_no_grad("lsq_attention_prefill_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# split-key decode attention on 8-bit levels (_attn_decode_split_w8_host.py): GPU tensors -> liblsq_hip_attn_decode_split_w8.so (one
+# call, three launches, a workspace from one torch.empty) where its plan says "split", else the existing ops composed; CPU tensors ->
+# that composition; the decode op's shape-only kernel.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_attention_decode_split_w8_q8_q", attn_decode_split_w8_q)
+del _lib_key
+
+
+def _fake_attention_decode_split_w8_q(q_levels, q_scale, q_zero, k_levels, k_scale, k_zero, v_levels, v_scale, v_zero, table, scores_scale,
+                                      scores_shift, scores_quant_min, scores_quant_max, scores_type_min, scores_type_max, probs_scale,
+                                      probs_shift, probs_quant_min, probs_quant_max, probs_type_min, probs_type_max, out_scale, out_shift,
+                                      out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype, causal=False, causal_offset=0,
+                                      key_lengths=None, splits=0):
+    B, H, Tq, D = q_levels.shape
+    return torch.empty((B, Tq, H * D), dtype=_fake_level_dtype(out_quant_max, out_type_max), device=q_levels.device)
+
+
+torch.library.register_fake("torchlsq::lsq_attention_decode_split_w8_q8_q", _fake_attention_decode_split_w8_q, lib=_lib_def)
+_lib_def.impl("lsq_attention_decode_split_w8_q8_q", _requant_no_grad("lsq_attention_decode_split_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)),
+              "Autograd")

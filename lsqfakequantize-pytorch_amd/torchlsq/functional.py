@@ -1539,7 +1539,7 @@ def lsq_masked_softmax_w8_q(x: LevelsTensor, table: Tensor, out_scale: Tensor = 
 
 
 def lsq_attention_decode_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor, table: Tensor, scores_out, probs_out, out,
-                              mid_dtype=torch.float32, causal=None, key_lengths: Tensor = None) -> LevelsTensor:
+                              mid_dtype=torch.float32, causal=None, key_lengths: Tensor = None, split=None) -> LevelsTensor:
     """DECODE attention on 8-bit levels against a grouped-query KV cache, one launch (liblsq_hip_attn_decode_w8.so): q
     [B, H, Tq, D] `LevelsTensor` (a view of a qkv buffer is read in place) against k and v [B, Hkv, Tk, D] `LevelsTensor`s -- the
     cache buffers of `KVCacheW8`, read in place -- with Hkv dividing H: query head h reads kv head h // (H / Hkv), HF's `repeat_kv`.
@@ -1557,12 +1557,42 @@ def lsq_attention_decode_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor,
     not.  On the GPU one workgroup takes a (b, kv head) and the H / Hkv heads share its k and v reads where (H / Hkv) Tq <= 16,
     D % 16 == 0, 16 <= D <= 128, Tk <= 8192 and q, k, v have 16-byte aligned bases and strides that are multiples of 16
     (`torchlsq.extension.attn_decode_w8_plan` says which); every other input runs the existing ops composed, with the same bytes.
-    The CPU path is that composition and the GPU equals it bit for bit.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only."""
-    return _attention_gqa_w8_q("lsq_attention_decode_w8_q", torch.ops.torchlsq.lsq_attention_decode_w8_q8_q, q, k, v, table, scores_out,
-                               probs_out, out, mid_dtype, causal, key_lengths)
+    The CPU path is that composition and the GPU equals it bit for bit.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only.
+
+    `split` (opt-in; None: everything above, untouched) deals one kv head's keys to several workgroups
+    (liblsq_hip_attn_decode_split_w8.so: three launches and a workspace allocated per call; served up to Tk = 65536) -- for small batches
+    against long caches, where one workgroup per (b, kv head) leaves most of the part idle.  The bytes are the same for every value:
+    every intermediate of the definition is a byte or an exact integer without a summation order.  An int >= 1 asks for at most that
+    many splits (never more than one per 64 keys; 1 is legal); "auto" takes the split form, with the library's own chunk, where the
+    single-launch kernel does not serve the shape but the split kernels do (Tk > 8192), or where B Hkv is at most the device's CU
+    count (the largest grid at which the split form was measured to win: DESIGN.md 9.22) and Tk is at least two chunks, and
+    today's path elsewhere (`torchlsq.extension.attn_decode_split_w8_plan(..., splits="auto")` says which)."""
+    what = "lsq_attention_decode_w8_q"
+    if split is None:
+        return _attention_gqa_w8_q(what, torch.ops.torchlsq.lsq_attention_decode_w8_q8_q, q, k, v, table, scores_out, probs_out, out,
+                                   mid_dtype, causal, key_lengths)
+    assert split == "auto" or (isinstance(split, int) and not isinstance(split, bool) and split >= 1), \
+        "%s: split must be None, \"auto\" or an int >= 1, got %r" % (what, split)
+    ql, kl = _levels_in(what, q).levels, _levels_in(what, k).levels
+    assert ql.dim() == 4 and kl.dim() == 4, "%s: q and k must have 4 axes, got %s and %s" % (what, tuple(ql.shape), tuple(kl.shape))
+    if split == "auto":
+        from ._attn_decode_split_w8_host import auto_splits
+        cus = torch.cuda.get_device_properties(ql.device).multi_processor_count if ql.is_cuda else None
+        vl = _levels_in(what, v).levels
+        aligned = all(t.data_ptr() % 16 == 0 for t in (ql, kl, vl))
+        strides = {n + "_strides": (t.stride(0), t.stride(1), t.stride(2)) for n, t in (("q", ql), ("k", kl), ("v", vl))}
+        if not (vl.dim() == 4 and kl.numel() and ql.numel() and kl.shape[1] and ql.shape[1] % kl.shape[1] == 0 and
+                auto_splits(ql.shape[0], ql.shape[1], kl.shape[1], ql.shape[2], kl.shape[2], ql.shape[3], cus, aligned, **strides)):
+            return _attention_gqa_w8_q(what, torch.ops.torchlsq.lsq_attention_decode_w8_q8_q, q, k, v, table, scores_out, probs_out, out,
+                                       mid_dtype, causal, key_lengths)
+        splits = 0
+    else:
+        splits = max(1, min(split, (int(kl.shape[2]) + 63) // 64))
+    return _attention_gqa_w8_q(what, torch.ops.torchlsq.lsq_attention_decode_split_w8_q8_q, q, k, v, table, scores_out, probs_out, out,
+                               mid_dtype, causal, key_lengths, (splits,))
 
 
-def _attention_gqa_w8_q(what, op, q, k, v, table, scores_out, probs_out, out, mid_dtype, causal, key_lengths):
+def _attention_gqa_w8_q(what, op, q, k, v, table, scores_out, probs_out, out, mid_dtype, causal, key_lengths, more=()):
     """the argument handling `lsq_attention_decode_w8_q` and `lsq_attention_prefill_w8_q` share, and the call of their op"""
     _assert_has_ops()
     q, k, v = _levels_in(what, q), _levels_in(what, k), _levels_in(what, v)
@@ -1581,7 +1611,7 @@ def _attention_gqa_w8_q(what, op, q, k, v, table, scores_out, probs_out, out, mi
             assert isinstance(causal, int) and causal >= 0, "%s: causal must be None, a bool or an offset >= 0, got %r" % (what, causal)
             on, off = True, int(causal)
     lv = op(q.levels, q.scale, q.zero_point, k.levels, k.scale, k.zero_point, v.levels, v.scale, v.zero_point, table, *sides[0][:6],
-            *sides[1][:6], *sides[2][:6], mid_dtype, on, off, key_lengths)
+            *sides[1][:6], *sides[2][:6], mid_dtype, on, off, key_lengths, *more)
     o = sides[2]
     return _levels_out(lv, o[0], o[1], o[2:6])
 

@@ -151,17 +151,26 @@ class AttentionCoreW8Q(nn.Module):
     liblsq_hip_attn_prefill_w8.so (no `repeat_interleave`, no score tensor in memory, nothing above the diagonal computed) and a
     step with (H / Hkv) Tq <= 16 one launch of the decode kernel, so one module instance serves both (set `causal` per call: an
     offset for the prompt, True for the steps).  With `prefill=False` nothing changes, for any combination of `fused` and `decode`.
+
+    SPLIT.  `split` (opt-in; an attribute, not a buffer: the `state_dict` is the same; None, "auto" or an int >= 1 as
+    in `lsq_attention_decode_w8_q`) sends a forward with (H / Hkv) Tq <= 16 through `lsq_attention_decode_w8_q(..., split=split)`,
+    whichever of `decode` / `prefill` is on: one kv head's keys dealt to several workgroups (liblsq_hip_attn_decode_split_w8.so), the
+    same bytes.  A forward with more rows, and every forward with `split=None`, goes where it went before.
     Inference only."""
 
     decode = False          # (the default of a module pickled before the attribute existed)
     prefill = False         # (likewise)
+    split = None            # (likewise)
 
     def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False, causal=False,
-                 decode=False, prefill=False):
+                 decode=False, prefill=False, split=None):
         super().__init__()
+        assert split is None or split == "auto" or (isinstance(split, int) and not isinstance(split, bool) and split >= 1), \
+            "AttentionCoreW8Q: split must be None, \"auto\" or an int >= 1, got %r" % (split,)
         self.fused = bool(fused)
         self.decode = bool(decode)
         self.prefill = bool(prefill)
+        self.split = split
         self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
         self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16, causal=causal)
         self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
@@ -178,6 +187,11 @@ class AttentionCoreW8Q(nn.Module):
 
     def forward(self, q, k, v, key_lengths=None):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        if self.split is not None and (self.decode or self.prefill) and q.levels.dim() == 4 and k.levels.dim() == 4 and k.shape[1] > 0 \
+                and q.shape[1] % k.shape[1] == 0 and q.shape[1] // k.shape[1] * q.shape[2] <= 16:
+            return lsq_attention_decode_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
+                                             self.context._out("output"), self.scores.mid_dtype, causal=self.causal, key_lengths=key_lengths,
+                                             split=self.split)
         if self.prefill:
             return lsq_attention_prefill_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
                                               self.context._out("output"), self.scores.mid_dtype, causal=self.causal, key_lengths=key_lengths)
@@ -207,6 +221,10 @@ class AttentionCoreW8Q(nn.Module):
         return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
 
     def extra_repr(self):
+        split = "" if self.split is None else ", split=%r (lsq_attention_decode_w8_q(split=...) where (H / Hkv) Tq <= 16)" % (self.split,)
+        return self._repr_route() + (split if self.decode or self.prefill else "")
+
+    def _repr_route(self):
         if self.prefill:
             return "prefill=True (lsq_attention_prefill_w8_q: one launch of the prefill or the decode kernel where they serve the shape, " \
                 "grouped-query k and v)%s" % ("" if self.causal is None or self.causal is False else ", causal=%r" % (self.causal,))
