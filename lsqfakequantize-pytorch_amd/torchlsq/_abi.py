@@ -764,6 +764,44 @@ def attn_decode_split_w8_library():
                               attn_decode_split_w8_error_str)
 
 
+# A paged KV cache on 8-bit levels: the append into pages of a pool and the split-key decode attention reading the pool through a
+# block table (include/lsq_hip_attn_paged_w8.h): a twenty-third companion library; the ABIs above stay as they are.  The decode's
+# geometry and constants are lsq_attn_decode_w8's structs, the geometry's k and v strides being the pools' (page, head, slot).
+class LsqAttnPagedW8Pages(ctypes.Structure):
+    """lsq_attn_paged_w8_pages (include/lsq_hip_attn_paged_w8.h): the pages of a pool, the slots of a page, the entries of a block
+    table row and the row stride of the block table"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("Np", "ps", "Mp", "bt_ld")]
+
+
+class LsqKvAppendPagedW8Geom(ctypes.Structure):
+    """lsq_kv_append_paged_w8_geom (include/lsq_hip_attn_paged_w8.h): the sources' extents and strides, the pages and the pools' strides"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "T", "Hkv", "D")] + [("pages", LsqAttnPagedW8Pages)] + \
+               [(name, ctypes.c_int64) for name in ("k_sb", "k_st", "k_sh", "v_sb", "v_st", "v_sh", "kp_sp", "kp_sh", "kp_ss", "vp_sp",
+                                                    "vp_sh", "vp_ss")]
+
+
+ATTN_PAGED_W8_ABI_VERSION = 1
+_APPP = ctypes.POINTER(LsqAttnPagedW8Pages)
+_KAGP = ctypes.POINTER(LsqKvAppendPagedW8Geom)
+C_ABI_ATTN_PAGED_W8 = {
+    "lsq_attn_paged_w8_abi_version": (_int, []),
+    "lsq_attn_paged_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_attn_paged_w8_workspace": (_int, [_ADGP, _APPP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "lsq_attn_paged_w8_decode": (_int, [_ADGP, _APPP, ctypes.POINTER(LsqAttnDecodeW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    "lsq_attn_paged_w8_plan": (_int, [_ADGP, _APPP, _int, _int, ctypes.c_int64, _PLAN8]),
+    "lsq_kv_append_paged_w8": (_int, [_KAGP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_kv_append_paged_w8_plan": (_int, [_KAGP, _int, _PLAN8]),
+}
+_ATTN_PAGED_W8_LIB, attn_paged_w8_error_str = _load_companion("liblsq_hip_attn_paged_w8.so", C_ABI_ATTN_PAGED_W8,
+                                                              "lsq_attn_paged_w8_abi_version", ATTN_PAGED_W8_ABI_VERSION)
+
+
+def attn_paged_w8_library():
+    """The ctypes handle of liblsq_hip_attn_paged_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_PAGED_W8_LIB, "attn_paged_w8", "the paged KV cache on 8-bit levels needs", attn_paged_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

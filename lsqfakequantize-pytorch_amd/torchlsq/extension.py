@@ -58,12 +58,14 @@ from ._rope_w8_host import rope_w8, rope_w8_kv_copy, rope_w8_plan, rope_w8_q  # 
 from ._attn_decode_w8_host import attn_decode_w8_plan, attn_decode_w8_q  # noqa: F401
 from ._attn_prefill_w8_host import attn_prefill_w8_plan, attn_prefill_w8_q  # noqa: F401
 from ._attn_decode_split_w8_host import attn_decode_split_w8_plan, attn_decode_split_w8_q  # noqa: F401
+from ._attn_paged_w8_host import (attn_paged_w8_plan, attn_paged_w8_q, kv_append_paged_w8, kv_append_paged_w8_plan,  # noqa: F401
+                                  kv_gather_paged_w8)
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -283,6 +285,20 @@ _lib_def.define("lsq_attention_prefill_w8_q8_q(Tensor q_levels, Tensor q_scale, 
 _lib_def.define("lsq_attention_decode_split_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
                 "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s, "
                 "int splits=0) -> Tensor" % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
+#  * The PAGED KV CACHE on 8-bit LEVELS (liblsq_hip_attn_paged_w8.so, include/lsq_hip_attn_paged_w8.h): the arguments and the result of
+#    lsq_attention_decode_split_w8_q8_q with the POOLS [Np, Hkv, ps, D] in place of k and v and `block_table` int32 [B, Mp] on their
+#    device: key j of batch entry b lies in page clamp(block_table[b, j // ps], 0, Np - 1) at slot j % ps, and the result is
+#    lsq_attention_decode_w8_q8_q's on the caches so gathered -- without gathering them where R = G Tq <= 16, D % 16 == 0, D <= 128, ps is
+#    a power of two >= 16, Mp ps <= 65536 and q and the pools are 16-byte aligned with strides that are multiples of 16; the gather
+#    and the existing ops composed elsewhere, with the same bytes.  `lsq_kv_append_paged_w8` writes a step's k and v [B, T, Hkv, D]
+#    into the pools at positions[b] + t in one launch; a token outside the table's capacity or with an entry outside [0, Np) is not
+#    written.  Inference only.
+_lib_def.define("lsq_attention_decode_paged_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_pool, Tensor k_scale, "
+                "Tensor k_zero, Tensor v_pool, Tensor v_scale, Tensor v_zero, Tensor block_table, Tensor table, %s, %s, %s, "
+                "ScalarType mid_dtype, %s, int splits=0) -> Tensor"
+                % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
+_lib_def.define("lsq_kv_append_paged_w8(Tensor k_levels, Tensor v_levels, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
+                "Tensor? positions=None) -> ()")
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1204,3 +1220,35 @@ def _fake_attention_decode_split_w8_q(q_levels, q_scale, q_zero, k_levels, k_sca
 torch.library.register_fake("torchlsq::lsq_attention_decode_split_w8_q8_q", _fake_attention_decode_split_w8_q, lib=_lib_def)
 _lib_def.impl("lsq_attention_decode_split_w8_q8_q", _requant_no_grad("lsq_attention_decode_split_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)),
               "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the paged KV cache on 8-bit levels (_attn_paged_w8_host.py): GPU tensors -> liblsq_hip_attn_paged_w8.so (the decode: one call, three
+# launches, a workspace from one torch.empty where its plan says "paged", else the gather and the existing ops composed; the append:
+# one call, one launch); CPU tensors -> the gather and that composition, and plain index assignment; a shape-only kernel each.
+# Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_attention_decode_paged_w8_q8_q", attn_paged_w8_q)
+    _lib_key.impl("lsq_kv_append_paged_w8", kv_append_paged_w8)
+del _lib_key
+
+
+def _fake_attention_decode_paged_w8_q(q_levels, q_scale, q_zero, k_pool, k_scale, k_zero, v_pool, v_scale, v_zero, block_table, table,
+                                      scores_scale, scores_shift, scores_quant_min, scores_quant_max, scores_type_min, scores_type_max,
+                                      probs_scale, probs_shift, probs_quant_min, probs_quant_max, probs_type_min, probs_type_max, out_scale,
+                                      out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype, causal=False,
+                                      causal_offset=0, key_lengths=None, splits=0):
+    B, H, Tq, D = q_levels.shape
+    return torch.empty((B, Tq, H * D), dtype=_fake_level_dtype(out_quant_max, out_type_max), device=q_levels.device)
+
+
+def _fake_kv_append_paged_w8(k_levels, v_levels, k_pool, v_pool, block_table, positions=None):
+    return None
+
+
+torch.library.register_fake("torchlsq::lsq_attention_decode_paged_w8_q8_q", _fake_attention_decode_paged_w8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_kv_append_paged_w8", _fake_kv_append_paged_w8, lib=_lib_def)
+_lib_def.impl("lsq_attention_decode_paged_w8_q8_q", _requant_no_grad("lsq_attention_decode_paged_w8_q8_q", (1, 4, 7, 11, 12, 17, 18, 23, 24)),
+              "Autograd")
+_lib_def.impl("lsq_kv_append_paged_w8", _requant_no_grad("lsq_kv_append_paged_w8", ()), "Autograd")

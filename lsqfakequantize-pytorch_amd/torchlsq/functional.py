@@ -1710,3 +1710,82 @@ def lsq_kv_append_w8(x: LevelsTensor, out: Tensor, positions: Tensor = None, sca
     assert x.levels.dim() == 4, "lsq_kv_append_w8 needs levels of [B, T, H, D], got %s" % (tuple(x.shape),)
     torch.ops.torchlsq.lsq_kv_copy_w8(x.levels, out, positions, bool(scatter))
     return LevelsTensor(out, x.scale, x.zero_point, x.quant_min, x.quant_max, x.type_min, x.type_max)
+
+
+def lsq_kv_gather_paged_w8(pool: LevelsTensor, block_table: Tensor) -> LevelsTensor:
+    """The dense cache a block table names: `pool` a `LevelsTensor` [Np, Hkv, ps, D] (any view with unit innermost
+    stride), `block_table` int32 [B, Mp] on its device -> a `LevelsTensor` [B, Hkv, Mp ps, D] with
+
+        result[b, hkv, j, :] = pool[clamp(block_table[b, j // ps], 0, Np - 1), hkv, j % ps, :]
+
+    in torch ops, nothing is read back.  It is the DEFINITION of the paged layout, the route a paged user had before
+    `lsq_attention_decode_paged_w8_q`, and the way back to a dense cache.  Inference only."""
+    _assert_has_ops()
+    pool = _levels_in("lsq_kv_gather_paged_w8", pool)
+    return LevelsTensor(_E.kv_gather_paged_w8(pool.levels, block_table), pool.scale, pool.zero_point, pool.quant_min, pool.quant_max,
+                        pool.type_min, pool.type_max)
+
+
+def lsq_attention_decode_paged_w8_q(q: LevelsTensor, k_pool: LevelsTensor, v_pool: LevelsTensor, block_table: Tensor, table: Tensor,
+                                    scores_out, probs_out, out, mid_dtype=torch.float32, causal=None, key_lengths: Tensor = None,
+                                    splits: int = 0) -> LevelsTensor:
+    """DECODE attention on 8-bit levels against a PAGED KV cache (liblsq_hip_attn_paged_w8.so): q [B, H, Tq, D] `LevelsTensor` against
+    the pools `k_pool` and `v_pool`, `LevelsTensor`s [Np, Hkv, ps, D] (Hkv dividing H; any view with unit innermost stride, so the
+    storage order [Np, ps, Hkv, D] too) through `block_table`, int32 [B, Mp] on their device, read in the kernels and never on the
+    host, so a captured graph follows it.  The logical capacity is Tk = Mp ps <= 65536 keys and key j of batch entry b lies in page
+    clamp(block_table[b, j // ps], 0, Np - 1) at slot j % ps: READS CLAMP, a wrong entry never leaves the pool.  The result is
+
+        lsq_attention_decode_w8_q(q, lsq_kv_gather_paged_w8(k_pool, block_table), lsq_kv_gather_paged_w8(v_pool, block_table), ...)
+
+    BIT FOR BIT, with the same `table`, sides, `mid_dtype`, `causal` (True: the offset Tk - Tq with this Tk) and `key_lengths` -- and
+    that IS the CPU path.  Entries at logical pages at or beyond ceil(n / ps) and pool bytes at keys at or beyond a batch entry's
+    largest key count are never read.  On the GPU no page is copied where (H / Hkv) Tq <= 16, D % 16 == 0, 16 <= D <= 128, ps is a power
+    of two >= 16 and q and the pools have 16-byte aligned bases and strides that are multiples of 16: the three launches of the
+    split-key decode with a workspace allocated per call (`torchlsq.extension.attn_paged_w8_plan` says which); every other input is
+    gathered and composed, with the same bytes.  `splits`: 0 the library's own chunk, s >= 1 at most s splits (clamped to one per 64
+    keys); the bytes are the same for every value.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only."""
+    what = "lsq_attention_decode_paged_w8_q"
+    _assert_has_ops()
+    q, k_pool, v_pool = _levels_in(what, q), _levels_in(what, k_pool), _levels_in(what, v_pool)
+    assert isinstance(splits, int) and not isinstance(splits, bool) and splits >= 0, "%s: splits must be an int >= 0, got %r" % (what, splits)
+    assert q.levels.dim() == 4 and k_pool.levels.dim() == 4 and block_table.dim() == 2, \
+        "%s: q must be [B, H, Tq, D], the pools [Np, Hkv, ps, D] and block_table [B, Mp], got %s, %s and %s" \
+        % (what, tuple(q.shape), tuple(k_pool.shape), tuple(block_table.shape))
+    sides = []
+    for name, side in (("scores_out", scores_out), ("probs_out", probs_out), ("out", out)):
+        assert side is not None and len(side) == 6, "%s: %s must be (scale, shift, quant_min, quant_max, type_min, type_max)" % (what, name)
+        sides.append(_out_args("%s (%s)" % (what, name), *side, False))
+    Tq, Tk = int(q.shape[2]), int(block_table.shape[1]) * int(k_pool.shape[2])
+    on, off = False, 0
+    if causal is not None and causal is not False:
+        if causal is True:
+            assert Tk >= Tq, "%s: causal=True lets the last query see every key and needs Mp ps >= Tq, got Tq = %d and %d" % (what, Tq, Tk)
+            on, off = True, Tk - Tq
+        else:
+            assert isinstance(causal, int) and causal >= 0, "%s: causal must be None, a bool or an offset >= 0, got %r" % (what, causal)
+            on, off = True, int(causal)
+    splits = min(splits, (Tk + 63) // 64)
+    lv = torch.ops.torchlsq.lsq_attention_decode_paged_w8_q8_q(q.levels, q.scale, q.zero_point, k_pool.levels, k_pool.scale, k_pool.zero_point,
+                                                               v_pool.levels, v_pool.scale, v_pool.zero_point, block_table, table,
+                                                               *sides[0][:6], *sides[1][:6], *sides[2][:6], mid_dtype, on, off, key_lengths,
+                                                               splits)
+    o = sides[2]
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_kv_append_paged_w8(k: LevelsTensor, v: LevelsTensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, positions: Tensor = None):
+    """The append into a PAGED KV cache, k and v in one launch and no arithmetic (liblsq_hip_attn_paged_w8.so): the levels of k and v
+    [B, T, Hkv, D] (views of a qkv buffer are read in place; v, and a k that is rotated already) into the pools `k_pool` and `v_pool`
+    [Np, Hkv, ps, D] of the same dtypes through `block_table` int32 [B, Mp]: token (b, t) at p = positions[b] + t (`positions`: int32
+    [B] on the device, read in the kernel; None: zeros) goes to page block_table[b, p // ps], slot p % ps.  WRITES SKIP, they do not
+    clamp: a token with p < 0, p >= Mp ps or an entry outside [0, Np) is not written at all.  Two tokens of one call that name the
+    same physical slot are the caller's error (which bytes win is undefined).  Returns the pools as `LevelsTensor`s with k's and v's
+    constants.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_kv_append_paged_w8"
+    k, v = _levels_in(what, k), _levels_in(what, v)
+    assert k.levels.dim() == 4 and v.levels.dim() == 4, "%s needs levels of [B, T, Hkv, D], got %s and %s" % (what, tuple(k.shape), tuple(v.shape))
+    k_pool, v_pool = (p.levels if isinstance(p, LevelsTensor) else p for p in (k_pool, v_pool))      # (the pools a previous append returned)
+    torch.ops.torchlsq.lsq_kv_append_paged_w8(k.levels, v.levels, k_pool, v_pool, block_table, positions)
+    return (LevelsTensor(k_pool, k.scale, k.zero_point, k.quant_min, k.quant_max, k.type_min, k.type_max),
+            LevelsTensor(v_pool, v.scale, v.zero_point, v.quant_min, v.quant_max, v.type_min, v.type_max))

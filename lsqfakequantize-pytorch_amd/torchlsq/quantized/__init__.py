@@ -22,6 +22,7 @@ from .modules.eltwise_w8 import ActivationW8Q, MulGateW8Q, convert_w8a8_eltwise 
 from .modules.norm_w8 import LayerNormW8Q, RMSNormW8Q, convert_w8a8_norm  # noqa: F401
 from .modules.attn_w8 import AttentionCoreW8Q, MatmulW8Q, SoftmaxW8Q  # noqa: F401
 from .modules.rope_w8 import KVCacheW8, RotaryW8Q  # noqa: F401
+from .modules.paged_kv_w8 import PagedKVCacheW8  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
@@ -123,5 +124,5 @@ __all__ = ["LSQFakeQuantizer", "LSQWeightGroup", "PackedLinear", "PackedLinearA8
            "LinearW8A8AddQ", "Conv2dW8A8AddQ", "AddW8A8Q", "convert_w8a8_add_q",
            "MaxPool2dW8", "AvgPool2dW8Q", "AdaptiveAvgPool2dW8Q", "convert_w8a8_pool",
            "DepthwiseConv2dW8A8Q", "convert_w8a8_depthwise", "LayerNormW8Q", "RMSNormW8Q", "convert_w8a8_norm", "AttentionCoreW8Q", "MatmulW8Q", "SoftmaxW8Q",
-           "RotaryW8Q", "KVCacheW8",
+           "RotaryW8Q", "KVCacheW8", "PagedKVCacheW8",
            "enable_rank_sync", "prepare_ddp"] + [row[0] for row in _TABLE]

@@ -23,7 +23,7 @@ the steps in one launch of the decode kernel, through one module instance.
 import torch
 from torch import nn
 
-from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_decode_w8_q, lsq_attention_prefill_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_decode_paged_w8_q, lsq_attention_decode_w8_q, lsq_attention_prefill_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
                                  lsq_masked_softmax_w8, lsq_masked_softmax_w8_q, lsq_softmax_table, lsq_softmax_w8, lsq_softmax_w8_q)
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import _MID_DTYPES, _as_levels
@@ -156,6 +156,12 @@ class AttentionCoreW8Q(nn.Module):
     in `lsq_attention_decode_w8_q`) sends a forward with (H / Hkv) Tq <= 16 through `lsq_attention_decode_w8_q(..., split=split)`,
     whichever of `decode` / `prefill` is on: one kv head's keys dealt to several workgroups (liblsq_hip_attn_decode_split_w8.so), the
     same bytes.  A forward with more rows, and every forward with `split=None`, goes where it went before.
+
+    PAGED.  `forward(q, k, v, key_lengths=None, block_table=None)`: with a `block_table` (int32 [B, Mp] on q's device)
+    and `decode` or `prefill` on, k and v are the POOLS of a paged cache, `LevelsTensor`s [Np, Hkv, ps, D] (`PagedKVCacheW8`'s), and
+    the forward goes through `lsq_attention_decode_paged_w8_q` (liblsq_hip_attn_paged_w8.so) with the same constants, table, `causal`
+    and `key_lengths`; `split`, where it is an int, gives `splits`, otherwise `splits` is 0 (the library's chunk).  Without a block
+    table nothing changes.
     Inference only."""
 
     decode = False          # (the default of a module pickled before the attribute existed)
@@ -185,8 +191,14 @@ class AttentionCoreW8Q(nn.Module):
     def causal(self, value):
         self.softmax.causal = value
 
-    def forward(self, q, k, v, key_lengths=None):
+    def forward(self, q, k, v, key_lengths=None, block_table=None):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        if block_table is not None:
+            assert self.decode or self.prefill, "AttentionCoreW8Q: a block_table (paged k and v) needs decode=True or prefill=True"
+            splits = self.split if isinstance(self.split, int) and not isinstance(self.split, bool) else 0
+            return lsq_attention_decode_paged_w8_q(q, k, v, block_table, self.softmax.table, self.scores._out("output"),
+                                                   self.softmax._out("output"), self.context._out("output"), self.scores.mid_dtype,
+                                                   causal=self.causal, key_lengths=key_lengths, splits=splits)
         if self.split is not None and (self.decode or self.prefill) and q.levels.dim() == 4 and k.levels.dim() == 4 and k.shape[1] > 0 \
                 and q.shape[1] % k.shape[1] == 0 and q.shape[1] // k.shape[1] * q.shape[2] <= 16:
             return lsq_attention_decode_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
