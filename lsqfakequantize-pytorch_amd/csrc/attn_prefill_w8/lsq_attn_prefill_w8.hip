@@ -27,7 +27,7 @@
 #include "../lsq_companion_abi.hpp"
 #include "../qlinear_w8/lsq_w8_shared.hpp"
 #include "../attn_w8/lsq_attn_w8_dev.hpp"
-#include "../attn_w8/lsq_attn_w8_checks.hpp"
+#include "../attn_w8/lsq_attn_decode_checks.hpp"
 #include "../../../include/lsq_hip_attn_prefill_w8.h"
 
 namespace lsq {
@@ -325,8 +325,6 @@ struct PrePlan {
     PreGeom g;
 };
 
-inline bool strides16(const lsq_attn_w8_strides& s) { return s.s0 % 16 == 0 && s.s1 % 16 == 0 && s.ld % 16 == 0; }
-
 inline PrePlan plan_prefill(const lsq_attn_decode_w8_geom& ge, bool qkv_aligned, bool y_aligned) {
     PrePlan pl = {};
     pl.family = LSQ_ATTN_PREFILL_W8_COMPOSITION;
@@ -357,52 +355,6 @@ inline PrePlan plan_prefill(const lsq_attn_decode_w8_geom& ge, bool qkv_aligned,
 // ------------------------------------------------------------------------------------------------
 // the C ABI of include/lsq_hip_attn_prefill_w8.h: validation, error bookkeeping
 // ------------------------------------------------------------------------------------------------
-namespace {
-
-int check_prefill_geom(const char* what, const lsq_attn_decode_w8_geom* g) {
-    if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
-    if (!level_dtype(g->q_dtype) || !level_dtype(g->k_dtype) || !level_dtype(g->v_dtype))
-        return fail(LSQ_EINVAL, "%s: q_dtype, k_dtype and v_dtype must be LSQ_ATTN_W8_U8 (0) or LSQ_ATTN_W8_I8 (1), got %lld, %lld and %lld",
-                    what, static_cast<ll>(g->q_dtype), static_cast<ll>(g->k_dtype), static_cast<ll>(g->v_dtype));
-    if (g->B < 1 || g->H < 1 || g->Hkv < 1 || g->Tq < 1 || g->Tk < 1 || g->D < 1)
-        return fail(LSQ_EINVAL, "%s: [B, H, Hkv, Tq, Tk, D] = [%lld, %lld, %lld, %lld, %lld, %lld], every extent must be at least 1", what,
-                    static_cast<ll>(g->B), static_cast<ll>(g->H), static_cast<ll>(g->Hkv), static_cast<ll>(g->Tq), static_cast<ll>(g->Tk),
-                    static_cast<ll>(g->D));
-    if (g->H % g->Hkv != 0)
-        return fail(LSQ_EINVAL, "%s: H = %lld query heads are not a multiple of Hkv = %lld kv heads", what, static_cast<ll>(g->H),
-                    static_cast<ll>(g->Hkv));
-    if (g->causal && g->causal_offset < 0)
-        return fail(LSQ_EINVAL, "%s: causal_offset = %lld must be at least 0", what, static_cast<ll>(g->causal_offset));
-    if (g->D > LSQ_ATTN_W8_MAX_K || g->Tk > LSQ_ATTN_W8_MAX_K)
-        return fail(LSQ_EINVAL, "%s: D = %lld and Tk = %lld, at most %d are served (the raw sums stay in 32 bits)", what, static_cast<ll>(g->D),
-                    static_cast<ll>(g->Tk), LSQ_ATTN_W8_MAX_K);
-    const int64_t lim = int64_t{1} << 20;
-    if (g->Tq > lim || g->B > lim || g->H > lim || g->B * g->H > lim)
-        return fail(LSQ_EINVAL, "%s: Tq = %lld and B * H = %lld x %lld may each be 2^20 at most", what, static_cast<ll>(g->Tq),
-                    static_cast<ll>(g->B), static_cast<ll>(g->H));
-    if (int rc = check_strides(what, "q", g->q, g->D)) return rc;
-    if (int rc = check_strides(what, "k", g->k, g->D)) return rc;
-    if (int rc = check_strides(what, "v", g->v, g->D)) return rc;
-    if (int rc = check_strides(what, "y", g->y, g->D)) return rc;
-    if (self_overlap(g->y, g->B, g->H, g->Tq, g->D))
-        return fail(LSQ_EINVAL, "%s: y's rows or batches overlap each other (strides %lld, %lld, %lld for [%lld, %lld, %lld, %lld])", what,
-                    static_cast<ll>(g->y.s0), static_cast<ll>(g->y.s1), static_cast<ll>(g->y.ld), static_cast<ll>(g->B),
-                    static_cast<ll>(g->H), static_cast<ll>(g->Tq), static_cast<ll>(g->D));
-    return LSQ_OK;
-}
-
-// a side of the prefill op is a quantizer: levels out only
-int check_side(const char* what, const char* name, const lsq_attn_w8_out* c, lsq::AttnOut& arg) {
-    int64_t y_elem = 1;
-    if (int rc = check_out(what, c, arg, y_elem)) return rc;
-    if (!c->out_scale) return fail(LSQ_EINVAL, "%s: the %s side needs out_scale and out_shift (levels out only)", what, name);
-    return LSQ_OK;
-}
-
-int side_off(const lsq_attn_w8_out* c) { return std::max(c->quant_max, c->type_max) > 127 ? 128 : 0; }
-
-}  // namespace
-
 extern "C" {
 
 int lsq_attn_prefill_w8_abi_version(void) { return LSQ_ATTN_PREFILL_W8_ABI_VERSION; }
@@ -414,24 +366,12 @@ int lsq_attn_prefill_w8(const lsq_attn_decode_w8_geom* geom, const lsq_attn_deco
                         const void* q_levels, const void* k_levels, const void* v_levels, void* y, void* stream) {
     const char* what = "lsq_attn_prefill_w8";
     lsq::AttnOut so{}, po{}, co{};
-    if (int rc = check_prefill_geom(what, geom)) return rc;
-    if (!consts) return fail(LSQ_EINVAL, "%s: NULL constants", what);
-    const void* cs[8] = {consts->s_q, consts->z_q, consts->s_k, consts->z_k, consts->s_v, consts->z_v, consts->s_p, consts->z_p};
-    for (const void* c : cs) {
-        if (!c) return fail(LSQ_EINVAL, "%s: NULL scale or zero point", what);
-        if (!aligned_to(c, 4)) return fail(LSQ_EINVAL, "%s: the scales and zero points must be element-aligned", what);
-    }
-    if (int rc = check_side(what, "scores", scores_out, so)) return rc;
-    if (int rc = check_side(what, "probabilities", probs_out, po)) return rc;
-    if (int rc = check_side(what, "context", ctx_out, co)) return rc;
-    if (scores_out->mid_dtype != probs_out->mid_dtype || scores_out->mid_dtype != ctx_out->mid_dtype)
-        return fail(LSQ_EINVAL, "%s: the three sides carry one mid_dtype, got codes %lld, %lld and %lld", what,
-                    static_cast<ll>(scores_out->mid_dtype), static_cast<ll>(probs_out->mid_dtype), static_cast<ll>(ctx_out->mid_dtype));
+    if (int rc = check_decode_geom(what, geom)) return rc;
+    if (int rc = check_decode_consts(what, consts)) return rc;
+    if (int rc = check_decode_sides(what, scores_out, probs_out, ctx_out, so, po, co)) return rc;
     if (!table || !q_levels || !k_levels || !v_levels || !y) return fail(LSQ_EINVAL, "%s: NULL buffer", what);
     if (!aligned_to(table, 4)) return fail(LSQ_EINVAL, "%s: the table must be element-aligned", what);
-    if (geom->has_lengths && !key_lengths) return fail(LSQ_EINVAL, "%s: key_lengths is NULL but the geometry says has_lengths", what);
-    if (!geom->has_lengths && key_lengths) return fail(LSQ_EINVAL, "%s: key_lengths is given but the geometry says has_lengths = 0", what);
-    if (key_lengths && !aligned_to(key_lengths, 4)) return fail(LSQ_EINVAL, "%s: key_lengths must be 4-byte aligned", what);
+    if (int rc = check_key_lengths(what, geom, key_lengths)) return rc;
     const int64_t q_span = span_of(geom->q, geom->B, geom->H, geom->Tq, geom->D), k_span = span_of(geom->k, geom->B, geom->Hkv, geom->Tk, geom->D);
     const int64_t v_span = span_of(geom->v, geom->B, geom->Hkv, geom->Tk, geom->D), y_bytes = span_of(geom->y, geom->B, geom->H, geom->Tq, geom->D);
     if (overlap(y, y_bytes, q_levels, q_span) || overlap(y, y_bytes, k_levels, k_span) || overlap(y, y_bytes, v_levels, v_span) ||
@@ -469,7 +409,7 @@ int lsq_attn_prefill_w8(const lsq_attn_decode_w8_geom* geom, const lsq_attn_deco
 
 int lsq_attn_prefill_w8_plan(const lsq_attn_decode_w8_geom* geom, int qkv_aligned, int y_aligned, int32_t* out8) {
     const char* what = "lsq_attn_prefill_w8_plan";
-    if (int rc = check_prefill_geom(what, geom)) return rc;
+    if (int rc = check_decode_geom(what, geom)) return rc;
     if (!out8) return fail(LSQ_EINVAL, "%s: NULL output", what);
     const lsq::PrePlan pl = lsq::plan_prefill(*geom, qkv_aligned != 0, y_aligned != 0);
     if (int rc = check_grid(what, pl.grid)) return rc;
