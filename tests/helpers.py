@@ -41,6 +41,33 @@ def assert_reduction_close(got, want, abs_terms, what, tol=TOL):
                              (what, i, got[i], want[i], abs(got[i] - want[i]), tol * scale[i]))
 
 
+def same_stored(got, want, dtype, what):
+    """a result of the GPU (a tensor) against the oracle's (an array), bit for bit.  16-bit storage: the oracle's fp32 result
+    rounded to the storage type; rounding does not say which of the storage type's NaNs an fp32 NaN becomes (the payload cannot
+    be kept), so where the oracle has a NaN the result must be a NaN, and every other element must have the rounded value's
+    bits."""
+    import torch
+    if dtype in (torch.float32, torch.float64):
+        return assert_bits_equal(got.cpu().numpy(), want, what)
+    want = torch.from_numpy(np.ascontiguousarray(want)).reshape(got.shape)
+    nan = torch.isnan(want)
+    got = got.cpu()
+    assert torch.equal(torch.isnan(got), nan), what + ": NaNs are not where the oracle's are"
+    assert_bits_equal(got.masked_fill(nan, 0).view(torch.int16).numpy(), want.to(dtype).masked_fill(nan, 0).view(torch.int16).numpy(), what)
+
+
+def check_sums(got, wide, abs_terms, what):
+    """d_scale / d_shift (a tensor) against the oracle's fp64 sums: the oracle's NaN / +-inf pattern exactly -- which shows that a
+    non-finite term stayed with its own channel or group -- and assert_reduction_close on the finite ones"""
+    got, wide = got.cpu().numpy().astype(np.float64).reshape(-1), np.asarray(wide, dtype=np.float64).reshape(-1)
+    bad = ~np.isfinite(wide)
+    assert (np.isfinite(got) == ~bad).all(), "%s: non-finite channels got %r want %r" % (what, got, wide)
+    assert (np.isnan(got) == np.isnan(wide)).all(), "%s: NaN channels got %r want %r" % (what, got, wide)
+    inf = np.isinf(wide)
+    assert (got[inf] == wide[inf]).all(), "%s: inf signs got %r want %r" % (what, got, wide)
+    assert_reduction_close(got[~bad], wide[~bad], np.asarray(abs_terms).reshape(-1)[~bad], what + " (finite channels)")
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 

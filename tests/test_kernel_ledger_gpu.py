@@ -26,7 +26,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_bits_equal, assert_reduction_close, pc_coordinates, per_channel_kernels
+from helpers import assert_bits_equal, pc_coordinates, per_channel_kernels
+from helpers import check_sums as _check_sums, same_stored as _same_stored
 from oracle import lsq_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -148,19 +149,6 @@ def _bits(t):
     return t.cpu().contiguous().view(torch.uint8).numpy()
 
 
-def _same_stored(got, want, dtype, what):
-    """a result of the GPU against the oracle's, bit for bit.  16-bit storage: the oracle's fp32 result rounded to the storage
-    type; rounding does not say which of the storage type's NaNs an fp32 NaN becomes (the payload cannot be kept), so where
-    the oracle has a NaN the result must be a NaN, and every other element must have the rounded value's bits."""
-    if dtype in (torch.float32, torch.float64):
-        return assert_bits_equal(got.cpu().numpy(), want, what)
-    want = torch.from_numpy(np.ascontiguousarray(want)).reshape(got.shape)
-    nan = torch.isnan(want)
-    got = got.cpu()
-    assert torch.equal(torch.isnan(got), nan), what + ": NaNs are not where the oracle's are"
-    assert_bits_equal(got.masked_fill(nan, 0).view(torch.int16).numpy(), want.to(dtype).masked_fill(nan, 0).view(torch.int16).numpy(), what)
-
-
 def _reference(shape, axis, dtype, x, g, s, b):
     outer, C, inner = O.axis_to_ocl(shape, axis)
     xs, gs, sn, bn = _np(x), _np(g), s.numpy(), b.numpy()
@@ -170,16 +158,6 @@ def _reference(shape, axis, dtype, x, g, s, b):
         sym, init, ev = m
         ref[m] = O.bwd_pc(gs, xs, sn, bn, outer, C, inner, *Q, True, 1.0, sym, ev, init)
     return ref
-
-
-def _check_sums(got, wide, abs_terms, what):
-    got, wide = got.cpu().numpy().astype(np.float64), np.asarray(wide, dtype=np.float64)
-    bad = ~np.isfinite(wide)
-    assert (np.isfinite(got) == ~bad).all(), "%s: non-finite channels got %r want %r" % (what, got, wide)
-    assert (np.isnan(got) == np.isnan(wide)).all(), "%s: NaN channels got %r want %r" % (what, got, wide)
-    inf = np.isinf(wide)
-    assert (got[inf] == wide[inf]).all(), "%s: inf signs got %r want %r" % (what, got, wide)
-    assert_reduction_close(got[~bad], wide[~bad], np.asarray(abs_terms)[~bad], what + " (finite channels)")
 
 
 def _held(T, shipped, run, names, check):
