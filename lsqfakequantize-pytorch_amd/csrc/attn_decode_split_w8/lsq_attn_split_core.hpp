@@ -28,6 +28,18 @@
 //                   the decode kernel's epilogue and store.  nmax = 0: no chunk is read, I = 0.
 // No atomics, no flags: the stream orders the three launches.
 //
+// ROW TILES (liblsq_hip_attn_chunk_w8.so: any R).  The bodies are templates over `kTiled`.  false, the default and what the two decode
+// libraries instantiate, is everything above: one tile, row0 = 0, and every line below that names row0 folds to the text without
+// it.  true deals the R rows of a kv head to NT = ceil(R / 16) tiles of 16 and makes the tile a grid coordinate: launches 1 and 2
+// run B Hkv NT S workgroups ((b, kv head), tile, split -- the split innermost), launch 3 B Hkv NT.  Tile i holds the rows
+// row0 = 16 i .. min(row0 + 15, R - 1) and may straddle two query heads (Tq % 16 != 0).  In place of nmax stands the TILE's
+//     nmax_tile = the largest n of the tile's live rows = n(b, Tq - 1) where the tile straddles a head border, else n of its last row
+// (n is non-decreasing in t in all three mask modes): a workgroup whose chunk starts at or beyond nmax_tile returns before its first
+// barrier -- the early tiles of a causal prompt skip the late chunks --, launch 2 reads a row's prefix below 16 ceil(n_r / 16) <=
+// 16 ceil(nmax_tile / 16), which the same tile's launch-1 workgroups wrote, and launch 3 sums the chunks that start below nmax_tile.
+// A row with n_r below a processed chunk carries the byte z_p there and contributes exactly 0.  kTiled also knows the third mask
+// mode (g.causal == 2: n(b, t) = max(0, L_b - (Tq - 1 - t)), L_b = min(Tk, max(key_lengths[b], 0))).
+//
 // WHERE A KEY'S ROW LIES is the one thing the two libraries do not share: launches 1 and 2 are templates over a key-addressing
 // policy `Keys`, a kernel argument.  A policy provides
 //     Keys::Rows keys.rows(T, s, b, hkv)       the rows of head (b, hkv) of the tensor T with the strides s = (s0, s1, ld), with
@@ -84,7 +96,7 @@ struct SplGeom {            // kernel argument
     int64_t ldw;            // bytes between the score rows in the workspace, a multiple of 16 that is at least Tk
     int Hkv, G, Tq, Tk, D;
     int R;                  // G Tq
-    int causal, off;        // row t sees t + 1 + off keys (off clamped to Tk on the host)
+    int causal, off;        // 1: row t sees t + 1 + off keys (off clamped to Tk on the host); 2 (kTiled only): counted back from the length
     int chunk, S;           // keys of a chunk (a multiple of 64); ceil(Tk / chunk)
 };
 
@@ -116,32 +128,71 @@ struct DenseKeys {          // kernel argument
 };
 
 // n(b, t) of the contract; len: max(key_lengths[b], 0), or Tk without lengths
+template <bool kTiled = false>
 __device__ __forceinline__ int spl_count(const SplGeom& g, int len, int t) {
     int n = min(g.Tk, len);
-    if (g.causal) n = min(n, t + 1 + g.off);           // t < 16 and off <= Tk <= 65536
+    if (kTiled && g.causal == 2) return max(n - (g.Tq - 1 - t), 0);    // the last row sees L_b keys, the row before it one fewer
+    if (g.causal) n = min(n, t + 1 + g.off);           // t < Tq <= 2^20 and off <= Tk <= 65536
     return n;
 }
 
+// the row tile of a workgroup.  `bh` comes in as the workgroup's index without its split, ((b, kv head), tile), and leaves as
+// (b, kv head); the tile's first row is returned.  !kTiled: one tile, nothing is touched
+template <bool kTiled>
+__device__ __forceinline__ int spl_tile(const SplGeom& g, int64_t& bh) {
+    if constexpr (kTiled) {
+        const int NT = (g.R + kSplRows - 1) / kSplRows;
+        const int64_t bt = bh;
+        bh = bt / NT;
+        return kSplRows * static_cast<int>(bt - bh * NT);
+    } else {
+        return 0;
+    }
+}
+
+// R D, the integers of one chunk of a kv head: at most 2048 with one tile, beyond an int with row tiles
+template <bool kTiled>
+__device__ __forceinline__ auto spl_chunk_stride(const SplGeom& g) {
+    if constexpr (kTiled) {
+        return static_cast<int64_t>(g.R) * g.D;
+    } else {
+        return g.R * g.D;
+    }
+}
+
+// the largest n among the rows of the tile that starts at row0: where the workgroup's key loops end
+template <bool kTiled>
+__device__ __forceinline__ int spl_nmax(const SplGeom& g, int len, int row0) {
+    if constexpr (kTiled) {
+        const int last = min(row0 + kSplRows, g.R) - 1;                 // the tile's last live row
+        const int h0 = row0 / g.Tq, h1 = last / g.Tq;
+        return spl_count<true>(g, len, h0 != h1 ? g.Tq - 1 : last - h1 * g.Tq);    // a straddled border: the row t = Tq - 1 is in the tile
+    } else {
+        return spl_count(g, len, g.Tq - 1);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launch 1: the scores of a chunk
-template <class Keys>
+template <class Keys, bool kTiled = false>
 __device__ __forceinline__ void attn_split_scores(const SplGeom& g, const SplArg& a, const AttnOut& so, const int32_t* __restrict__ lens,
                                                   const uint8_t* __restrict__ Q, const uint8_t* __restrict__ K, uint8_t* __restrict__ ws,
                                                   const Keys& keys) {
     __shared__ __attribute__((aligned(16))) unsigned char sc[kSplScoreLds];      // [16][272]: the score bytes of a round
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
     const int nl = lane & 15, q = lane >> 4;
-    const int64_t bh = static_cast<int64_t>(blockIdx.x) / g.S;
+    int64_t bh = static_cast<int64_t>(blockIdx.x) / g.S;
     const int s = static_cast<int>(static_cast<int64_t>(blockIdx.x) - bh * g.S);
+    const int row0 = spl_tile<kTiled>(g, bh);
     const int64_t b0 = bh / g.Hkv, b1 = bh - b0 * g.Hkv;
     const int len = lens ? max(lens[b0], 0) : g.Tk;
-    const int nmax = spl_count(g, len, g.Tq - 1);                       // 0 .. Tk, the same for the S workgroups of the head
+    const int nmax = spl_nmax<kTiled>(g, len, row0);                    // 0 .. Tk, the same for the S workgroups of the head (kTiled: of the tile)
     const int c0 = s * g.chunk;                                         // s chunk < Tk + chunk: no overflow
     if (c0 >= nmax) return;                                             // the same for the whole workgroup, before any barrier
     const int c1 = min(c0 + g.chunk, nmax);
     const int jend = (c1 + 15) >> 4;                                    // 16-key sub-tiles below c1
     const i32x4 ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
     const uint32_t flip_q = a.off_q ? 0x80808080u : 0u, flip_k = a.off_k ? 0x80808080u : 0u;
-    const int r = min(nl, g.R - 1);                                     // a clamped row computes values nobody stores
+    const int r = min(row0 + nl, g.R - 1);                              // a clamped row computes values nobody stores
     const int rg = r / g.Tq, rt = r - rg * g.Tq;
     const uint8_t* __restrict__ qrow = Q + b0 * g.q_s0 + (b1 * g.G + rg) * g.q_s1 + static_cast<int64_t>(rt) * g.q_ld;
     const typename Keys::Rows krows = keys.rows(K, g.k, b0, b1);
@@ -158,7 +209,7 @@ __device__ __forceinline__ void attn_split_scores(const SplGeom& g, const SplArg
     const BmmInt ex = bmm_int_constants(static_cast<int64_t>(a.z_q[0]) - a.off_q, static_cast<int64_t>(a.z_k[0]) - a.off_k, g.D);
     const float s_q = a.s_q[0], s_k = a.s_k[0];
     const bool two = g.D > 64;                                          // the same for the whole grid
-    uint8_t* __restrict__ wrow = ws + (bh * g.R + (tid >> 4)) * g.ldw;  // the row this thread copies out (used where tid / 16 < R)
+    uint8_t* __restrict__ wrow = ws + (bh * g.R + row0 + (tid >> 4)) * g.ldw;       // the row this thread copies out (used where it is < R)
     // the entries of this wave's sub-tiles of the round, all four in flight at once: a sub-tile at or beyond jend takes the entry of
     // the chunk's last one (16 (jend - 1) < c1 <= nmax: a live key) and is never used
     typename Keys::Rows::Entry ent[kSplInFlight];
@@ -215,7 +266,7 @@ __device__ __forceinline__ void attn_split_scores(const SplGeom& g, const SplArg
         {
             const int pr = tid >> 4, pk = tid & 15;                     // (row, packet of the round)
             // 16 (jb + pk) + 16 <= 16 jend <= 16 ceil(Tk / 16) <= ldw
-            if (pr < g.R && jb + pk < jend)
+            if (row0 + pr < g.R && jb + pk < jend)
                 *reinterpret_cast<u32x4*>(wrow + 16 * static_cast<int64_t>(jb + pk)) = *reinterpret_cast<const u32x4*>(sc + pr * kSplScoreLd + 16 * pk);
         }
         __syncthreads();                                                // before the next round overwrites them
@@ -223,7 +274,7 @@ __device__ __forceinline__ void attn_split_scores(const SplGeom& g, const SplArg
 }
 
 // ------------------------------------------------------------------------------------------------ launch 2: the chunk's context integer
-template <class Keys>
+template <class Keys, bool kTiled = false>
 __device__ __forceinline__ void attn_split_context(const SplGeom& g, const SplArg& a, const AttnOut& po, const int32_t* __restrict__ table,
                                                    const int32_t* __restrict__ lens, const uint8_t* __restrict__ V,
                                                    const uint8_t* __restrict__ ws, int64_t* __restrict__ wi, const Keys& keys) {
@@ -236,11 +287,12 @@ __device__ __forceinline__ void attn_split_context(const SplGeom& g, const SplAr
     unsigned char* stage = ptile + 2 * kSplRows * kSplTStride;                      // 2 x [D][80]: v transposed
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
     const int nl = lane & 15, q = lane >> 4;
-    const int64_t bh = static_cast<int64_t>(blockIdx.x) / g.S;
+    int64_t bh = static_cast<int64_t>(blockIdx.x) / g.S;
     const int s = static_cast<int>(static_cast<int64_t>(blockIdx.x) - bh * g.S);
+    const int row0 = spl_tile<kTiled>(g, bh);
     const int64_t b0 = bh / g.Hkv, b1 = bh - b0 * g.Hkv;
     const int len = lens ? max(lens[b0], 0) : g.Tk;
-    const int nmax = spl_count(g, len, g.Tq - 1);
+    const int nmax = spl_nmax<kTiled>(g, len, row0);
     const int c0 = s * g.chunk;
     if (c0 >= nmax) return;                                             // the same for the whole workgroup, before any barrier
     const int c1 = min(c0 + g.chunk, nmax);
@@ -251,13 +303,13 @@ __device__ __forceinline__ void attn_split_context(const SplGeom& g, const SplAr
     tab[tid] = table[tid];                                              // 256 threads
     __syncthreads();
 
-    // ---- the rows' maximum and sum over their WHOLE prefix: packets below 16 ceil(n_r / 16) <= 16 ceil(nmax / 16), all written
+    // ---- the tile's rows' maximum and sum over their WHOLE prefix: packets below 16 ceil(n_r / 16) <= 16 ceil(nmax / 16), all written
     for (int r = wave; r < kSplRows; r += kSplWaves) {                  // the same for the whole wave
         int n = 0, m = 0;
         float rcp = 0.0f;
-        if (r < g.R) {
-            const uint8_t* __restrict__ row = wsb + r * g.ldw;
-            n = spl_count(g, len, r % g.Tq);                            // n <= nmax
+        if (row0 + r < g.R) {
+            const uint8_t* __restrict__ row = wsb + (row0 + r) * g.ldw;
+            n = spl_count<kTiled>(g, len, (row0 + r) % g.Tq);           // n <= nmax
             const int npk = (n + 15) >> 4;
             spl_u16x2 me = {0, 0}, mo = {0, 0};
             for (int p = lane; p < npk; p += 64) {
@@ -304,7 +356,7 @@ __device__ __forceinline__ void attn_split_context(const SplGeom& g, const SplAr
     const int pr = tid >> 4, pw = tid & 15;                             // this thread's (row, word) of a p tile
     const int my_n = row_n[pr], my_m = row_m[pr];
     const float my_r = row_r[pr];
-    const uint8_t* __restrict__ srow = wsb + min(pr, g.R - 1) * g.ldw;  // read only where a key lies below my_n (0 in rows >= R)
+    const uint8_t* __restrict__ srow = wsb + min(row0 + pr, g.R - 1) * g.ldw;       // read only where a key lies below my_n (0 in rows >= R)
     const typename Keys::Rows vrows = keys.rows(V, g.v, b0, b1);
     const int subs = g.D >> 4;                                          // 16-column sub-tiles of the context, 1 .. 8
     const int wpr = g.D >> 2, items = 16 * wpr;                         // words of a v row; (four keys, a word) items of a step
@@ -373,7 +425,7 @@ __device__ __forceinline__ void attn_split_context(const SplGeom& g, const SplAr
                 if (key + i < my_n) {
                     const int b = static_cast<int>((sw >> (8 * i)) & 0xffu);
                     byte = w8o_byte(smx_value(tab[(my_m - b) & 0xff], my_r, pq.mid), pq) ^ fb;
-                } else if (pr < g.R && key + i < c1) {
+                } else if (row0 + pr < g.R && key + i < c1) {
                     byte = zb ^ fb;                                     // the byte z_p in [n_r, c1): contributes (z_p - z_p) = 0
                 }
                 w |= (byte & 0xffu) << (8 * i);
@@ -414,26 +466,36 @@ __device__ __forceinline__ void attn_split_context(const SplGeom& g, const SplAr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = 4 * q + i;                                    // D of the MFMA: column = lane & 15, row = 4 * (lane >> 4) + register
-            if (r < g.R) out[static_cast<int64_t>(r) * g.D + 16 * j + nl] = bmm_exact(P[jj][i], Cs[jj][i], Rs[i], c1 - c0, z_p, z_v);
+            if (row0 + r < g.R) out[static_cast<int64_t>(row0 + r) * g.D + 16 * j + nl] = bmm_exact(P[jj][i], Cs[jj][i], Rs[i], c1 - c0, z_p, z_v);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launch 3: the sum over the chunks, the levels
+template <bool kTiled = false>
 __device__ __forceinline__ void attn_split_reduce(const SplGeom& g, const SplArg& a, const AttnOut& co, const int32_t* __restrict__ lens,
                                                   const int64_t* __restrict__ wi, uint8_t* __restrict__ y) {
     __shared__ __attribute__((aligned(16))) unsigned char tile[kSplRows * LSQ_ATTN_DECODE_SPLIT_W8_MAX_D];      // the level tile [R][D]
     const int tid = static_cast<int>(threadIdx.x);
-    const int64_t bh = static_cast<int64_t>(blockIdx.x);
+    int64_t bh = static_cast<int64_t>(blockIdx.x);
+    const int row0 = spl_tile<kTiled>(g, bh);
     const int64_t b0 = bh / g.Hkv, b1 = bh - b0 * g.Hkv;
     const int len = lens ? max(lens[b0], 0) : g.Tk;
-    const int nmax = spl_count(g, len, g.Tq - 1);
+    const int nmax = spl_nmax<kTiled>(g, len, row0);
     const int live = (nmax + g.chunk - 1) / g.chunk;                    // the chunks that start below nmax: the ones launch 2 wrote; <= S
     const AttnQ oq = attn_constants(co);
     const float s_p = a.s_p[0], s_v = a.s_v[0];
-    const int RD = g.R * g.D;                                           // <= 2048
-    const int64_t* __restrict__ src = wi + bh * g.S * RD;               // [S][R][D]
-    for (int e = tid; e < RD; e += kSplThreads) {
+    const auto RD = spl_chunk_stride<kTiled>(g);                        // the integers between two chunks
+    int rows, TD;                                                       // the tile's live rows and their integers, <= 2048
+    if constexpr (kTiled) {
+        rows = min(kSplRows, g.R - row0);
+        TD = rows * g.D;
+    } else {
+        rows = g.R;
+        TD = RD;
+    }
+    const int64_t* __restrict__ src = wi + bh * g.S * RD + static_cast<int64_t>(row0) * g.D;    // [S][R][D], from the tile's first row
+    for (int e = tid; e < TD; e += kSplThreads) {
         int64_t I = 0;
         for (int c = 0; c < live; ++c) I += src[static_cast<int64_t>(c) * RD + e];
         const float u = bmm_value(static_cast<float>(I), s_p, s_v, oq.mid);
@@ -441,12 +503,13 @@ __device__ __forceinline__ void attn_split_reduce(const SplGeom& g, const SplArg
     }
     __syncthreads();
     uint8_t* __restrict__ yb = y + b0 * g.y_s0 + (b1 * g.G) * g.y_s1;
-    const int subs = g.D >> 4, total = g.R * subs;                      // 16-byte packets of the rows that exist
+    // 16-byte packets of the rows that exist (one tile: g.R by its name, which keeps the decode libraries' code objects the bytes they were)
+    const int subs = g.D >> 4, total = (kTiled ? rows : g.R) * subs;
     for (int idx = tid; idx < total; idx += kSplThreads) {
-        const int r = idx / subs, c = (idx - r * subs) * 16;
+        const int lr = idx / subs, c = (idx - lr * subs) * 16, r = row0 + lr;
         const int rg = r / g.Tq, rt = r - rg * g.Tq;
         uint8_t* dst = yb + rg * g.y_s1 + static_cast<int64_t>(rt) * g.y_ld + c;
-        const unsigned char* from = tile + r * g.D + c;
+        const unsigned char* from = tile + lr * g.D + c;
         if (a.y_packets) {
             *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(from);
         } else {
@@ -460,48 +523,64 @@ __device__ __forceinline__ void attn_split_reduce(const SplGeom& g, const SplArg
 // ------------------------------------------------------------------------------------------------
 struct SplPlan {
     bool served;
-    int rows, chunk, splits, lds, store;
-    int64_t grid, heads, ldw, ws_scores, ws_bytes;      // B Hkv S; B Hkv; the workspace's row stride, its score part and its size
+    int rows, tiles, chunk, splits, lds, store;
+    // B Hkv NT S; B Hkv NT (launch 3's grid); the workspace's row stride, its score part and its size
+    int64_t grid, heads, ldw, ws_scores, ws_bytes;
     SplGeom g;
 };
 
-// the chunk for `splits` (0: the library's own choice; else at most that many splits), a multiple of 64
-inline int64_t split_chunk(int64_t heads, int64_t Tk, int64_t splits) {
+// what differs between the libraries' plans: whether the rows are dealt to tiles (else R <= 16 is asked for), and the constants of
+// the library's own choice of the chunk (splits = 0); max_chunk 0: no upper bound
+struct SplRule {
+    bool tiled;
+    int64_t want, max_splits, min_chunk, max_chunk;
+};
+constexpr SplRule kSplDecodeRule = {false, static_cast<int64_t>(LSQ_ATTN_DECODE_SPLIT_W8_WG_PER_CU) * LSQ_ATTN_DECODE_SPLIT_W8_CUS,
+                                    LSQ_ATTN_DECODE_SPLIT_W8_MAX_SPLITS, LSQ_ATTN_DECODE_SPLIT_W8_MIN_CHUNK, LSQ_ATTN_DECODE_SPLIT_W8_MAX_CHUNK};
+
+// the chunk for `splits` (0: the library's own choice; else at most that many splits), a multiple of 64; `heads`: the workgroups
+// of a launch before the keys are split, B Hkv NT
+inline int64_t split_chunk(int64_t heads, int64_t Tk, int64_t splits, const SplRule& rule) {
     const int64_t units = (Tk + kSplStep - 1) / kSplStep;
     if (splits > 0) return kSplStep * ((units + splits - 1) / splits);
     // the fewest splits with which the grid fills the part, dealt evenly; the chunk taken into its range
-    const int64_t want = static_cast<int64_t>(LSQ_ATTN_DECODE_SPLIT_W8_WG_PER_CU) * LSQ_ATTN_DECODE_SPLIT_W8_CUS;
-    const int64_t fewest = std::min<int64_t>((want + heads - 1) / heads, LSQ_ATTN_DECODE_SPLIT_W8_MAX_SPLITS);
-    const int64_t chunk = kSplStep * ((units + fewest - 1) / fewest);
-    return std::min<int64_t>(std::max<int64_t>(chunk, LSQ_ATTN_DECODE_SPLIT_W8_MIN_CHUNK), LSQ_ATTN_DECODE_SPLIT_W8_MAX_CHUNK);
+    const int64_t fewest = std::min<int64_t>((rule.want + heads - 1) / heads, rule.max_splits);
+    const int64_t chunk = std::max<int64_t>(kSplStep * ((units + fewest - 1) / fewest), rule.min_chunk);
+    return rule.max_chunk ? std::min<int64_t>(chunk, rule.max_chunk) : chunk;
 }
 
-// what both libraries ask of a geometry (each adds its own limit: Tk there, the page size here) and plan the same way; `ldw` is
+// what the libraries ask of a geometry (each adds its own limit: Tk there, the page size here) and plan the same way; `ldw` is
 // the library's: a multiple of 16 that is at least Tk
-inline SplPlan plan_split_core(const lsq_attn_decode_w8_geom& ge, bool qkv_aligned, bool y_aligned, int64_t splits, int64_t ldw) {
+inline SplPlan plan_split_core(const lsq_attn_decode_w8_geom& ge, bool qkv_aligned, bool y_aligned, int64_t splits, int64_t ldw,
+                               const SplRule& rule = kSplDecodeRule) {
     SplPlan pl = {};
-    const int64_t G = ge.H / ge.Hkv, R = G * ge.Tq;
+    const int64_t G = ge.H / ge.Hkv, R = G * ge.Tq;                     // R <= 2^40: check_decode_geom
     pl.served = qkv_aligned && strides16(ge.q) && strides16(ge.k) && strides16(ge.v) && ge.D % 16 == 0 && ge.D >= 16 &&
-                ge.D <= LSQ_ATTN_DECODE_SPLIT_W8_MAX_D && ge.Tk <= LSQ_ATTN_DECODE_SPLIT_W8_MAX_TK && R <= LSQ_ATTN_DECODE_SPLIT_W8_MAX_ROWS;
+                ge.D <= LSQ_ATTN_DECODE_SPLIT_W8_MAX_D && ge.Tk <= LSQ_ATTN_DECODE_SPLIT_W8_MAX_TK &&
+                (rule.tiled || R <= LSQ_ATTN_DECODE_SPLIT_W8_MAX_ROWS);
     if (!pl.served) return pl;
     const int Tk = static_cast<int>(ge.Tk), D = static_cast<int>(ge.D);
-    pl.heads = ge.B * ge.Hkv;
-    pl.chunk = static_cast<int>(split_chunk(pl.heads, ge.Tk, splits));
-    pl.splits = (Tk + pl.chunk - 1) / pl.chunk;
-    pl.rows = static_cast<int>(R);
+    const int64_t tiles = (R + kSplRows - 1) / kSplRows;
+    pl.heads = ge.B * ge.Hkv * tiles;                                   // <= 2^40
+    pl.chunk = static_cast<int>(split_chunk(pl.heads, ge.Tk, splits, rule));
+    pl.splits = (Tk + pl.chunk - 1) / pl.chunk;                         // <= 1024
+    // (a grid beyond 2^24 - 1 workgroups is refused by every entry before these two are used: R < 2^28 where a plan is launched)
+    pl.rows = static_cast<int>(std::min<int64_t>(R, INT32_MAX));
+    pl.tiles = static_cast<int>(std::min<int64_t>(tiles, INT32_MAX));
     pl.lds = spl_context_lds(D);
     pl.store = y_aligned && strides16(ge.y) ? LSQ_ATTN_W8_STORE_PACKETS : LSQ_ATTN_W8_STORE_ELEMS;
     pl.grid = pl.heads * pl.splits;
     pl.ldw = ldw;
-    pl.ws_scores = pl.heads * R * pl.ldw;                               // a multiple of 16: the integers behind it are aligned
-    pl.ws_bytes = pl.ws_scores + 8 * pl.heads * pl.splits * R * ge.D;
+    pl.ws_scores = ge.B * ge.Hkv * R * pl.ldw;                          // a multiple of 16: the integers behind it are aligned; <= 2^56
+    pl.ws_bytes = pl.ws_scores + 8 * ge.B * ge.Hkv * pl.splits * R * ge.D;
+    const int mode = !ge.causal ? 0 : rule.tiled && ge.causal == 2 ? 2 : 1;
     pl.g = SplGeom{ge.q.s0, ge.q.s1, ge.q.ld, ge.k, ge.v, ge.y.s0, ge.y.s1, ge.y.ld, pl.ldw,
-                   static_cast<int>(ge.Hkv), static_cast<int>(G), static_cast<int>(ge.Tq), Tk, D, pl.rows, ge.causal ? 1 : 0,
-                   ge.causal ? static_cast<int>(std::min<int64_t>(ge.causal_offset, ge.Tk)) : 0, pl.chunk, pl.splits};
+                   static_cast<int>(ge.Hkv), static_cast<int>(G), static_cast<int>(ge.Tq), Tk, D, pl.rows, mode,
+                   mode == 1 ? static_cast<int>(std::min<int64_t>(ge.causal_offset, ge.Tk)) : 0, pl.chunk, pl.splits};
     return pl;
 }
 
-// what a `*_plan` entry reports of a plan; `family`: the library's code for it (its composition code where !pl.served: all else 0)
+// what a `*_plan` entry of the two decode libraries reports of a plan; `family`: the library's code for it (its composition code where !pl.served: all else 0)
 inline void split_plan_out(const SplPlan& pl, int family, int32_t* out8) {
     out8[0] = family;
     out8[1] = static_cast<int32_t>(pl.grid);

@@ -3,20 +3,17 @@
 //
 // The decode is the split library's: the three launches, their constants, the chunk rule, the plan and the launch sequence are
 // ../attn_decode_split_w8/lsq_attn_split_core.hpp, and the geometry, constants, sides and key_lengths are checked by
-// ../attn_w8/lsq_attn_decode_checks.hpp.  What is left here: the PagedKeys policy -- a key's row is not T + j ld but lies in the page
-// the block table names,
-//     row(b, hkv, j) = pool + clamp(block_table[b, j >> log2 ps], 0, Np - 1) * page stride + hkv * head stride + (j & (ps - 1)) * slot stride,
-// ps a power of two >= 16, so that an entry serves aligned runs of at least 16 keys as the core asks; READS CLAMP, and the core asks
-// only for entries of keys below nmax, so table entries at logical pages >= ceil(nmax / ps) and pool bytes at keys >= nmax are
-// never read --, the kernels as the core's bodies on that policy, the plan with this library's workspace row stride and page rule,
-// the checks of the pages and of the buffers, the C ABI, and the append:
+// ../attn_w8/lsq_attn_decode_checks.hpp; the PagedKeys policy -- a key's row lies in the page the block table names, READS CLAMP --
+// and the checks of the pages are lsq_attn_paged_keys.hpp, which the chunk library reads too.  What is left here: the kernels as the
+// core's bodies on that policy, the plan with this library's workspace row stride and page rule, the checks of the buffers, the C
+// ABI, and the append:
 //
 // kv_append_paged: one lane per 16-byte packet (or per byte) of k and of v; a token whose position or entry is out of range is
 // skipped as a whole.
 #include "../lsq_companion_abi.hpp"
 #include "../attn_w8/lsq_attn_decode_checks.hpp"
 #include "../attn_decode_split_w8/lsq_attn_split_core.hpp"
-#include "../../../include/lsq_hip_attn_paged_w8.h"
+#include "lsq_attn_paged_keys.hpp"
 
 namespace lsq {
 
@@ -28,29 +25,6 @@ static_assert(LSQ_ATTN_PAGED_W8_MAX_ROWS == LSQ_ATTN_DECODE_SPLIT_W8_MAX_ROWS &&
                   LSQ_ATTN_PAGED_W8_WG_PER_CU == LSQ_ATTN_DECODE_SPLIT_W8_WG_PER_CU &&
                   LSQ_ATTN_PAGED_W8_MAX_SPLITS == LSQ_ATTN_DECODE_SPLIT_W8_MAX_SPLITS && LSQ_ATTN_PAGED_W8_CUS == LSQ_ATTN_DECODE_SPLIT_W8_CUS,
               "the paged header's constants are the split header's");
-static_assert(LSQ_ATTN_PAGED_W8_MIN_PAGE % 16 == 0, "a sub-tile of launch 1 lies in one page");
-
-// keys in the pages of a pool; the strides of T are (page, head, slot)
-struct PagedKeys {          // kernel argument
-    const int32_t* bt;      // the block table
-    int64_t bt_ld;          // elements between its rows
-    int Np, lps, psm;       // pages of a pool; log2 ps; ps - 1
-    struct Rows {
-        typedef int Entry;                      // the page
-        const uint8_t* __restrict__ base;       // the kv head's slots of page 0
-        const int32_t* __restrict__ btrow;
-        int64_t sp, ld;
-        int Np, lps, psm;
-        // READS CLAMP (j < Tk = Mp ps, so j >> lps < Mp)
-        __device__ __forceinline__ Entry entry(int j) const { return min(max(btrow[j >> lps], 0), Np - 1); }
-        __device__ __forceinline__ const uint8_t* row(Entry e, int j) const {
-            return base + static_cast<int64_t>(e) * sp + static_cast<int64_t>(j & psm) * ld;
-        }
-    };
-    __device__ __forceinline__ Rows rows(const uint8_t* __restrict__ T, const lsq_attn_w8_strides& s, int64_t b, int64_t hkv) const {
-        return Rows{T + hkv * s.s1, bt + b * bt_ld, s.s0, s.ld, Np, lps, psm};
-    }
-};
 
 __global__ __launch_bounds__(kSplThreads) void attn_paged_scores_kernel(SplGeom g, SplArg a, AttnOut so, const int32_t* __restrict__ lens,
                                                                         const uint8_t* __restrict__ Q, const uint8_t* __restrict__ K,
@@ -116,17 +90,10 @@ __global__ __launch_bounds__(kSplThreads) void kv_append_paged_kernel(ApGeom g, 
 // ------------------------------------------------------------------------------------------------
 // the workspace's score rows are Tk = Mp ps bytes apart (a multiple of 16); ps a power of two >= 16 (Mp ps <= 65536: the API's own limit)
 inline SplPlan plan_paged(const lsq_attn_decode_w8_geom& ge, const lsq_attn_paged_w8_pages& pg, bool qkv_aligned, bool y_aligned, int64_t splits) {
-    const bool page_served = pg.ps >= LSQ_ATTN_PAGED_W8_MIN_PAGE && (pg.ps & (pg.ps - 1)) == 0;
-    return plan_split_core(ge, qkv_aligned && page_served, y_aligned, splits, ge.Tk);
+    return plan_split_core(ge, qkv_aligned && paged_page_served(pg), y_aligned, splits, ge.Tk);
 }
 
 inline int paged_family(const SplPlan& pl) { return pl.served ? LSQ_ATTN_PAGED_W8_PAGED : LSQ_ATTN_PAGED_W8_COMPOSITION; }
-
-inline PagedKeys paged_keys(const lsq_attn_paged_w8_pages& pg, const void* block_table) {
-    int lps = 0;
-    while ((int64_t{1} << lps) < pg.ps) ++lps;
-    return PagedKeys{static_cast<const int32_t*>(block_table), pg.bt_ld, static_cast<int>(pg.Np), lps, static_cast<int>(pg.ps - 1)};
-}
 
 struct ApPlan {
     int family, units;
@@ -155,31 +122,6 @@ inline ApPlan plan_append(const lsq_kv_append_paged_w8_geom& ge, bool aligned) {
 // the C ABI of include/lsq_hip_attn_paged_w8.h: validation, error bookkeeping
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-constexpr int64_t kMaxPages = (int64_t{1} << 31) - 1;       // an entry is an int32
-
-int check_pages(const char* what, const lsq_attn_paged_w8_pages* p) {
-    if (!p) return fail(LSQ_EINVAL, "%s: NULL pages", what);
-    if (p->ps < 1 || p->Mp < 1 || p->Np < 1)
-        return fail(LSQ_EINVAL, "%s: [Np, ps, Mp] = [%lld, %lld, %lld], every extent must be at least 1", what, static_cast<ll>(p->Np),
-                    static_cast<ll>(p->ps), static_cast<ll>(p->Mp));
-    if (p->Np > kMaxPages) return fail(LSQ_EINVAL, "%s: Np = %lld pages are beyond 2^31 - 1", what, static_cast<ll>(p->Np));
-    if (p->bt_ld < p->Mp)
-        return fail(LSQ_EINVAL, "%s: the block table's row stride bt_ld = %lld is smaller than its row of Mp = %lld", what,
-                    static_cast<ll>(p->bt_ld), static_cast<ll>(p->Mp));
-    return LSQ_OK;
-}
-
-// the pages, then the checks of a decode geometry with k and v read as pools
-int check_paged_geom(const char* what, const lsq_attn_decode_w8_geom* g, const lsq_attn_paged_w8_pages* p) {
-    if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
-    if (int rc = check_pages(what, p)) return rc;
-    if (p->ps > LSQ_ATTN_PAGED_W8_MAX_TK || p->Mp > LSQ_ATTN_PAGED_W8_MAX_TK || p->Mp * p->ps > LSQ_ATTN_PAGED_W8_MAX_TK)
-        return fail(LSQ_EINVAL, "%s: Mp ps = %lld x %lld keys, at most %d are served (the raw sums stay in 32 bits)", what,
-                    static_cast<ll>(p->Mp), static_cast<ll>(p->ps), LSQ_ATTN_PAGED_W8_MAX_TK);
-    const DecodePools pools{p->Np, p->ps, p->Mp};
-    return check_decode_geom(what, g, &pools);
-}
 
 int check_append_geom(const char* what, const lsq_kv_append_paged_w8_geom* g) {
     if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);

@@ -1,5 +1,5 @@
 // lsq_attn_decode_checks.hpp -- the host-side checks that the C ABIs on a `lsq_attn_decode_w8_geom` say the same way: liblsq_hip_attn_
-// decode_w8.so, liblsq_hip_attn_prefill_w8.so, liblsq_hip_attn_decode_split_w8.so and liblsq_hip_attn_paged_w8.so
+// decode_w8.so, liblsq_hip_attn_prefill_w8.so, liblsq_hip_attn_decode_split_w8.so, liblsq_hip_attn_paged_w8.so, liblsq_hip_attn_chunk_w8.so
 // (include/lsq_hip_attn_decode_w8.h lists the refusals).  Every refusal of a geometry, of the eight constants, of a side and of
 // key_lengths has ONE text here; an entry calls the checks in the order of its header.  Host code only, in the anonymous namespace
 // of the including translation unit, as lsq_attn_w8_checks.hpp, which this includes.

@@ -802,6 +802,33 @@ def attn_paged_w8_library():
     return _require_companion(_ATTN_PAGED_W8_LIB, "attn_paged_w8", "the paged KV cache on 8-bit levels needs", attn_paged_w8_error_str)
 
 
+# Chunked prefill attention on 8-bit levels: the split launches with the query rows of a kv head dealt to row tiles of 16, on a dense
+# cache or on pools through a block table, and the mask mode that counts every row's keys back from key_lengths
+# (include/lsq_hip_attn_chunk_w8.h): a twenty-fourth companion library; the ABIs above stay as they are.  Its geometry, constants and
+# pages are lsq_attn_decode_w8's and lsq_attn_paged_w8's structs; its plans report nine values.
+ATTN_CHUNK_W8_ABI_VERSION = 1
+_PLAN9 = ctypes.POINTER(ctypes.c_int32 * 9)
+C_ABI_ATTN_CHUNK_W8 = {
+    "lsq_attn_chunk_w8_abi_version": (_int, []),
+    "lsq_attn_chunk_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_attn_chunk_w8_workspace": (_int, [_ADGP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "lsq_attn_chunk_paged_w8_workspace": (_int, [_ADGP, _APPP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "lsq_attn_chunk_w8": (_int, [_ADGP, ctypes.POINTER(LsqAttnDecodeW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 ctypes.c_int64, ctypes.c_int64, _vp]),
+    "lsq_attn_chunk_paged_w8": (_int, [_ADGP, _APPP, ctypes.POINTER(LsqAttnDecodeW8Consts), _AOP, _AOP, _AOP, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    "lsq_attn_chunk_w8_plan": (_int, [_ADGP, _int, _int, ctypes.c_int64, _PLAN9]),
+    "lsq_attn_chunk_paged_w8_plan": (_int, [_ADGP, _APPP, _int, _int, ctypes.c_int64, _PLAN9]),
+}
+_ATTN_CHUNK_W8_LIB, attn_chunk_w8_error_str = _load_companion("liblsq_hip_attn_chunk_w8.so", C_ABI_ATTN_CHUNK_W8,
+                                                              "lsq_attn_chunk_w8_abi_version", ATTN_CHUNK_W8_ABI_VERSION)
+
+
+def attn_chunk_w8_library():
+    """The ctypes handle of liblsq_hip_attn_chunk_w8.so (raises if it is missing)."""
+    return _require_companion(_ATTN_CHUNK_W8_LIB, "attn_chunk_w8", "chunked prefill attention on 8-bit levels needs", attn_chunk_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -60,12 +60,13 @@ from ._attn_prefill_w8_host import attn_prefill_w8_plan, attn_prefill_w8_q  # no
 from ._attn_decode_split_w8_host import attn_decode_split_w8_plan, attn_decode_split_w8_q  # noqa: F401
 from ._attn_paged_w8_host import (attn_paged_w8_plan, attn_paged_w8_q, kv_append_paged_w8, kv_append_paged_w8_plan,  # noqa: F401
                                   kv_gather_paged_w8)
+from ._attn_chunk_w8_host import attn_chunk_paged_w8_plan, attn_chunk_paged_w8_q, attn_chunk_w8_plan, attn_chunk_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -299,6 +300,21 @@ _lib_def.define("lsq_attention_decode_paged_w8_q8_q(Tensor q_levels, Tensor q_sc
                 % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK,)))
 _lib_def.define("lsq_kv_append_paged_w8(Tensor k_levels, Tensor v_levels, Tensor(a!) k_pool, Tensor(b!) v_pool, Tensor block_table, "
                 "Tensor? positions=None) -> ()")
+#  * CHUNKED PREFILL ATTENTION on 8-bit LEVELS (liblsq_hip_attn_chunk_w8.so, include/lsq_hip_attn_chunk_w8.h): the arguments, the
+#    definition and the result of lsq_attention_decode_split_w8_q8_q (and of lsq_attention_decode_paged_w8_q8_q: pools and a block table)
+#    for ANY number of query rows, with `causal` an int MODE: 0 off, 1 row t sees t + 1 + causal_offset keys, 2 every row's keys counted
+#    back from key_lengths on the device -- n(b, t) = max(0, min(Tk, max(key_lengths[b], 0)) - (Tq - 1 - t)); needs key_lengths and
+#    causal_offset 0.  Three launches with the rows of a kv head dealt to row tiles of 16 and a workspace allocated per call where
+#    D % 16 == 0, D <= 128, Tk <= 65536 (ps a power of two >= 16) and q, k, v are 16-byte aligned with strides that are multiples of 16;
+#    the existing ops composed elsewhere, with the same bytes.  Inference only.
+_MASK_MODE = "int causal=0, int causal_offset=0, Tensor? key_lengths=None"
+_lib_def.define("lsq_attention_chunk_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_levels, Tensor k_scale, "
+                "Tensor k_zero, Tensor v_levels, Tensor v_scale, Tensor v_zero, Tensor table, %s, %s, %s, ScalarType mid_dtype, %s, "
+                "int splits=0) -> Tensor" % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK_MODE,)))
+_lib_def.define("lsq_attention_chunk_paged_w8_q8_q(Tensor q_levels, Tensor q_scale, Tensor q_zero, Tensor k_pool, Tensor k_scale, "
+                "Tensor k_zero, Tensor v_pool, Tensor v_scale, Tensor v_zero, Tensor block_table, Tensor table, %s, %s, %s, "
+                "ScalarType mid_dtype, %s, int splits=0) -> Tensor"
+                % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK_MODE,)))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1252,3 +1268,19 @@ torch.library.register_fake("torchlsq::lsq_kv_append_paged_w8", _fake_kv_append_
 _lib_def.impl("lsq_attention_decode_paged_w8_q8_q", _requant_no_grad("lsq_attention_decode_paged_w8_q8_q", (1, 4, 7, 11, 12, 17, 18, 23, 24)),
               "Autograd")
 _lib_def.impl("lsq_kv_append_paged_w8", _requant_no_grad("lsq_kv_append_paged_w8", ()), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# chunked prefill attention on 8-bit levels (_attn_chunk_w8_host.py): GPU tensors -> liblsq_hip_attn_chunk_w8.so (one call, three
+# launches over row tiles, a workspace from one torch.empty) where its plan says "chunk", else (the gather and) the existing ops
+# composed with per-row key counts; CPU tensors -> that composition; the decode ops' shape-only kernels.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_attention_chunk_w8_q8_q", attn_chunk_w8_q)
+    _lib_key.impl("lsq_attention_chunk_paged_w8_q8_q", attn_chunk_paged_w8_q)
+del _lib_key
+torch.library.register_fake("torchlsq::lsq_attention_chunk_w8_q8_q", _fake_attention_decode_split_w8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_attention_chunk_paged_w8_q8_q", _fake_attention_decode_paged_w8_q, lib=_lib_def)
+_lib_def.impl("lsq_attention_chunk_w8_q8_q", _requant_no_grad("lsq_attention_chunk_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")
+_lib_def.impl("lsq_attention_chunk_paged_w8_q8_q", _requant_no_grad("lsq_attention_chunk_paged_w8_q8_q", (1, 4, 7, 11, 12, 17, 18, 23, 24)),
+              "Autograd")

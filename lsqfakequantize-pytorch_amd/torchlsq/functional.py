@@ -1773,6 +1773,66 @@ def lsq_attention_decode_paged_w8_q(q: LevelsTensor, k_pool: LevelsTensor, v_poo
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 
+def lsq_attention_chunk_w8_q(q: LevelsTensor, k: LevelsTensor, v: LevelsTensor, table: Tensor, scores_out, probs_out, out,
+                             mid_dtype=torch.float32, causal=None, key_lengths: Tensor = None, block_table: Tensor = None,
+                             splits: int = 0) -> LevelsTensor:
+    """CHUNKED PREFILL attention on 8-bit levels (liblsq_hip_attn_chunk_w8.so): the arguments, the definition and the
+    result of `lsq_attention_decode_w8_q` -- q [B, H, Tq, D] against k and v [B, Hkv, Tk, D] with Hkv dividing H, or, with a
+    `block_table` (int32 [B, Mp]), against the POOLS [Np, Hkv, ps, D] of a paged cache as in `lsq_attention_decode_paged_w8_q`
+    (Tk = Mp ps, READS CLAMP) -- for ANY number of query rows against up to 65536 keys.  `causal` is None / False, True (the offset
+    Tk - Tq), an int offset >= 0, or "lengths":
+
+        L_b = min(Tk, max(key_lengths[b], 0)),      n(b, t) = max(0, L_b - (Tq - 1 - t))
+
+    -- the last query row of batch entry b sees its L_b keys, the row before it one fewer, a row whose count would be negative none
+    (`out`'s level of 0.0).  It needs `key_lengths`, which is read in the kernels and never on the host: feed a prompt in pieces into
+    a growing cache with the lengths `KVCacheW8.append` / `PagedKVCacheW8.append` return and one captured graph serves every piece.
+    With Tq = 1 it is `causal=True` with `key_lengths`.  Keys at or beyond n take no part and are never read.  On the GPU: three
+    launches -- those of the split-key decode with the (H / Hkv) Tq rows of a kv head dealt to row tiles of 16, every tile's key loops
+    ended at its own largest n -- and a workspace allocated per call of
+
+        B Hkv R ldw + 8 B Hkv S R D bytes,     R = (H / Hkv) Tq,  ldw = 16 ceil(Tk / 16)  (paged: Mp ps),  S the splits
+
+    (large in R: 512 tokens x 4 heads a kv head x 32768 keys are 64 MB per kv head) where D % 16 == 0, 16 <= D <= 128, ps is a power
+    of two >= 16 and q, k, v have 16-byte aligned bases and strides that are multiples of 16 (`torchlsq.extension.attn_chunk_w8_plan`
+    / `attn_chunk_paged_w8_plan` say which); every other input is (gathered and) composed from the existing ops, with the same bytes.
+    `splits`: 0 the library's own chunk, s >= 1 at most s splits of the keys (clamped to one per 64 keys); the bytes are the same for
+    every value.  The CPU path is that composition.  Returns a `LevelsTensor` [B, Tq, H D].  Inference only."""
+    what = "lsq_attention_chunk_w8_q"
+    _assert_has_ops()
+    q, k, v = _levels_in(what, q), _levels_in(what, k), _levels_in(what, v)
+    assert isinstance(splits, int) and not isinstance(splits, bool) and splits >= 0, "%s: splits must be an int >= 0, got %r" % (what, splits)
+    assert q.levels.dim() == 4 and k.levels.dim() == 4 and (block_table is None or block_table.dim() == 2), \
+        "%s: q must be [B, H, Tq, D], k and v [B, Hkv, Tk, D] (pools [Np, Hkv, ps, D] with a block_table [B, Mp]), got %s and %s" \
+        % (what, tuple(q.shape), tuple(k.shape))
+    sides = []
+    for name, side in (("scores_out", scores_out), ("probs_out", probs_out), ("out", out)):
+        assert side is not None and len(side) == 6, "%s: %s must be (scale, shift, quant_min, quant_max, type_min, type_max)" % (what, name)
+        sides.append(_out_args("%s (%s)" % (what, name), *side, False))
+    Tq = int(q.shape[2])
+    Tk = int(k.shape[2]) if block_table is None else int(block_table.shape[1]) * int(k.shape[2])
+    mode, off = 0, 0
+    if isinstance(causal, str):
+        assert causal == "lengths", "%s: causal must be None, a bool, an offset >= 0 or \"lengths\", got %r" % (what, causal)
+        assert key_lengths is not None, "%s: causal=\"lengths\" counts every row's keys back from key_lengths and needs them" % what
+        mode = 2
+    elif causal is True:
+        assert Tk >= Tq, "%s: causal=True lets the last query see every key and needs Tk >= Tq, got Tq = %d and Tk = %d" % (what, Tq, Tk)
+        mode, off = 1, Tk - Tq
+    elif causal is not None and causal is not False:
+        assert isinstance(causal, int) and causal >= 0, "%s: causal must be None, a bool, an offset >= 0 or \"lengths\", got %r" % (what, causal)
+        mode, off = 1, int(causal)
+    splits = min(splits, (Tk + 63) // 64)
+    head = (q.levels, q.scale, q.zero_point, k.levels, k.scale, k.zero_point, v.levels, v.scale, v.zero_point)
+    tail = (table, *sides[0][:6], *sides[1][:6], *sides[2][:6], mid_dtype, mode, off, key_lengths, splits)
+    if block_table is None:
+        lv = torch.ops.torchlsq.lsq_attention_chunk_w8_q8_q(*head, *tail)
+    else:
+        lv = torch.ops.torchlsq.lsq_attention_chunk_paged_w8_q8_q(*head, block_table, *tail)
+    o = sides[2]
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
 def lsq_kv_append_paged_w8(k: LevelsTensor, v: LevelsTensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, positions: Tensor = None):
     """The append into a PAGED KV cache, k and v in one launch and no arithmetic (liblsq_hip_attn_paged_w8.so): the levels of k and v
     [B, T, Hkv, D] (views of a qkv buffer are read in place; v, and a k that is rotated already) into the pools `k_pool` and `v_pool`

@@ -23,7 +23,7 @@ the steps in one launch of the decode kernel, through one module instance.
 import torch
 from torch import nn
 
-from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_decode_paged_w8_q, lsq_attention_decode_w8_q, lsq_attention_prefill_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
+from torchlsq.functional import (LevelsTensor, _act_constants, lsq_attention_chunk_w8_q, lsq_attention_decode_paged_w8_q, lsq_attention_decode_w8_q, lsq_attention_prefill_w8_q, lsq_attention_w8_q, lsq_bmm_w8, lsq_bmm_w8_q,
                                  lsq_masked_softmax_w8, lsq_masked_softmax_w8_q, lsq_softmax_table, lsq_softmax_w8, lsq_softmax_w8_q)
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import _MID_DTYPES, _as_levels
@@ -162,14 +162,22 @@ class AttentionCoreW8Q(nn.Module):
     the forward goes through `lsq_attention_decode_paged_w8_q` (liblsq_hip_attn_paged_w8.so) with the same constants, table, `causal`
     and `key_lengths`; `split`, where it is an int, gives `splits`, otherwise `splits` is 0 (the library's chunk).  Without a block
     table nothing changes.
+
+    CHUNK.  `chunk=True` (opt-in; an attribute, not a buffer: the `state_dict` is the same) sends EVERY forward, dense
+    or with a `block_table`, through `torchlsq.functional.lsq_attention_chunk_w8_q` (liblsq_hip_attn_chunk_w8.so) with the same
+    constants, table, `causal` and `key_lengths`: the same definition for any number of query rows against up to 65536 keys, `split`,
+    where it is an int, giving `splits` as in the paged route.  Only then may `causal` be "lengths": every row's keys are counted
+    back from `key_lengths` in the kernels, so a prompt is fed in pieces into a growing cache (the lengths the caches' `append`
+    returns) by one module instance, with no host read-back.  With `chunk=False` nothing changes.
     Inference only."""
 
     decode = False          # (the default of a module pickled before the attribute existed)
     prefill = False         # (likewise)
     split = None            # (likewise)
+    chunk = False           # (likewise)
 
     def __init__(self, scores_quantizer, probs_quantizer, out_quantizer, alpha=1.0, mid_dtype=torch.float32, fused=False, causal=False,
-                 decode=False, prefill=False, split=None):
+                 decode=False, prefill=False, split=None, chunk=False):
         super().__init__()
         assert split is None or split == "auto" or (isinstance(split, int) and not isinstance(split, bool) and split >= 1), \
             "AttentionCoreW8Q: split must be None, \"auto\" or an int >= 1, got %r" % (split,)
@@ -177,6 +185,7 @@ class AttentionCoreW8Q(nn.Module):
         self.decode = bool(decode)
         self.prefill = bool(prefill)
         self.split = split
+        self.chunk = bool(chunk)
         self.scores = MatmulW8Q(scores_quantizer, True, mid_dtype)
         self.softmax = SoftmaxW8Q(scores_quantizer, probs_quantizer, alpha, mid_dtype, row_pad=16, causal=causal)
         self.context = MatmulW8Q(out_quantizer, False, mid_dtype)
@@ -193,6 +202,13 @@ class AttentionCoreW8Q(nn.Module):
 
     def forward(self, q, k, v, key_lengths=None, block_table=None):
         q, k, v = _levels("AttentionCoreW8Q", q, k, v)
+        assert self.chunk or not isinstance(self.causal, str), \
+            "AttentionCoreW8Q: causal=%r (key counts taken from key_lengths in the kernels) needs chunk=True" % (self.causal,)
+        if self.chunk:
+            splits = self.split if isinstance(self.split, int) and not isinstance(self.split, bool) else 0
+            return lsq_attention_chunk_w8_q(q, k, v, self.softmax.table, self.scores._out("output"), self.softmax._out("output"),
+                                            self.context._out("output"), self.scores.mid_dtype, causal=self.causal, key_lengths=key_lengths,
+                                            block_table=block_table, splits=splits)
         if block_table is not None:
             assert self.decode or self.prefill, "AttentionCoreW8Q: a block_table (paged k and v) needs decode=True or prefill=True"
             splits = self.split if isinstance(self.split, int) and not isinstance(self.split, bool) else 0
@@ -233,6 +249,10 @@ class AttentionCoreW8Q(nn.Module):
         return LevelsTensor(buf, y.scale, y.zero_point, y.quant_min, y.quant_max, y.type_min, y.type_max)
 
     def extra_repr(self):
+        if self.chunk:
+            return "chunk=True (lsq_attention_chunk_w8_q: three launches over row tiles of 16, dense or paged k and v)%s%s" % (
+                "" if self.causal is None or self.causal is False else ", causal=%r" % (self.causal,),
+                ", splits=%d" % self.split if isinstance(self.split, int) and not isinstance(self.split, bool) else "")
         split = "" if self.split is None else ", split=%r (lsq_attention_decode_w8_q(split=...) where (H / Hkv) Tq <= 16)" % (self.split,)
         return self._repr_route() + (split if self.decode or self.prefill else "")
 
