@@ -829,6 +829,35 @@ def attn_chunk_w8_library():
     return _require_companion(_ATTN_CHUNK_W8_LIB, "attn_chunk_w8", "chunked prefill attention on 8-bit levels needs", attn_chunk_w8_error_str)
 
 
+# The gated product act(gate) * up of a gated MLP on 8-bit levels: a 256-entry float table on the gate byte, both operands read in
+# place through a row stride (include/lsq_hip_glu_w8.h): a twenty-fifth companion library; the ABIs above stay as they are.
+class LsqGluW8Shape(ctypes.Structure):
+    """lsq_glu_w8_shape (include/lsq_hip_glu_w8.h): gate, up and y [rows, C], the row strides of gate and up in bytes"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("rows", "C", "gate_row_stride", "up_row_stride")]
+
+
+class LsqGluW8Consts(ctypes.Structure):
+    """lsq_glu_w8_consts (include/lsq_hip_glu_w8.h): up's device constants, the output quantizer (or none) and mid_dtype"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("s_u", "z_u", "out_scale", "out_shift")] + \
+               [(name, ctypes.c_int64) for name in ("quant_min", "quant_max", "type_min", "type_max", "mid_dtype")]
+
+
+GLU_W8_ABI_VERSION = 1
+_GSP = ctypes.POINTER(LsqGluW8Shape)
+C_ABI_GLU_W8 = {
+    "lsq_glu_w8_abi_version": (_int, []),
+    "lsq_glu_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_glu_w8": (_int, [_int, _vp, _int, _vp, _vp, _GSP, ctypes.POINTER(LsqGluW8Consts), _vp, _vp]),
+    "lsq_glu_w8_plan": (_int, [_GSP, _int, _PLAN8]),
+}
+_GLU_W8_LIB, glu_w8_error_str = _load_companion("liblsq_hip_glu_w8.so", C_ABI_GLU_W8, "lsq_glu_w8_abi_version", GLU_W8_ABI_VERSION)
+
+
+def glu_w8_library():
+    """The ctypes handle of liblsq_hip_glu_w8.so (raises if it is missing)."""
+    return _require_companion(_GLU_W8_LIB, "glu_w8", "the gated product on 8-bit levels needs", glu_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -61,12 +61,13 @@ from ._attn_decode_split_w8_host import attn_decode_split_w8_plan, attn_decode_s
 from ._attn_paged_w8_host import (attn_paged_w8_plan, attn_paged_w8_q, kv_append_paged_w8, kv_append_paged_w8_plan,  # noqa: F401
                                   kv_gather_paged_w8)
 from ._attn_chunk_w8_host import attn_chunk_paged_w8_plan, attn_chunk_paged_w8_q, attn_chunk_w8_plan, attn_chunk_w8_q  # noqa: F401
+from ._glu_w8_host import glu_w8, glu_w8_plan, glu_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -315,6 +316,16 @@ _lib_def.define("lsq_attention_chunk_paged_w8_q8_q(Tensor q_levels, Tensor q_sca
                 "Tensor k_zero, Tensor v_pool, Tensor v_scale, Tensor v_zero, Tensor block_table, Tensor table, %s, %s, %s, "
                 "ScalarType mid_dtype, %s, int splits=0) -> Tensor"
                 % (tuple(_ATTN_SIDE % ((n,) * 6) for n in ("scores", "probs", "out")) + (_MASK_MODE,)))
+#  * THE GATED PRODUCT of a gated MLP on 8-bit LEVELS (liblsq_hip_glu_w8.so, include/lsq_hip_glu_w8.h): gate and up levels of the same
+#    shape [.., C], each with innermost stride 1 and one row stride over its leading axes (the halves of a fused linear's [.., 2 C]
+#    output are read in place; anything else is made dense first).  `table`: 256 float32 values holding values of `mid_dtype`,
+#    indexed by the gate byte as stored (`torchlsq.functional.lsq_glu_table` builds it from existing ops).  a = table[gate byte],
+#    d = up dequantized to `mid_dtype`, one rounded product, and the levels of the output quantizer (_q) or the floats themselves,
+#    as a new dense [.., C] tensor.  Inference only.
+_GLU = "Tensor gate_levels, Tensor up_levels, Tensor up_scale, Tensor up_zero, Tensor table"
+_lib_def.define("lsq_glu_w8_q8_q(%s, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, "
+                "int out_type_max, ScalarType mid_dtype) -> Tensor" % _GLU)
+_lib_def.define("lsq_glu_w8_q8(%s, ScalarType out_dtype) -> Tensor" % _GLU)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1284,3 +1295,28 @@ torch.library.register_fake("torchlsq::lsq_attention_chunk_paged_w8_q8_q", _fake
 _lib_def.impl("lsq_attention_chunk_w8_q8_q", _requant_no_grad("lsq_attention_chunk_w8_q8_q", (1, 4, 7, 10, 11, 16, 17, 22, 23)), "Autograd")
 _lib_def.impl("lsq_attention_chunk_paged_w8_q8_q", _requant_no_grad("lsq_attention_chunk_paged_w8_q8_q", (1, 4, 7, 11, 12, 17, 18, 23, 24)),
               "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the gated product on 8-bit levels (_glu_w8_host.py): GPU tensors -> liblsq_hip_glu_w8.so (one call, one launch), CPU tensors -> the
+# definition in torch ops; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_glu_w8_q8_q", glu_w8_q)
+    _lib_key.impl("lsq_glu_w8_q8", glu_w8)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_glu_w8_q8_q", lib=_lib_def)
+def _fake_glu_w8_q8_q(gate_levels, up_levels, up_scale, up_zero, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min,
+                      out_type_max, mid_dtype):
+    return torch.empty(gate_levels.shape, dtype=_fake_level_dtype(out_quant_max, out_type_max), device=gate_levels.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_glu_w8_q8", lib=_lib_def)
+def _fake_glu_w8_q8(gate_levels, up_levels, up_scale, up_zero, table, out_dtype):
+    return torch.empty(gate_levels.shape, dtype=out_dtype, device=gate_levels.device)
+
+
+_lib_def.impl("lsq_glu_w8_q8_q", _requant_no_grad("lsq_glu_w8_q8_q", (2, 4, 5, 6)), "Autograd")
+_lib_def.impl("lsq_glu_w8_q8", _requant_no_grad("lsq_glu_w8_q8", (2, 4)), "Autograd")

@@ -1280,6 +1280,86 @@ def lsq_mul_gate_w8(x: LevelsTensor, gate: LevelsTensor, out_dtype=torch.float32
     return torch.ops.torchlsq.lsq_mul_gate_w8_q8(*_gate_operands("lsq_mul_gate_w8", x, gate), out_dtype)
 
 
+# -------------------------------------------------------------------------------------------------
+# the gated product of a gated MLP (SwiGLU / GeGLU / classic GLU) on 8-bit levels: act(gate) * up in one launch
+# -------------------------------------------------------------------------------------------------
+def lsq_glu_table(fn, gate_scale: Tensor, gate_zero_point: Tensor, gate_dtype, act_out=None, mid_dtype=torch.float32) -> Tensor:
+    """The 256-entry FLOAT table (float32 [256], on `gate_scale`'s device, holding values of `mid_dtype`) of the gate side of a
+    gated MLP, built from existing ops alone -- no new kernel, nothing read back:
+
+        b = arange(256, uint8) viewed as `gate_dtype` (uint8 / int8): every byte a gate level can be stored as
+        u = LevelsTensor(b, gate_scale, gate_zero_point).dequantize(mid_dtype)
+        without an activation quantizer (`act_out` None):   A = fn(u).float()
+        with one, `act_out` = (scale, shift, quant_min, quant_max[, type_min, type_max]) of the quantizer after the activation:
+            A = LevelsTensor(lsq_act_table(fn, ..., act_out, mid_dtype), that quantizer's constants).dequantize(mid_dtype).float()
+
+    so `lsq_glu_w8_q(gate, up, A, ...)` equals the unfused chains `lsq_levels_per_tensor(fn(gate.dequantize(mid)) *
+    up.dequantize(mid), out)` and `lsq_mul_gate_w8_q(lsq_lut_w8(gate, act table), up, out)` on the same device, bit for bit.  `fn`
+    as in `act_function` ("silu", "gelu", "gelu_tanh", "sigmoid" for the classic GLU, "relu", ..., a module or any callable).
+    For the transcendental functions ATen's CPU and GPU kernels may round differently (`lsq_act_table`): build the table on the
+    device whose unfused chain it has to equal, or build it once and move it."""
+    _assert_has_ops()
+    assert gate_dtype in (torch.uint8, torch.int8), "lsq_glu_table: gate_dtype must be torch.uint8 or torch.int8"
+    assert mid_dtype in (torch.float32, torch.bfloat16, torch.float16), "lsq_glu_table: mid_dtype must be float32, bfloat16 or float16"
+    if act_out is not None:
+        assert isinstance(act_out, (tuple, list)) and len(act_out) in (4, 6), \
+            "lsq_glu_table: act_out is (scale, shift, quant_min, quant_max[, type_min, type_max]) of the activation's quantizer"
+        o = _out_args("lsq_glu_table", *act_out, *([None] * (6 - len(act_out))), False)
+        lv = lsq_act_table(fn, gate_scale, gate_zero_point, gate_dtype, *o[:6], mid_dtype=mid_dtype)
+        lv = lv if max(o[3], o[5]) > 127 else lv.view(torch.int8)
+        return _levels_out(lv, o[0], o[1], o[2:6]).dequantize(mid_dtype).float()
+    call, _ = act_function(fn)
+    b = torch.arange(256, dtype=torch.uint8, device=gate_scale.device).view(gate_dtype)
+    lo, hi = (0, 255) if gate_dtype == torch.uint8 else (-128, 127)
+    u = LevelsTensor(b, gate_scale.detach().reshape(-1)[:1].to(torch.float32), gate_zero_point, lo, hi).dequantize(mid_dtype)
+    v = u if call is None else call(u)
+    assert isinstance(v, Tensor) and v.shape == u.shape and v.dtype == mid_dtype, \
+        "lsq_glu_table: the function must return a %s tensor of its input's shape" % str(mid_dtype).replace("torch.", "")
+    return v.float()
+
+
+def _glu_operands(what, gate, up):
+    gate, up = _levels_in(what, gate), _levels_in(what, up)
+    assert gate.levels.dim() >= 1 and tuple(gate.shape) == tuple(up.shape), \
+        "%s needs gate and up of one shape [.., C], got %s and %s" % (what, tuple(gate.shape), tuple(up.shape))
+    return gate.levels, up.levels, up.scale, up.zero_point
+
+
+def lsq_glu_w8_q(gate: LevelsTensor, up: LevelsTensor, table: Tensor, out_scale: Tensor = None, out_shift: Tensor = None,
+                 out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                 mid_dtype=torch.float32) -> LevelsTensor:
+    """The gated product of a gated MLP on 8-bit levels with an 8-bit output, `act(gate) * up`: gate and up are `LevelsTensor`s
+    of one shape [.., C], with quantizers and level dtypes of their own, `table` is `lsq_glu_table`'s for gate's quantizer.
+    Per element a = table[gate byte], d = up.dequantize(mid_dtype), one rounded product, the output quantizer's levels -- ONE
+    launch (liblsq_hip_glu_w8.so), two bytes read and one written per element, nothing read back.  Each operand is read in place
+    where its innermost stride is 1 and its leading axes share one row stride: the halves `gu[..., :C]` and `gu[..., C:]` of a
+    fused gate_up linear's output are not copied.  Returns a dense `LevelsTensor` of that shape.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_glu_w8_q"
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    lv = torch.ops.torchlsq.lsq_glu_w8_q8_q(*_glu_operands(what, gate, up), table, *o[:6], mid_dtype)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_glu_w8(gate: LevelsTensor, up: LevelsTensor, table: Tensor, out_dtype=torch.float32) -> Tensor:
+    """`lsq_glu_w8_q` without an output quantizer: the products `round_to(out_dtype, table[gate byte] * up.dequantize(out_dtype))`
+    as a dense floating tensor of the operands' shape.  Inference only."""
+    _assert_has_ops()
+    return torch.ops.torchlsq.lsq_glu_w8_q8(*_glu_operands("lsq_glu_w8", gate, up), table, out_dtype)
+
+
+def lsq_glu_act_w8_q(gate: LevelsTensor, up: LevelsTensor, fn, out_scale: Tensor = None, out_shift: Tensor = None,
+                     out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                     act_out=None, mid_dtype=torch.float32) -> LevelsTensor:
+    """`lsq_glu_w8_q` for an activation given as in `act_function`: bit for bit `lsq_levels_per_tensor(fn(gate.dequantize(
+    mid_dtype)) * up.dequantize(mid_dtype), output quantizer)` on the operands' device.  THIS FUNCTION BUILDS THE TABLE ON EVERY
+    CALL (`lsq_glu_table`: a handful of launches on 256 elements) before the one launch of `lsq_glu_w8_q`;
+    `torchlsq.quantized.GLUW8Q` builds it once, at conversion.  Inference only."""
+    gate = _levels_in("lsq_glu_act_w8_q", gate)
+    table = lsq_glu_table(fn, gate.scale, gate.zero_point, gate.levels.dtype, act_out, mid_dtype)
+    return lsq_glu_w8_q(gate, up, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype)
+
+
 def _norm_rows(what, x, weight, bias, normalized_shape, dim):
     """(levels whose LAST axis is the normalised one, as a dense view where x's memory allows it; weight and bias flattened; the
     way back to x's shape and memory format)"""

@@ -19,6 +19,7 @@ from .modules.w8a8_add_q import AddW8A8Q, Conv2dW8A8AddQ, LinearW8A8AddQ, conver
 from .modules.pool_w8 import AdaptiveAvgPool2dW8Q, AvgPool2dW8Q, MaxPool2dW8, convert_w8a8_pool  # noqa: F401
 from .modules.dwconv_w8a8 import DepthwiseConv2dW8A8Q, convert_w8a8_depthwise  # noqa: F401
 from .modules.eltwise_w8 import ActivationW8Q, MulGateW8Q, convert_w8a8_eltwise  # noqa: F401
+from .modules.glu_w8 import GLUW8Q, GatedMLPW8Q, convert_w8a8_glu  # noqa: F401
 from .modules.norm_w8 import LayerNormW8Q, RMSNormW8Q, convert_w8a8_norm  # noqa: F401
 from .modules.attn_w8 import AttentionCoreW8Q, MatmulW8Q, SoftmaxW8Q  # noqa: F401
 from .modules.rope_w8 import KVCacheW8, RotaryW8Q  # noqa: F401
