@@ -858,6 +858,27 @@ def glu_w8_library():
     return _require_companion(_GLU_W8_LIB, "glu_w8", "the gated product on 8-bit levels needs", glu_w8_error_str)
 
 
+# The decode shape (M <= 16) of the W8A8 linears with an 8-bit output, with an optional levels residual: the 16-wave
+# weight-streaming kernel with a levels epilogue (include/lsq_hip_lindec_w8.h): a twenty-sixth companion library; the ABIs above stay
+# as they are.  Its output quantizer, residual and pre-quantizer are lsq_requant_w8's and lsq_resadd_w8's structs.
+LINDEC_W8_ABI_VERSION = 1
+LINDEC_W8_MAX_ROWS = 16         # LSQ_LINDEC_W8_MAX_ROWS: rows of x one launch serves
+C_ABI_LINDEC_W8 = {
+    "lsq_lindec_w8_abi_version": (_int, []),
+    "lsq_lindec_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_lindec_w8_linear_levels": (_int, [_int, _vp, _i64, _vp, _vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _int, _ROP, _RRP, _RPP, _vp,
+                                           _vp]),
+    "lsq_lindec_w8_plan": (_int, [_i64, _i64, _i64, _int, _int, _int, _PLAN8]),
+}
+_LINDEC_W8_LIB, lindec_w8_error_str = _load_companion("liblsq_hip_lindec_w8.so", C_ABI_LINDEC_W8, "lsq_lindec_w8_abi_version",
+                                                      LINDEC_W8_ABI_VERSION)
+
+
+def lindec_w8_library():
+    """The ctypes handle of liblsq_hip_lindec_w8.so (raises if it is missing)."""
+    return _require_companion(_LINDEC_W8_LIB, "lindec_w8", "the decode-shape W8A8 linears with an 8-bit output need", lindec_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -62,12 +62,13 @@ from ._attn_paged_w8_host import (attn_paged_w8_plan, attn_paged_w8_q, kv_append
                                   kv_gather_paged_w8)
 from ._attn_chunk_w8_host import attn_chunk_paged_w8_plan, attn_chunk_paged_w8_q, attn_chunk_w8_plan, attn_chunk_w8_q  # noqa: F401
 from ._glu_w8_host import glu_w8, glu_w8_plan, glu_w8_q  # noqa: F401
+from ._lindec_w8_host import lindec_w8_linear_levels, lindec_w8_linear_levels_add, lindec_w8_plan  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -181,6 +182,13 @@ _lib_def.define("lsq_linear_w8_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, 
                 "Tensor? bias, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
 _lib_def.define("lsq_conv2d_w8_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
                 "Tensor? bias, int[2] stride, int[2] padding, int[2] dilation, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
+#  * the two linear ops above for the DECODE SHAPE: the same schemas and, bit for bit, the same results; on the GPU a call whose
+#    flattened x has at most 16 rows (K % 16 == 0, K <= 65536, 16-byte aligned levels) runs the 16-wave weight-streaming kernel
+#    of liblsq_hip_lindec_w8.so (include/lsq_hip_lindec_w8.h), every other call the libraries of the ops above.  Inference only.
+_lib_def.define("lsq_linear_w8_q8_dec_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, %s, ScalarType mid_dtype) -> Tensor" % _OUT_Q)
+_lib_def.define("lsq_linear_w8_q8_dec_add_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
+                "Tensor? bias, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
 #  * 2-D pooling on 8-bit LEVELS [B, C, H, W], read channels-last (liblsq_hip_pool_w8.so, include/lsq_hip_pool_w8.h): the max pool
 #    gives levels of the same quantizer; the average pool sums (level - x_zero) exactly, takes (float(S) * x_scale) / float(D)
 #    in fp32 with ATen's divisor D, rounds to `mid_dtype` and gives the levels of the output quantizer (_q) or the floats
@@ -883,6 +891,20 @@ def _fake_conv2d_w8_q8_add_q(x_levels, s_x, zx, w_levels, w_scale, w_zero, bias,
 
 _lib_def.impl("lsq_linear_w8_q8_add_q", _requant_no_grad("lsq_linear_w8_q8_add_q", (1, 4, 6, 7, 8, 16, 18, 19)), "Autograd")
 _lib_def.impl("lsq_conv2d_w8_q8_add_q", _requant_no_grad("lsq_conv2d_w8_q8_add_q", (1, 4, 6, 10, 11, 19, 21, 22)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the decode shape of the two linear ops above (_lindec_w8_host.py): GPU tensors -> liblsq_hip_lindec_w8.so for what it serves, the
+# two libraries above for the rest; CPU tensors -> the same composition; the same shape-only and Autograd kernels.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_w8_q8_dec_q", lindec_w8_linear_levels)
+    _lib_key.impl("lsq_linear_w8_q8_dec_add_q", lindec_w8_linear_levels_add)
+del _lib_key
+torch.library.register_fake("torchlsq::lsq_linear_w8_q8_dec_q", _fake_linear_w8_q8_q, lib=_lib_def)
+torch.library.register_fake("torchlsq::lsq_linear_w8_q8_dec_add_q", _fake_linear_w8_q8_add_q, lib=_lib_def)
+_lib_def.impl("lsq_linear_w8_q8_dec_q", _requant_no_grad("lsq_linear_w8_q8_dec_q", (1, 4, 6, 7, 8)), "Autograd")
+_lib_def.impl("lsq_linear_w8_q8_dec_add_q", _requant_no_grad("lsq_linear_w8_q8_dec_add_q", (1, 4, 6, 7, 8, 16, 18, 19)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

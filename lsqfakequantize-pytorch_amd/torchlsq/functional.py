@@ -861,10 +861,25 @@ def _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type
     return (sc, sh, int(out_quant_min), int(out_quant_max), int(tmin), int(tmax), bool(relu))
 
 
+# Whether `lsq_linear_w8a8_q` / `lsq_linear_w8a8_add_q` and the modules on them take the decode-shape ops (liblsq_hip_lindec_w8.so)
+# when `decode` is None.  The bits are the same either way; this is a matter of speed alone, and the default is what the A/B
+# measurement of tools/exp_lindec_w8_ab.py decided (profiles/r35_lindec_w8_ab.txt: all 12 cases faster than the
+# 32-row tile beyond the spread, new / parent 0.30 to 0.55).
+W8A8_DECODE_DEFAULT = True
+W8A8_DECODE_MAX_ROWS = 16
+
+
+def _takes_decode(decode, levels):
+    """`decode` True / False / None (the module-level default) and at most 16 rows in the flattened levels"""
+    if decode is None:
+        decode = W8A8_DECODE_DEFAULT
+    return bool(decode) and levels.dim() >= 1 and levels.shape[-1] > 0 and levels.numel() // levels.shape[-1] <= W8A8_DECODE_MAX_ROWS
+
+
 def lsq_linear_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, scale: Tensor = None, shift: Tensor = None, quant_min: int = None,
                       quant_max: int = None, type_min: int = None, type_max: int = None, out_scale: Tensor = None,
                       out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None,
-                      out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32) -> LevelsTensor:
+                      out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32, decode: bool = None) -> LevelsTensor:
     """`lsq_linear_w8a8` with an 8-bit output: the integer sum, its fp32 steps `v`, `u = float(round_to(mid_dtype, v))`, an
     optional ReLU (a select: a NaN stays a NaN) and the levels of the per-tensor quantizer (`out_scale`, `out_shift`,
     `out_quant_min`, `out_quant_max`, type range) of `u` -- in one launch, one byte written per output
@@ -874,6 +889,8 @@ def lsq_linear_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, scale: Tensor = 
     x is a `LevelsTensor` (its device constants are used, nothing is read back), a per-tensor `torch.quint8` / `torch.qint8`
     tensor, or a floating tensor with the INPUT quantizer's `scale`, `shift`, `quant_min`, `quant_max` (then `mid_dtype` is x's
     dtype).  Returns a `LevelsTensor` whose constants are formed on the device from `out_scale` and `out_shift`.
+    `decode`: True takes the decode-shape op (liblsq_hip_lindec_w8.so: 16 waves per workgroup streaming the weight) when x is
+    levels of at most 16 rows, False never, None follows `W8A8_DECODE_DEFAULT`; the bits are the same either way.
     Inference only."""
     _assert_has_ops()
     what = "lsq_linear_w8a8_q"
@@ -882,7 +899,8 @@ def lsq_linear_w8a8_q(x, weight_q: Tensor, bias: Tensor = None, scale: Tensor = 
     if isinstance(x, Tensor) and x.is_quantized:
         x = LevelsTensor.from_quantized(x)
     if isinstance(x, LevelsTensor):
-        lv = torch.ops.torchlsq.lsq_linear_w8_q8_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype)
+        op = torch.ops.torchlsq.lsq_linear_w8_q8_dec_q if _takes_decode(decode, x.levels) else torch.ops.torchlsq.lsq_linear_w8_q8_q
+        lv = op(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype)
     else:
         assert scale is not None and shift is not None and quant_min is not None and quant_max is not None, \
             "%s on a floating x needs the input quantizer's scale, shift, quant_min and quant_max" % what
@@ -941,7 +959,7 @@ def lsq_linear_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTen
                           out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
                           relu: bool = False, mid_dtype=torch.float32, pre_scale: Tensor = None, pre_shift: Tensor = None,
                           pre_quant_min: int = None, pre_quant_max: int = None, pre_type_min: int = None,
-                          pre_type_max: int = None) -> LevelsTensor:
+                          pre_type_max: int = None, decode: bool = None) -> LevelsTensor:
     """The end of a residual block in one launch: `lsq_linear_w8a8_q` with `residual`, a `LevelsTensor` of the output's shape,
     added before the ReLU.  With u the layer's value rounded to `mid_dtype`: `p` is u, or with a pre-quantizer (`pre_scale`,
     `pre_shift`, `pre_quant_min`, `pre_quant_max`, type range: the layer's own output fake-quantizer, as a torch.ao QAT layer
@@ -951,7 +969,7 @@ def lsq_linear_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTen
     select, `lsq_levels_per_tensor`.
 
     x is a `LevelsTensor` or a per-tensor `torch.quint8` / `torch.qint8` tensor.  Returns a `LevelsTensor`; nothing is read
-    back from the device.  Inference only."""
+    back from the device.  `decode`: as in `lsq_linear_w8a8_q`.  Inference only."""
     _assert_has_ops()
     what = "lsq_linear_w8a8_add_q"
     w = w8_weight_operands(weight_q) + (bias,)
@@ -960,7 +978,8 @@ def lsq_linear_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTen
     if isinstance(x, Tensor) and x.is_quantized:
         x = LevelsTensor.from_quantized(x)
     assert isinstance(x, LevelsTensor), "%s needs x as a LevelsTensor or a per-tensor quantized tensor" % what
-    lv = torch.ops.torchlsq.lsq_linear_w8_q8_add_q(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype, *r)
+    op = torch.ops.torchlsq.lsq_linear_w8_q8_dec_add_q if _takes_decode(decode, x.levels) else torch.ops.torchlsq.lsq_linear_w8_q8_add_q
+    lv = op(x.levels, x.scale, x.zero_point, *w, *o, mid_dtype, *r)
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 

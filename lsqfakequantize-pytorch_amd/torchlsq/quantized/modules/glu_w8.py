@@ -94,6 +94,7 @@ def _fuse_linears(a, b):
         setattr(m, name, getattr(a, name).clone())
     if a.bias is not None:
         m.bias = nn.Parameter(torch.cat([a.bias.detach(), b.bias.detach()], 0), requires_grad=False)
+    m.decode = a.decode
     return m
 
 
@@ -124,12 +125,13 @@ class GatedMLPW8Q(nn.Module):
 
     @classmethod
     def from_float(cls, gate_proj, up_proj, down, act, input_quantizer, gate_quantizer, up_quantizer, hidden_quantizer,
-                   act_quantizer=None, mid_dtype=torch.float32):
+                   act_quantizer=None, mid_dtype=torch.float32, decode=None):
         """from the (QAT) linear layers `gate_proj` and `up_proj`, the ALREADY CONVERTED down projection (`LinearW8A8Q` /
         `LinearW8A8AddQ`), the activation, and the trained per-tensor `LSQFakeQuantizer`s of the MLP's input, of the two
         projections' outputs, of the product (the down projection's input) and, where the model has one, of the activation's
         output.  When `gate_quantizer is up_quantizer` the two projections become ONE linear and the product reads its halves
-        in place; otherwise two."""
+        in place; otherwise two.  `decode` becomes the `decode` attribute of the projections made here (the down projection
+        keeps its own)."""
         if not isinstance(down, (LinearW8A8Q, LinearW8A8AddQ)):
             raise ValueError("GatedMLPW8Q.from_float: the down projection must be a converted LinearW8A8Q or LinearW8A8AddQ, got %s"
                              % type(down).__name__)
@@ -138,6 +140,7 @@ class GatedMLPW8Q(nn.Module):
             raise ValueError("GatedMLPW8Q.from_float: gate_proj and up_proj must have one shape [C, K] and down must read C features")
         g = LinearW8A8Q.from_float(gate_proj, input_quantizer, gate_quantizer, False, mid_dtype)
         u = LinearW8A8Q.from_float(up_proj, input_quantizer, up_quantizer, False, mid_dtype)
+        g.decode = u.decode = decode
         glu = GLUW8Q.from_float(act, gate_quantizer, hidden_quantizer, act_quantizer, mid_dtype, device=g.weight_levels.device)
         if gate_quantizer is up_quantizer:
             m = cls(glu, down, gate_up=_fuse_linears(g, u))
@@ -151,14 +154,15 @@ _GLU_NEEDED = ("input_quantizer", "gate_quantizer", "up_quantizer", "hidden_quan
 _GLU_KEYS = _GLU_NEEDED + ("act_quantizer", "add_quantizer")
 
 
-def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False):
+def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False, decode=None):
     """Replace the gated MLP modules of `model`.  `mlps` maps the qualified name of a module that has `gate_proj`, `up_proj` and
     `down_proj` linear children and an `act_fn` (or `act`) child to a dict of trained per-tensor `LSQFakeQuantizer`s:
     `input_quantizer`, `gate_quantizer`, `up_quantizer` (the same object as `gate_quantizer`: ONE fused gate_up linear),
     `hidden_quantizer` (the product's, the down projection's input), `down_output_quantizer` (the down projection's own output)
     and optionally `act_quantizer` (between the activation and the product) and `add_quantizer` (the quantizer of the block's
     residual add: the down projection becomes a `LinearW8A8AddQ`, and `forward(x, residual)` hands the residual to it).  The
-    module becomes a `GatedMLPW8Q`.  Anything else is refused by name.  Returns the model (a deep copy unless inplace=True)."""
+    module becomes a `GatedMLPW8Q`.  Anything else is refused by name.  `decode` becomes the `decode` attribute of every linear
+    layer made here.  Returns the model (a deep copy unless inplace=True)."""
     assert mid_dtype in _MID_DTYPES.values(), "mid_dtype must be torch.float32, torch.bfloat16 or torch.float16"
     if not inplace:
         model = copy.deepcopy(model)
@@ -178,8 +182,9 @@ def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False):
                                              mid_dtype=mid_dtype)
         else:
             down = LinearW8A8Q.from_float(child.down_proj, q["hidden_quantizer"], q["down_output_quantizer"], False, mid_dtype)
+        down.decode = decode
         swaps.append((name, GatedMLPW8Q.from_float(child.gate_proj, child.up_proj, down, act, q["input_quantizer"], q["gate_quantizer"],
-                                                   q["up_quantizer"], q["hidden_quantizer"], q.get("act_quantizer"), mid_dtype)))
+                                                   q["up_quantizer"], q["hidden_quantizer"], q.get("act_quantizer"), mid_dtype, decode)))
     for name, new in swaps:
         if name == "":
             return new

@@ -10,7 +10,7 @@ import copy
 import torch
 from torch import nn
 
-from torchlsq.functional import LevelsTensor
+from torchlsq.functional import LevelsTensor, _takes_decode
 from .linear_w8a8 import _is_w8_linear
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_q import Conv2dW8A8Q, LinearW8A8Q, _as_levels, _has_batch_norm, _plain_or_relu_conv
@@ -99,9 +99,10 @@ class LinearW8A8AddQ(_PreQuantizer, LinearW8A8Q):
     def _launch(self, x, residual, relu):
         x = _as_levels(x)
         assert isinstance(x, LevelsTensor), "LinearW8A8AddQ reads levels: a LevelsTensor or a per-tensor quantized tensor"
-        lv = torch.ops.torchlsq.lsq_linear_w8_q8_add_q(x.levels, x.scale, x.zero_point, self.weight_levels, self.weight_scale,
-                                                       self.weight_zero_point, self.bias, *self._out_args_with(relu), self.mid_dtype,
-                                                       *self._res_args(residual))
+        ops = torch.ops.torchlsq
+        op = ops.lsq_linear_w8_q8_dec_add_q if _takes_decode(self.decode, x.levels) else ops.lsq_linear_w8_q8_add_q
+        lv = op(x.levels, x.scale, x.zero_point, self.weight_levels, self.weight_scale, self.weight_zero_point, self.bias,
+                *self._out_args_with(relu), self.mid_dtype, *self._res_args(residual))
         return self._wrap(lv)
 
     @classmethod
@@ -168,7 +169,7 @@ class AddW8A8Q(nn.Module):
         return self._close(a, b, True)
 
 
-def convert_w8a8_add_q(model, adds, input_quantizers, mid_dtype=torch.float32, inplace=False):
+def convert_w8a8_add_q(model, adds, input_quantizers, mid_dtype=torch.float32, inplace=False, decode=None):
     """Replace the ends of the residual blocks of `model`.  `adds` maps the qualified name of a block's
     `torch.ao.nn.quantized.FloatFunctional` to the name of the layer whose output it adds to the identity, e.g.
     `{"layer1.0.add_relu": "layer1.0.conv2"}`; `input_quantizers` maps that layer's name to the trained per-tensor
@@ -176,7 +177,8 @@ def convert_w8a8_add_q(model, adds, input_quantizers, mid_dtype=torch.float32, i
     FloatFunctional's `activation_post_process` and whose pre-quantizer is the layer's own `activation_post_process` if it has
     one; the FloatFunctional becomes an `AddW8A8Q`, so the block's `forward` (`self.add_relu.add_relu(out, identity)`) stays
     as it is.  A layer with a batch norm is refused by name.  `convert_w8a8_q` serves the other layers of the same model: the
-    two work on disjoint names.  Returns the model (a deep copy unless inplace=True)."""
+    two work on disjoint names.  `decode` becomes the `decode` attribute of every converted linear layer.  Returns the model (a
+    deep copy unless inplace=True)."""
     if not inplace:
         model = copy.deepcopy(model)
     modules = dict(model.named_modules())
@@ -195,6 +197,7 @@ def convert_w8a8_add_q(model, adds, input_quantizers, mid_dtype=torch.float32, i
             new = Conv2dW8A8AddQ.from_float(*args, mid_dtype=mid_dtype)
         elif _is_w8_linear(child):
             new = LinearW8A8AddQ.from_float(*args, mid_dtype=mid_dtype)
+            new.decode = decode
         else:
             raise ValueError("convert_w8a8_add_q: %r is not a linear layer or a 2-D convolution with groups == 1 and zero padding that "
                              "has a trained per-channel (ch_axis 0) or per-tensor LSQFakeQuantizer weight quantizer" % name)

@@ -10,7 +10,7 @@ import copy
 import torch
 from torch import nn
 
-from torchlsq.functional import LevelsTensor, _act_constants
+from torchlsq.functional import LevelsTensor, _act_constants, _takes_decode
 from .conv_w8a8 import Conv2dW8A8, _is_w8_conv
 from .linear_w8a8 import LinearW8A8, _is_w8_linear
 from .observers import LSQFakeQuantizer
@@ -81,25 +81,29 @@ class LinearW8A8Q(LinearW8A8, _OutputQuantizer):
                  output_range=(0, 255, 0, 255), relu=False, mid_dtype=torch.float32):
         super().__init__(in_features, out_features, bias, device, weight_dtype, input_range)
         self._init_output(device, output_range, relu, mid_dtype)
+        self.decode = None      # True: the decode-shape op for at most 16 rows of levels; False: never; None: the functional default
 
     def forward(self, x):
         w = (self.weight_levels, self.weight_scale, self.weight_zero_point, self.bias)
         x = _as_levels(x)
         if isinstance(x, LevelsTensor):
-            lv = torch.ops.torchlsq.lsq_linear_w8_q8_q(x.levels, x.scale, x.zero_point, *w, *self._out_args(), self.mid_dtype)
+            ops = torch.ops.torchlsq
+            op = ops.lsq_linear_w8_q8_dec_q if _takes_decode(self.decode, x.levels) else ops.lsq_linear_w8_q8_q
+            lv = op(x.levels, x.scale, x.zero_point, *w, *self._out_args(), self.mid_dtype)
         else:
             lv = torch.ops.torchlsq.lsq_linear_w8_a8_q(x, self.input_scale, self.input_shift, *self.input_range, *w, *self._out_args())
         return self._wrap(lv)
 
     def get_extra_state(self):
-        return dict(super().get_extra_state(), **self._output_state())
+        return dict(super().get_extra_state(), decode=self.decode, **self._output_state())
 
     def set_extra_state(self, state):
         super().set_extra_state(state)
         self._load_output_state(state)
+        self.decode = state.get("decode")       # a state dict from before the attribute: None
 
     def extra_repr(self):
-        return super().extra_repr() + self._output_repr()
+        return super().extra_repr() + self._output_repr() + ("" if self.decode is None else ", decode=%s" % self.decode)
 
     @classmethod
     def from_quantized(cls, weight_q, bias=None, input_quantizer=None, output_quantizer=None, relu=False, mid_dtype=torch.float32):
@@ -206,7 +210,7 @@ def _plain_or_relu_conv(mod):
     return _is_w8_conv(mod)
 
 
-def convert_w8a8_q(model, input_quantizers, output_quantizers, relu=(), mid_dtype=torch.float32, inplace=False):
+def convert_w8a8_q(model, input_quantizers, output_quantizers, relu=(), mid_dtype=torch.float32, inplace=False, decode=None):
     """Replace the layers of `model` that `input_quantizers` lists -- a dict from a module's qualified name to the trained
     per-tensor `LSQFakeQuantizer` of its input -- by `LinearW8A8Q` / `Conv2dW8A8Q`.  `output_quantizers` maps the same names to
     the quantizer of the layer's output (the next layer's input quantizer); a name it leaves out takes the layer's
@@ -214,8 +218,8 @@ def convert_w8a8_q(model, input_quantizers, output_quantizers, relu=(), mid_dtyp
     sits in an `nn.Sequential` directly before an `nn.ReLU`, that module becomes an `nn.Identity`; otherwise remove the ReLU
     from the model's forward yourself.  `torch.ao.nn.intrinsic.qat.ConvReLU2d` and `LinearReLU` convert with relu on; a module
     with a batch norm is refused by name.  `mid_dtype`: the dtype in which the unfused model handed y to the next quantizer.
-    Modules between two converted layers must pass a `LevelsTensor` on (`nn.Flatten` and `nn.Identity` do).  Returns the model
-    (a deep copy unless inplace=True)."""
+    Modules between two converted layers must pass a `LevelsTensor` on (`nn.Flatten` and `nn.Identity` do).  `decode` becomes
+    the `decode` attribute of every converted linear layer.  Returns the model (a deep copy unless inplace=True)."""
     if not inplace:
         model = copy.deepcopy(model)
     modules = dict(model.named_modules())
@@ -231,6 +235,7 @@ def convert_w8a8_q(model, input_quantizers, output_quantizers, relu=(), mid_dtyp
             new = Conv2dW8A8Q.from_float(*args)
         elif child is not None and _is_w8_linear(child):
             new = LinearW8A8Q.from_float(*args)
+            new.decode = decode
         else:
             raise ValueError("convert_w8a8_q: %r is not a linear layer or a 2-D convolution with groups == 1 and zero padding that "
                              "has a trained per-channel (ch_axis 0) or per-tensor LSQFakeQuantizer weight quantizer" % name)

@@ -1,0 +1,147 @@
+"""liblsq_hip_lindec_w8.so on the GPU: every byte against the plain reference of tests/test_lindec_w8_cpu.py and against the existing
+GPU op on the same operands.  No tolerance anywhere."""
+import copy
+
+import pytest
+import torch
+
+import test_lindec_w8_cpu as C
+from test_lindec_w8_cpu import BF16, F16, F32, I8, NONE, PRE, RES, U8
+from torchlsq import extension as E
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _big_n():
+    return 16 * (torch.cuda.get_device_properties(0).multi_processor_count + 1)     # the persistent loop's second pass
+
+
+# (M, N, K, residual, x, weight, residual and output level types, mid_dtype, relu, bias); N = 0 stands for 16 (CUs + 1).
+# K: 16 less than one wave's step, 272 a partial step and idle waves, 4096 resident, 4112 restaged per tile; N: 40 a tail tile, clamped
+# rows, byte stores.  (A case needs some hundred outputs to meet requant_w8_cases' condition: M = 1 goes with the widest N.)
+CASES = [(16, 16, 16, PRE, U8, I8, U8, True, BF16, False, "f32"),
+         (3, 40, 16, RES, U8, I8, U8, True, BF16, False, "f32"),
+         (16, 48, 16, NONE, U8, I8, U8, True, BF16, False, "f32"),
+         (3, 40, 272, NONE, U8, I8, U8, True, F32, False, "f32"),
+         (16, 40, 272, RES, I8, U8, I8, False, BF16, False, "f32"),
+         (3, 40, 272, PRE, U8, I8, U8, True, F16, False, None),
+         (16, 16, 4096, NONE, U8, I8, U8, True, BF16, False, "f32"),
+         (3, 40, 4096, RES, U8, I8, U8, True, BF16, False, "f32"),
+         (16, 48, 4096, PRE, U8, U8, I8, False, F16, False, "f32"),
+         (16, 16, 4112, NONE, I8, I8, U8, False, BF16, False, None),
+         (3, 40, 4112, RES, U8, I8, U8, True, F32, False, "f32"),
+         (16, 48, 4112, PRE, U8, I8, U8, True, BF16, False, "f32"),
+         (1, 0, 64, NONE, U8, I8, U8, True, BF16, True, "f32"),
+         (16, 0, 64, RES, U8, I8, U8, True, BF16, True, "f32"),
+         (3, 0, 64, PRE, I8, U8, I8, False, F16, False, "f32"),
+         (1, 0, 64, RES, U8, I8, U8, True, F32, False, "f32"),
+         (16, 48, 272, RES, U8, I8, U8, True, F32, False, None),
+         (16, 16, 272, NONE, U8, I8, U8, False, BF16, False, "f32")]
+
+
+def _case(spec):
+    spec = list(spec)
+    spec[1] = spec[1] or _big_n()
+    return C.case(*spec)
+
+
+@pytest.mark.parametrize("spec", CASES, ids=lambda s: "-".join(str(v).replace("torch.", "") for v in s))
+def test_bytes_equal_the_reference_and_the_existing_op(spec):
+    c = _case(spec)
+    M, N, K = spec[0], c["want"].shape[1], spec[2]
+    assert E.lindec_w8_plan(M, N, K)["served"]
+    got, old = C.run(c, DEV), C.run(c, DEV, dec=False)
+    again = C.run(c, DEV)
+    torch.cuda.synchronize()
+    assert torch.equal(got.cpu(), c["want"]) and torch.equal(got, old) and torch.equal(got, again)
+    if M > 1:           # a row's bytes depend on that row alone
+        one = dict(lin=(c["lin"][0][1:2],) + c["lin"][1:], res=None if c["res"] is None else (c["res"][0][1:2],) + c["res"][1:])
+        assert torch.equal(C.run(one, DEV).cpu(), c["want"][1:2])
+
+
+@pytest.mark.parametrize("kind", [NONE, PRE])
+def test_longest_k_with_border_levels(kind):
+    """K = 65536, M = N = 16: row m of x holds level 0 on its first 4096 (m + 1) k and 255 after them, against zx = 255; an even row of w
+    holds -128 on a prefix and 127 after it against zw = 127, an odd one 127 and then -128 against zw = -128.  So (15, 14) has every
+    raw product at 2^14, the raw int32 sum at 2^30 and I = 65536 * 255 * 255 > 2^31, and (15, 15) has I = -65536 * 255 * 255"""
+    K, k = 65536, torch.arange(65536)
+    n = torch.arange(16).reshape(16, 1)
+    lx = torch.where(k < (n + 1) * 4096, 0, 255).to(U8)
+    even = n % 2 == 0
+    lw = torch.where((k < (n // 2 * 2 + 2) * 4096) == even, -128, 127).to(I8)
+    s, z = torch.tensor([2.0 ** -10]), torch.tensor([255], dtype=torch.int32)
+    s_w, zw = torch.full((16,), 2.0 ** -12), torch.where(even.flatten(), 127, -128).to(torch.int32)
+    I = (lx.long() - 255) @ (lw.long() - zw.long().reshape(-1, 1)).t()
+    assert int(I[15, 14]) == K * 255 * 255 > 2 ** 31 and int(I[15, 15]) == -K * 255 * 255 and int((lx[15].long() - 128) @ lw[14].long()) == 2 ** 30
+    v = (s_w * I.float()) * s
+    bias = torch.zeros(16)
+    osc, osh, rng = C.R.out_quantizer(v + bias, True, False)
+    res = None
+    if kind == PRE:
+        res = (C.W.levels((16, 16), 0, 255, 5), 0.4 * osc, torch.tensor([128], dtype=torch.int32), 1.1 * osc, -128 * 1.1 * osc, 0, 255, 0, 255)
+    c = dict(lin=(lx, s, z, lw, s_w, zw, bias, osc, osh, rng, False, F32), res=res)
+    want = C.reference(c)
+    C.R.assert_not_vacuous(want, rng, "K = 65536")
+    got, old = C.run(c, DEV), C.run(c, DEV, dec=False)
+    torch.cuda.synchronize()
+    assert torch.equal(got.cpu(), want) and torch.equal(got, old)
+
+
+@pytest.mark.parametrize("spec", [(3, 40, 272, PRE), (16, 48, 4112, RES), (16, 16, 64, NONE)])
+def test_odd_byte_offsets_and_guard_bytes(spec):
+    """y and the residual at odd byte offsets inside larger buffers (byte stores and byte loads); the guard bytes stay as they were"""
+    c = C.case(*spec)
+    M, N = c["want"].shape
+    buf = torch.full((M * N + 64,), 0x5A, dtype=torch.uint8, device=DEV)
+    out = buf[31:31 + M * N].view(M, N)
+    if c["res"] is not None:
+        rbuf = torch.full((M * N + 64,), 0xA5, dtype=torch.uint8, device=DEV)
+        rbuf[13:13 + M * N] = c["res"][0].to(DEV).flatten()
+        c = dict(c, res=(rbuf[13:13 + M * N].view(M, N),) + c["res"][1:])
+    C.run(c, DEV, out=out)
+    torch.cuda.synchronize()
+    assert torch.equal(out.cpu(), c["want"])
+    assert bool((buf[:31] == 0x5A).all()) and bool((buf[31 + M * N:] == 0x5A).all())
+    if c["res"] is not None:
+        assert bool((rbuf[:13] == 0xA5).all()) and bool((rbuf[13 + M * N:] == 0xA5).all())
+
+
+@pytest.mark.parametrize("spec", [(3, 40, 4112, PRE), (16, 48, 4096, NONE)])
+def test_a_call_in_a_graph(spec):
+    c = C.moved(C.case(*spec), DEV)                 # nothing is copied to the device during the capture
+    eager = C.run(c, DEV)
+    out = torch.zeros_like(eager)
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        C.run(c, DEV, out=out)                      # warm-up: the LDS opt-in is not captured
+        out.zero_()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream):
+            held = C.run(c, DEV, out=out)
+        for _ in range(3):
+            out.zero_()
+            graph.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(held, eager) and torch.equal(out, eager)
+
+
+def test_one_decode_step_of_the_llama_layer():
+    """tests/decoder_glu_w8_cases.py's layer, prompt then single-token steps: with every linear's decode=True each stage and the
+    cache hold the bytes they hold with decode=False (and the CPU run's)"""
+    import decoder_glu_w8_cases as L
+    from torchlsq.functional import LevelsTensor
+    mid, name = torch.bfloat16, "short"
+    xl = L.input_levels(name)
+    xg = LevelsTensor(xl.levels.to(DEV), xl.scale.to(DEV), xl.zero_point.to(DEV), xl.quant_min, xl.quant_max)
+    runs = {}
+    for decode in (False, True):
+        layer = copy.deepcopy(L.chain(name, mid)).to(DEV)
+        for lin in (layer.qkv, layer.proj, layer.mlp.gate_up, layer.mlp.down):
+            lin.decode = decode
+        with torch.no_grad():
+            runs[decode] = L.sequence(layer, xg, L.make_cache(name, "dense", DEV), L.chunks_of(name, "steps"))
+    assert L.CASES[name]["B"] <= 16 and L.CASES[name]["steps"] >= 1
+    assert L.differing(runs[True], runs[False]) == [] and L.differing(runs[True], L.cpu_run(name, mid, "steps")) == []
