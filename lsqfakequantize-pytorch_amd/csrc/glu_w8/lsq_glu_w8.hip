@@ -18,7 +18,7 @@
 
 #include "../lsq_kernels.hpp"
 #include "../lsq_companion_abi.hpp"
-#include "../lsq_w8_out_side.hpp"
+#include "lsq_glu_w8_dev.hpp"
 #include "../lsq_w8_out_side_host.hpp"
 #include "../../../include/lsq_hip_glu_w8.h"
 
@@ -28,34 +28,11 @@ constexpr int kGluMaxP = 2;                     // packet positions per lane: th
 constexpr int kGluBlocksPerCU = 2;              // the grid "fills the chip" from here
 static_assert(kBlock == 256, "the table is staged one entry per thread");
 
-struct GluArg {             // kernel argument: the constants
-    const float* s_u;
-    const int32_t* z_u;
-    const float* scale;     // the output quantizer; NULL: a floating y
-    const float* shift;
-    float qmin, qmax, tmin, tmax;
-    int mid;                // LSQ_F32 / LSQ_BF16 / LSQ_F16
-    uint32_t flip_u;        // 0x80808080 for int8 levels of up (biased by 128 on load), 0 for uint8
-};
-
 struct GluGeom {            // kernel argument; the host has checked that every product fits 63 bits
     int64_t gs, us;         // the row strides of gate and up, bytes
     int C, P;               // columns, 16-column packets of a row
     int small;              // every item index of the launch fits 32 bits
 };
-
-struct GluQ : W8OutSide {   // the constants, read once per thread
-    float s_u, z_u, off_u;  // off_u: 128.0f for int8 levels, what the flipped byte carries too much; 0.0f for uint8
-};
-
-__device__ __forceinline__ GluQ glu_constants(const GluArg& a) {
-    GluQ q;
-    w8o_constants(q, a);
-    q.s_u = a.s_u[0];
-    q.z_u = static_cast<float>(a.z_u[0]);
-    q.off_u = a.flip_u ? 128.0f : 0.0f;
-    return q;
-}
 
 __device__ __forceinline__ int64_t glu_min(int64_t a, int64_t b) { return a < b ? a : b; }
 
@@ -70,18 +47,6 @@ __device__ __forceinline__ void glu_split(int64_t item, int per, int small, int6
         col = item - row * per;
     }
 }
-
-// LevelsTensor.dequantize(mid) of byte `I` of a packet's word `w` of up, which was flipped by 0x80 per byte for int8 levels so
-// that it holds level + off as an unsigned byte: float(level) = float(byte) - off exactly, then (float(level) - float(zero)) *
-// scale, rounded to mid
-template <int I>
-__device__ __forceinline__ float glu_dequant(uint32_t w, const GluQ& q) {
-    const float l = __fsub_rn(static_cast<float>((w >> (8 * I)) & 0xffu), q.off_u);
-    return w8o_round_mid(__fmul_rn(__fsub_rn(l, q.z_u), q.s_u), q.mid);
-}
-
-// t of the contract: one rounded fp32 multiply (never an fma), one rounding to mid
-__device__ __forceinline__ float glu_product(float a, float d, int mid) { return w8o_round_mid(__fmul_rn(a, d), mid); }
 
 // the four elements of one word of gate (as stored) and of up (flipped)
 __device__ __forceinline__ void glu_word(float* t, const float* tab, uint32_t gw, uint32_t uw, const GluQ& q) {

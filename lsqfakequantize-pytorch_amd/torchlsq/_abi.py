@@ -879,6 +879,34 @@ def lindec_w8_library():
     return _require_companion(_LINDEC_W8_LIB, "lindec_w8", "the decode-shape W8A8 linears with an 8-bit output need", lindec_w8_error_str)
 
 
+# The gate and up linears of a gated MLP's decode step (M <= 16) with the gated product in their epilogue: one launch, the levels of
+# act(gate) * up out (include/lsq_hip_linglu_w8.h): a twenty-seventh companion library; the ABIs above stay as they are.  Its
+# projections carry lsq_requant_w8's output quantizer, its product lsq_glu_w8's constants.
+class LsqLingluW8Proj(ctypes.Structure):
+    """lsq_linglu_w8_proj (include/lsq_hip_linglu_w8.h): one projection's weight, per-row constants, bias and output quantizer"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("w_levels", "w_scale", "w_zero", "bias")] + [("out", _ROP)] + \
+               [(name, ctypes.c_int64) for name in ("w_level_dtype", "bias_dtype")]
+
+
+LINGLU_W8_ABI_VERSION = 1
+LINGLU_W8_MAX_ROWS = 16         # LSQ_LINGLU_W8_MAX_ROWS: rows of x one launch serves
+_LPP = ctypes.POINTER(LsqLingluW8Proj)
+C_ABI_LINGLU_W8 = {
+    "lsq_linglu_w8_abi_version": (_int, []),
+    "lsq_linglu_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_linglu_w8": (_int, [_int, _vp, _i64, _vp, _vp, _LPP, _LPP, _i64, _i64, _vp, ctypes.POINTER(LsqGluW8Consts), _vp, _vp]),
+    "lsq_linglu_w8_plan": (_int, [_i64, _i64, _i64, _int, _int, _PLAN8]),
+}
+_LINGLU_W8_LIB, linglu_w8_error_str = _load_companion("liblsq_hip_linglu_w8.so", C_ABI_LINGLU_W8, "lsq_linglu_w8_abi_version",
+                                                      LINGLU_W8_ABI_VERSION)
+
+
+def linglu_w8_library():
+    """The ctypes handle of liblsq_hip_linglu_w8.so (raises if it is missing)."""
+    return _require_companion(_LINGLU_W8_LIB, "linglu_w8", "the decode-shape gate and up linears with the gated product in their epilogue need",
+                              linglu_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -1379,6 +1379,48 @@ def lsq_glu_act_w8_q(gate: LevelsTensor, up: LevelsTensor, fn, out_scale: Tensor
     return lsq_glu_w8_q(gate, up, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype)
 
 
+# Whether `lsq_gated_linear_w8a8_q` and `GatedMLPW8Q` take the one-launch op (liblsq_hip_linglu_w8.so: the gated product in the
+# epilogue of the decode-shape gate and up linears) when `glu_epilogue` is None.  The bits are the same either way; this is a
+# matter of speed alone, and the default is what the A/B measurement of tools/exp_linglu_w8_ab.py decided (DESIGN.md 9.29,
+# profiles/r36_linglu_w8_ab.txt: all 7 cases faster than the two- or three-launch route beyond the spread, new / parent 0.77 to 0.93).
+W8A8_GLU_EPILOGUE_DEFAULT = True
+
+
+def _takes_glu_epilogue(glu_epilogue, levels):
+    """`glu_epilogue` True / False / None (the module-level default) and at most 16 rows in the flattened levels"""
+    return _takes_decode(W8A8_GLU_EPILOGUE_DEFAULT if glu_epilogue is None else glu_epilogue, levels)
+
+
+def lsq_gated_linear_w8a8_q(x: LevelsTensor, gate_weight_q: Tensor, up_weight_q: Tensor, table: Tensor, gate_out, up_out=None,
+                            gate_bias: Tensor = None, up_bias: Tensor = None, out_scale: Tensor = None, out_shift: Tensor = None,
+                            out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                            mid_dtype=torch.float32, glu_epilogue: bool = None, decode: bool = None) -> LevelsTensor:
+    """The first half of a gated MLP on levels, `act(gate_proj(x)) * up_proj(x)`: bit for bit
+    `lsq_glu_w8_q(lsq_linear_w8a8_q(x, gate_weight_q, ...), lsq_linear_w8a8_q(x, up_weight_q, ...), table, ...)`.  `gate_out` and
+    `up_out` (None: gate's) are the projections' output quantizers as (scale, shift, quant_min, quant_max[, type_min, type_max]),
+    `table` is `lsq_glu_table`'s for gate's, the `out_*` arguments are the product's quantizer.
+    `glu_epilogue`: True takes ONE launch (liblsq_hip_linglu_w8.so: the two weight strips streamed by 16 waves per workgroup, the
+    product formed in LDS, the [.., 2 C] bytes between the steps never written) when x has at most 16 rows, False never, None
+    follows `W8A8_GLU_EPILOGUE_DEFAULT`; otherwise the two linears (with `decode`) and the product run one after the other.
+    Inference only."""
+    _assert_has_ops()
+    what = "lsq_gated_linear_w8a8_q"
+    x = _levels_in(what, x)
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    g = _out_args(what + " (gate_out)", *gate_out, *([None] * (6 - len(gate_out))), False)
+    u = g if up_out is None else _out_args(what + " (up_out)", *up_out, *([None] * (6 - len(up_out))), False)
+    if _takes_glu_epilogue(glu_epilogue, x.levels):
+        s_u, z_u = _act_constants(u[0], u[1], u[4], u[5])
+        lv = torch.ops.torchlsq.lsq_linear_w8_q8_dec_glu_q(x.levels, x.scale, x.zero_point, *w8_weight_operands(gate_weight_q), gate_bias,
+                                                           *g[:6], *w8_weight_operands(up_weight_q), up_bias, *u[:6], s_u, z_u, table,
+                                                           *o[:6], mid_dtype)
+        return _levels_out(lv, o[0], o[1], o[2:6])
+    kw = dict(mid_dtype=mid_dtype, decode=decode)
+    gate = lsq_linear_w8a8_q(x, gate_weight_q, gate_bias, None, None, None, None, None, None, *g[:6], **kw)
+    up = lsq_linear_w8a8_q(x, up_weight_q, up_bias, None, None, None, None, None, None, *u[:6], **kw)
+    return lsq_glu_w8_q(gate, up, table, *o[:6], mid_dtype)
+
+
 def _norm_rows(what, x, weight, bias, normalized_shape, dim):
     """(levels whose LAST axis is the normalised one, as a dense view where x's memory allows it; weight and bias flattened; the
     way back to x's shape and memory format)"""

@@ -10,7 +10,7 @@ import copy
 import torch
 from torch import nn
 
-from torchlsq.functional import LevelsTensor, _act_constants, act_function, lsq_glu_table
+from torchlsq.functional import LevelsTensor, _act_constants, _takes_glu_epilogue, act_function, lsq_glu_table
 from .eltwise_w8 import _EltwiseOutput, _level_dtype
 from .packed_linear_a8 import _per_tensor_constants
 from .w8a8_add_q import LinearW8A8AddQ
@@ -102,9 +102,11 @@ class GatedMLPW8Q(nn.Module):
     """`down(act(gate_proj(x)) * up_proj(x))` on levels.  Children: `gate_up` (ONE `LinearW8A8Q` of 2 C output rows, gate's then
     up's) or `gate_proj` and `up_proj` (two), `glu` (`GLUW8Q`) and `down` (`LinearW8A8Q` / `LinearW8A8AddQ`).
     `forward(x, residual=None)`: x a `LevelsTensor`; the residual, a `LevelsTensor`, is handed to a `LinearW8A8AddQ` down.
-    Inference only."""
+    `glu_epilogue` (extra state; True / False / None: `torchlsq.functional.W8A8_GLU_EPILOGUE_DEFAULT`): where it resolves to True
+    and x has at most 16 rows, the projections and the product are ONE launch (`lsq_linear_w8_q8_dec_glu_q`,
+    liblsq_hip_linglu_w8.so) with the same bytes.  Inference only."""
 
-    def __init__(self, glu, down, gate_up=None, gate_proj=None, up_proj=None):
+    def __init__(self, glu, down, gate_up=None, gate_proj=None, up_proj=None, glu_epilogue=None):
         super().__init__()
         assert (gate_up is None) != (gate_proj is None) and (gate_proj is None) == (up_proj is None), \
             "GatedMLPW8Q takes one fused gate_up linear or the pair gate_proj, up_proj"
@@ -114,24 +116,68 @@ class GatedMLPW8Q(nn.Module):
         else:
             self.gate_proj, self.up_proj = gate_proj, up_proj
         self.glu, self.down = glu, down
+        self.glu_epilogue = glu_epilogue
+
+    def _projections(self):
+        """(w_levels, w_scale, w_zero, bias) of gate and of up -- the halves of the fused linear as views -- and their two linears"""
+        if not self.fused:
+            g, u = self.gate_proj, self.up_proj
+            return ((g.weight_levels, g.weight_scale, g.weight_zero_point, g.bias),
+                    (u.weight_levels, u.weight_scale, u.weight_zero_point, u.bias), g, u)
+        m, C = self.gate_up, self.gate_up.out_features // 2
+        w = (m.weight_levels, m.weight_scale, m.weight_zero_point, m.bias)
+        return tuple(None if t is None else t[:C] for t in w), tuple(None if t is None else t[C:] for t in w), m, m
+
+    def _product_in_epilogue(self, x):
+        gw, uw, g, u = self._projections()
+        glu = self.glu
+        s_u, z_u = _act_constants(u.output_scale, u.output_shift, u.output_range[2], u.output_range[3])      # u._wrap's, on the device
+        lv = torch.ops.torchlsq.lsq_linear_w8_q8_dec_glu_q(x.levels, x.scale, x.zero_point, *gw, g.output_scale, g.output_shift,
+                                                           *g.output_range, *uw, u.output_scale, u.output_shift, *u.output_range, s_u, z_u,
+                                                           glu.table, glu.output_scale, glu.output_shift, *glu.output_range, glu.mid_dtype)
+        return glu._wrap(lv)
 
     def forward(self, x, residual=None):
-        h = self.glu(self.gate_up(x)) if self.fused else self.glu(self.gate_proj(x), self.up_proj(x))
+        x = _as_levels(x)
+        lins = (self.gate_up,) if self.fused else (self.gate_proj, self.up_proj)
+        if isinstance(x, LevelsTensor) and _takes_glu_epilogue(self.glu_epilogue, x.levels) and \
+                all(type(m) is LinearW8A8Q and not m.relu and m.mid_dtype == self.glu.mid_dtype for m in lins):
+            h = self._product_in_epilogue(x)
+        else:
+            h = self.glu(self.gate_up(x)) if self.fused else self.glu(self.gate_proj(x), self.up_proj(x))
         if residual is not None:
             if not isinstance(self.down, LinearW8A8AddQ):
                 raise TypeError("GatedMLPW8Q: a residual needs a LinearW8A8AddQ as the down projection, got %s" % type(self.down).__name__)
             return self.down(h, residual)
         return self.down(h)
 
+    def get_extra_state(self):
+        return dict(glu_epilogue=self.glu_epilogue)
+
+    def set_extra_state(self, state):
+        self.glu_epilogue = state.get("glu_epilogue")
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if self.glu_epilogue is None:       # the default is not written: the keys are those of a state dict from before the attribute
+            destination.pop(prefix + "_extra_state", None)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        state_dict.setdefault(prefix + "_extra_state", {})      # no key: None
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def extra_repr(self):
+        return "" if self.glu_epilogue is None else "glu_epilogue=%s" % self.glu_epilogue
+
     @classmethod
     def from_float(cls, gate_proj, up_proj, down, act, input_quantizer, gate_quantizer, up_quantizer, hidden_quantizer,
-                   act_quantizer=None, mid_dtype=torch.float32, decode=None):
+                   act_quantizer=None, mid_dtype=torch.float32, decode=None, glu_epilogue=None):
         """from the (QAT) linear layers `gate_proj` and `up_proj`, the ALREADY CONVERTED down projection (`LinearW8A8Q` /
         `LinearW8A8AddQ`), the activation, and the trained per-tensor `LSQFakeQuantizer`s of the MLP's input, of the two
         projections' outputs, of the product (the down projection's input) and, where the model has one, of the activation's
         output.  When `gate_quantizer is up_quantizer` the two projections become ONE linear and the product reads its halves
         in place; otherwise two.  `decode` becomes the `decode` attribute of the projections made here (the down projection
-        keeps its own)."""
+        keeps its own), `glu_epilogue` the module's."""
         if not isinstance(down, (LinearW8A8Q, LinearW8A8AddQ)):
             raise ValueError("GatedMLPW8Q.from_float: the down projection must be a converted LinearW8A8Q or LinearW8A8AddQ, got %s"
                              % type(down).__name__)
@@ -143,9 +189,9 @@ class GatedMLPW8Q(nn.Module):
         g.decode = u.decode = decode
         glu = GLUW8Q.from_float(act, gate_quantizer, hidden_quantizer, act_quantizer, mid_dtype, device=g.weight_levels.device)
         if gate_quantizer is up_quantizer:
-            m = cls(glu, down, gate_up=_fuse_linears(g, u))
+            m = cls(glu, down, gate_up=_fuse_linears(g, u), glu_epilogue=glu_epilogue)
         else:
-            m = cls(glu, down, gate_proj=g, up_proj=u)
+            m = cls(glu, down, gate_proj=g, up_proj=u, glu_epilogue=glu_epilogue)
         m.train(gate_proj.training)
         return m
 
@@ -154,7 +200,7 @@ _GLU_NEEDED = ("input_quantizer", "gate_quantizer", "up_quantizer", "hidden_quan
 _GLU_KEYS = _GLU_NEEDED + ("act_quantizer", "add_quantizer")
 
 
-def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False, decode=None):
+def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False, decode=None, glu_epilogue=None):
     """Replace the gated MLP modules of `model`.  `mlps` maps the qualified name of a module that has `gate_proj`, `up_proj` and
     `down_proj` linear children and an `act_fn` (or `act`) child to a dict of trained per-tensor `LSQFakeQuantizer`s:
     `input_quantizer`, `gate_quantizer`, `up_quantizer` (the same object as `gate_quantizer`: ONE fused gate_up linear),
@@ -162,7 +208,7 @@ def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False, decode
     and optionally `act_quantizer` (between the activation and the product) and `add_quantizer` (the quantizer of the block's
     residual add: the down projection becomes a `LinearW8A8AddQ`, and `forward(x, residual)` hands the residual to it).  The
     module becomes a `GatedMLPW8Q`.  Anything else is refused by name.  `decode` becomes the `decode` attribute of every linear
-    layer made here.  Returns the model (a deep copy unless inplace=True)."""
+    layer made here, `glu_epilogue` that of every `GatedMLPW8Q`.  Returns the model (a deep copy unless inplace=True)."""
     assert mid_dtype in _MID_DTYPES.values(), "mid_dtype must be torch.float32, torch.bfloat16 or torch.float16"
     if not inplace:
         model = copy.deepcopy(model)
@@ -184,7 +230,8 @@ def convert_w8a8_glu(model, mlps, mid_dtype=torch.float32, inplace=False, decode
             down = LinearW8A8Q.from_float(child.down_proj, q["hidden_quantizer"], q["down_output_quantizer"], False, mid_dtype)
         down.decode = decode
         swaps.append((name, GatedMLPW8Q.from_float(child.gate_proj, child.up_proj, down, act, q["input_quantizer"], q["gate_quantizer"],
-                                                   q["up_quantizer"], q["hidden_quantizer"], q.get("act_quantizer"), mid_dtype, decode)))
+                                                   q["up_quantizer"], q["hidden_quantizer"], q.get("act_quantizer"), mid_dtype, decode,
+                                                   glu_epilogue)))
     for name, new in swaps:
         if name == "":
             return new
