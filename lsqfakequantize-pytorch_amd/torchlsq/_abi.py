@@ -907,6 +907,37 @@ def linglu_w8_library():
                               linglu_w8_error_str)
 
 
+# The qkv linear of an attention block's decode step (M <= 16) with the rotary embedding and the KV-cache append in its epilogue: one
+# launch, the rotated q levels out and k and v in a dense cache or a paged pool (include/lsq_hip_linrope_w8.h): a twenty-eighth
+# companion library; the ABIs above stay as they are.  Its projection is the linglu library's struct (the same fields), its rotation
+# lsq_rope_w8's two sides, its pages lsq_attn_paged_w8's.
+class LsqLinropeW8Geom(ctypes.Structure):
+    """lsq_linrope_w8_geom (include/lsq_hip_linrope_w8.h): the extents, the style, rq's strides, dense or paged, and the (batch or
+    page, token or slot, head) strides of k's and v's destination"""
+    _fields_ = [(name, ctypes.c_int64) for name in ("B", "T", "H", "Hkv", "D", "R", "P", "style", "q_sb", "q_st", "q_sh", "paged", "Tmax",
+                                                    "k_so", "k_st", "k_sh", "v_so", "v_st", "v_sh")] + [("pages", LsqAttnPagedW8Pages)]
+
+
+LINROPE_W8_ABI_VERSION = 1
+LINROPE_W8_MAX_ROWS = 16        # LSQ_LINROPE_W8_MAX_ROWS: rows of x one launch serves
+_LRG = ctypes.POINTER(LsqLinropeW8Geom)
+C_ABI_LINROPE_W8 = {
+    "lsq_linrope_w8_abi_version": (_int, []),
+    "lsq_linrope_w8_last_error": (ctypes.c_char_p, []),
+    "lsq_linrope_w8": (_int, [_int, _vp, _vp, _vp, _LPP, _i64, _i64, _LRG, ctypes.POINTER(LsqRopeW8In), ctypes.POINTER(LsqRopeW8Out), _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_linrope_w8_plan": (_int, [_LRG, _i64, _int, _PLAN9]),
+}
+_LINROPE_W8_LIB, linrope_w8_error_str = _load_companion("liblsq_hip_linrope_w8.so", C_ABI_LINROPE_W8, "lsq_linrope_w8_abi_version",
+                                                        LINROPE_W8_ABI_VERSION)
+
+
+def linrope_w8_library():
+    """The ctypes handle of liblsq_hip_linrope_w8.so (raises if it is missing)."""
+    return _require_companion(_LINROPE_W8_LIB, "linrope_w8", "the decode-shape qkv linear with the rotary embedding and the KV-cache append "
+                              "in its epilogue needs", linrope_w8_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

@@ -1990,3 +1990,56 @@ def lsq_kv_append_paged_w8(k: LevelsTensor, v: LevelsTensor, k_pool: Tensor, v_p
     torch.ops.torchlsq.lsq_kv_append_paged_w8(k.levels, v.levels, k_pool, v_pool, block_table, positions)
     return (LevelsTensor(k_pool, k.scale, k.zero_point, k.quant_min, k.quant_max, k.type_min, k.type_max),
             LevelsTensor(v_pool, v.scale, v.zero_point, v.quant_min, v.quant_max, v.type_min, v.type_max))
+
+
+# Whether `lsq_qkv_rope_append_w8a8_q` and `QKVRotaryW8Q` take the one-launch op (liblsq_hip_linrope_w8.so: the rotary embedding and the
+# KV-cache append in the epilogue of the decode-shape qkv linear) when `rope_epilogue` is None.  The bits are the same either way; this
+# is a matter of speed alone, and the default is what the A/B measurement of tools/exp_linrope_w8_ab.py decided (DESIGN.md 9.30,
+# profiles/r37_linrope_w8_ab.txt: all 12 cases faster than the four-launch route beyond the spread, new / parent 0.52 to 0.72).
+W8A8_ROPE_EPILOGUE_DEFAULT = True
+
+
+def _takes_rope_epilogue(rope_epilogue, levels):
+    """`rope_epilogue` True / False / None (the module-level default) and at most 16 rows in the flattened levels"""
+    return _takes_decode(W8A8_ROPE_EPILOGUE_DEFAULT if rope_epilogue is None else rope_epilogue, levels)
+
+
+def lsq_qkv_rope_append_w8a8_q(x: LevelsTensor, weight_q: Tensor, cos: Tensor, sin: Tensor, qkv_out, rot_out, heads: int, kv_heads: int,
+                               k_cache: Tensor, v_cache: Tensor, positions: Tensor = None, block_table: Tensor = None, bias: Tensor = None,
+                               mid_dtype=torch.float32, rope_epilogue: bool = None, decode: bool = None):
+    """The first half of an attention block on levels: the qkv projection of x [B, T, K] (`weight_q` [(heads + 2 kv_heads) D, K]),
+    the rotary embedding (the half style, `cos` / `sin` from `lsq_rope_tables`) of its q and k heads at `positions[b] + t`, and the
+    append of the rotated k and of v into `k_cache` / `v_cache`: dense [B, kv_heads, Tmax, D] tensors, or with `block_table` (int32
+    [B, Mp]) the pools [Np, kv_heads, ps, D] of a paged cache.  Bit for bit `lsq_linear_w8a8_q`, `lsq_rope_w8_q` on the q view, and
+    for k and v `lsq_rope_w8_q(..., out=cache, scatter=True)` + `lsq_kv_append_w8`, or `lsq_rope_w8_q` + `lsq_kv_append_paged_w8`.
+    `qkv_out` and `rot_out` are the quantizers of the projection's and of the rotation's output as (scale, shift, quant_min,
+    quant_max[, type_min, type_max]).  `positions` (int32 [B] on the device) is read, never advanced.
+    `rope_epilogue`: True takes ONE launch (liblsq_hip_linrope_w8.so: the weight streamed in pairs of strips by 16 waves per
+    workgroup, the rotation formed in LDS, the qkv bytes never written) when x has at most 16 rows, False never, None follows
+    `W8A8_ROPE_EPILOGUE_DEFAULT`; otherwise the ops above run one after the other (the linear with `decode`).
+    Returns `(rq, k_levels, v_levels)`: the rotated q [B, T, heads, D] and the caches as `LevelsTensor`s.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_qkv_rope_append_w8a8_q"
+    x = _levels_in(what, x)
+    assert x.levels.dim() == 3, "%s needs levels of [B, T, K], got %s" % (what, tuple(x.shape))
+    g = _out_args(what + " (qkv_out)", *qkv_out, *([None] * (6 - len(qkv_out))), False)
+    r = _out_args(what + " (rot_out)", *rot_out, *([None] * (6 - len(rot_out))), False)
+    k_cache, v_cache = (c.levels if isinstance(c, LevelsTensor) else c for c in (k_cache, v_cache))
+    H, Hkv = int(heads), int(kv_heads)
+    if _takes_rope_epilogue(rope_epilogue, x.levels):
+        s_q, z_q = _act_constants(g[0], g[1], g[4], g[5])
+        rq = torch.ops.torchlsq.lsq_linear_w8_q8_dec_rope_q(x.levels, x.scale, x.zero_point, *w8_weight_operands(weight_q), bias, *g[:6],
+                                                            s_q, z_q, cos, sin, *r[:6], mid_dtype, H, Hkv, k_cache, v_cache, positions, block_table)
+        rq = _levels_out(rq, r[0], r[1], r[2:6])
+        return rq, LevelsTensor(k_cache, rq.scale, rq.zero_point, *r[2:6]), LevelsTensor(v_cache, s_q, z_q, *g[2:6])
+    qkv = lsq_linear_w8a8_q(x, weight_q, bias, None, None, None, None, None, None, *g[:6], mid_dtype=mid_dtype, decode=decode)
+    B, T = int(x.shape[0]), int(x.shape[1])
+    lv = qkv.levels.view(B, T, H + 2 * Hkv, -1)
+    q, k, v = (LevelsTensor(lv[:, :, a:b], qkv.scale, qkv.zero_point, *g[2:6]) for a, b in ((0, H), (H, H + Hkv), (H + Hkv, H + 2 * Hkv)))
+    rq = lsq_rope_w8_q(q, cos, sin, *r[:6], mid_dtype, positions)
+    if block_table is None:
+        kl = lsq_rope_w8_q(k, cos, sin, *r[:6], mid_dtype, positions, out=k_cache.permute(0, 2, 1, 3), scatter=True)
+        vl = lsq_kv_append_w8(v, v_cache.permute(0, 2, 1, 3), positions, scatter=True)
+        return rq, LevelsTensor(k_cache, kl.scale, kl.zero_point, *r[2:6]), LevelsTensor(v_cache, vl.scale, vl.zero_point, *g[2:6])
+    kl, vl = lsq_kv_append_paged_w8(lsq_rope_w8_q(k, cos, sin, *r[:6], mid_dtype, positions), v, k_cache, v_cache, block_table, positions)
+    return rq, kl, vl

@@ -20,7 +20,7 @@ class PagedKVCacheW8(nn.Module):
 
     `append(k, v, rotary=None)` mirrors `KVCacheW8.append`: a step's `LevelsTensor`s [B, T, Hkv, D]; with `rotary` (a `RotaryW8Q` with
     an output quantizer) k is first rotated at `lengths` into a [B, T, Hkv, D] buffer (one launch; the rotation fused into the paged
-    write is not served; `rotary`'s tables must cover the positions written, since a position beyond them is not rotated and leaves
+    write is `QKVRotaryW8Q`'s decode step, not this method's; `rotary`'s tables must cover the positions written, since a position beyond them is not rotated and leaves
     its row of that buffer as allocated), then k and v are written by `lsq_kv_append_paged_w8` (one launch) and `lengths.add_(T)`.  A token beyond
     `max_pages * page_size` or whose entry lies outside 0 .. num_pages - 1 is not written.  Returns `(k_pool, v_pool, lengths)`: the
     pools as `LevelsTensor`s [Np, Hkv, ps, D] and the new lengths, ready for `AttentionCoreW8Q(decode=True, causal=True).forward(q,
