@@ -45,8 +45,9 @@ def _halves_of_one(g, u):
     return parts
 
 
-def _composed(x_levels, s_x, zx, g, u, g_rng, u_rng, up_scale, up_zero, table, out_q, mid_dtype):
-    """the ops the new one composes, on either device: one linear on the fused weight where there is one, else two; the product"""
+def _composed(x_levels, s_x, zx, g, u, g_rng, u_rng, up_scale, up_zero, table, out_q, mid_dtype, out=None):
+    """the ops the new one composes, on either device: one linear on the fused weight where there is one, else two; the product
+    (`out`, GPU only: where it is written)"""
     same_q = g_rng == u_rng and g[4].data_ptr() == u[4].data_ptr() and g[5].data_ptr() == u[5].data_ptr()
     fused = _halves_of_one(g, u) if same_q else None
     if fused is not None:
@@ -56,7 +57,7 @@ def _composed(x_levels, s_x, zx, g, u, g_rng, u_rng, up_scale, up_zero, table, o
     else:
         gl = lindec_w8_linear_levels(x_levels, s_x, zx, *g[:4], g[4], g[5], *g_rng, False, mid_dtype)
         ul = lindec_w8_linear_levels(x_levels, s_x, zx, *u[:4], u[4], u[5], *u_rng, False, mid_dtype)
-    return glu_w8_q(gl, ul, up_scale, up_zero, table, *out_q, mid_dtype)
+    return glu_w8_q(gl, ul, up_scale, up_zero, table, *out_q, mid_dtype, out=out)
 
 
 def linglu_w8_q(x_levels, s_x, zx,
@@ -65,7 +66,7 @@ def linglu_w8_q(x_levels, s_x, zx,
                 up_w_levels, up_w_scale, up_w_zero, up_bias, up_out_scale, up_out_shift, up_quant_min, up_quant_max, up_type_min, up_type_max,
                 up_scale, up_zero, table, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, mid_dtype, out=None):
     """x_levels [.., K] bytes -> the levels [.., C] of table[gate byte] * up under the output quantizer.  `out` (not an argument of
-    the op, used by the one-launch route only): a dense [M, C] level tensor to write into, at any byte offset.  Inference only."""
+    the op, GPU only): a dense [M, C] level tensor to write into, at any byte offset, on either route.  Inference only."""
     what = "lsq_linear_w8_q8_dec_glu_q"
     _assert_has_ops()
     _check(x_levels.dtype in _LEVEL_CODE, "%s: the levels must be uint8 (0..255) or int8 (-128..127), got '%s'" % (what, _name(x_levels.dtype)))
@@ -111,6 +112,9 @@ def linglu_w8_q(x_levels, s_x, zx,
                             _stream_of(idx))
             _status(rc, "lsq_linglu_w8", lib, _ERR)
             return y.reshape(out_shape)
+        if out is not None:             # the product of the composition lands where the one launch would have put it
+            out = _take_out(what, out, (M, C), ydt, lx.device).view(out_shape)
+        return _composed(x_levels, s_x, zx, g, u, g_rng, u_rng, up_scale, up_zero, table, out_q, mid_dtype, out)
     return _composed(x_levels, s_x, zx, g, u, g_rng, u_rng, up_scale, up_zero, table, out_q, mid_dtype)
 
 

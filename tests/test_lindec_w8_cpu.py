@@ -63,6 +63,26 @@ def case(M, N, K, kind=NONE, x_dt=U8, w_dt=I8, r_dt=U8, unsigned=True, mid=BF16,
     return c
 
 
+@functools.lru_cache(maxsize=None)
+def extreme_lin(N=16):
+    """The twelve operands of the K = 65536, M = 16 case at the borders of what is served, on N weight rows (row n as row n % 16):
+    row m of x holds level 0 on its first 4096 (m + 1) k and 255 after them, against zx = 255; an even row of w holds -128 on a prefix
+    and 127 after it against zw = 127, an odd one 127 and then -128 against zw = -128.  So (15, 14) has every raw product at 2^14, the
+    raw int32 sum at 2^30 and I = 65536 * 255 * 255 > 2^31, and (15, 15) has I = -65536 * 255 * 255"""
+    K, k = 65536, torch.arange(65536)
+    m, n = torch.arange(16).reshape(16, 1), (torch.arange(N) % 16).reshape(N, 1)
+    lx = torch.where(k < (m + 1) * 4096, 0, 255).to(U8)
+    even = n % 2 == 0
+    lw = torch.where((k < (n // 2 * 2 + 2) * 4096) == even, -128, 127).to(I8)
+    s, z = torch.tensor([2.0 ** -10]), torch.tensor([255], dtype=torch.int32)
+    s_w, zw = torch.full((N,), 2.0 ** -12), torch.where(even.flatten(), 127, -128).to(torch.int32)
+    I = (lx.long() - 255) @ (lw.long() - zw.long().reshape(-1, 1)).t()
+    assert int(I[15, 14]) == K * 255 * 255 > 2 ** 31 and int(I[15, 15]) == -K * 255 * 255 and int((lx[15].long() - 128) @ lw[14].long()) == 2 ** 30
+    bias = torch.zeros(N)
+    osc, osh, rng = R.out_quantizer((s_w * I.float()) * s + bias, True, False)
+    return (lx, s, z, lw, s_w, zw, bias, osc, osh, rng, False, F32)
+
+
 def moved(c, device):
     res = None if c["res"] is None else tuple(R.to(device, *c["res"][:5])) + tuple(c["res"][5:])
     return dict(lin=tuple(R.to(device, *c["lin"][:9])) + tuple(c["lin"][9:]), res=res)

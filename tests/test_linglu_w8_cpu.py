@@ -32,6 +32,21 @@ def case(M, C, K, x_dt=U8, w_dt=I8, gate_u=True, up_u=True, out_u=True, mid=BF16
         both = [None if a is None else torch.cat((a, b)) for a, b in zip(gate[3:7], up[3:7])]
         gate = gate[:3] + tuple(None if t is None else t[:C] for t in both) + gate[7:]
         up = gate[:3] + tuple(None if t is None else t[C:] for t in both) + gate[7:]
+    return _with_product(gate, up, out_u, mid, fn, act_q, (M, C, K))
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_case():
+    """K = 65536, M = C = 16 on tests/test_lindec_w8_cpu.py's `extreme_lin`: the gate strip is its 16 weight rows, the up strip the same
+    rows in reverse order, so the outputs (15, 14) and (15, 15) of the gate and (15, 1) and (15, 0) of the up projection have the raw
+    int32 sum at 2^30 and |I| = 65536 * 255 * 255 > 2^31"""
+    gate = L.extreme_lin()
+    up = gate[:3] + tuple(t.flip(0).contiguous() for t in gate[3:7]) + gate[7:]
+    return _with_product(gate, up, True, F32, "silu", False, "K = 65536")
+
+
+def _with_product(gate, up, out_u, mid, fn, act_q, note):
+    """the case of two projections' operands: the product's table, its quantizer and the plain reference's bytes"""
     gb, ub = L.reference(dict(lin=gate, res=None)), L.reference(dict(lin=up, res=None))
     s_g, z_g = F._act_constants(gate[7], gate[8], *gate[9][2:])
     s_u, z_u = F._act_constants(up[7], up[8], *up[9][2:])
@@ -48,7 +63,7 @@ def case(M, C, K, x_dt=U8, w_dt=I8, gate_u=True, up_u=True, out_u=True, mid=BF16
     osc, osh, rng = G.out_quantizer(torch.from_numpy(t), out_u)
     lv = torch.from_numpy(E.numpy_levels(t, osc, osh, rng))
     c = dict(gate=gate, up=up, up_q=(s_u, z_u), table=table, out=(osc, osh, rng), mid=mid, want=lv.to(U8) if out_u else lv.to(I8))
-    R.assert_not_vacuous(c["want"], rng, (M, C, K))
+    R.assert_not_vacuous(c["want"], rng, note)
     return c
 
 

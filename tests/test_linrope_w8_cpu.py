@@ -20,16 +20,40 @@ FILL, TMAX, P = 0x5A, 32, 40            # the tables reach beyond the caches: a 
 
 
 @functools.lru_cache(maxsize=None)
-def case(B, T, H, Hkv, D, Rd, K, x_dt=U8, w_dt=I8, qkv_u=True, rot_u=True, mid=BF16, bias="f32", paged=None, shift=0):
+def case(B, T, H, Hkv, D, Rd, K, x_dt=U8, w_dt=I8, qkv_u=True, rot_u=True, mid=BF16, bias="f32", paged=None, shift=0, layout=None):
     """CPU operands of one case, built once and left unchanged.  `paged`: None (dense caches [B, Hkv, TMAX, D]) or (page size,
-    page_major).  positions[b] cycles through 0, TMAX - 1, TMAX, P and -2 from `shift`.  `want`: rq, k, v as the op must leave
-    destinations that held FILL; `at[b][t]`: (q written, k written, v written, batch entry or page, token or slot)"""
-    M, W = B * T, H + 2 * Hkv
-    lin = R.linear_case(M, W * D, K, (x_dt, 117 if x_dt == U8 else -11, w_dt, None, None, bias), (qkv_u, False, mid), 0)
+    page_major).  positions[b] cycles through 0, TMAX - 1, TMAX, P and -2 from `shift`.  `layout`: None or one of LAYOUTS, what
+    `call` hands the op besides.  `want`: rq, k, v as the op must leave destinations that held FILL; `at[b][t]`: (q written, k
+    written, v written, batch entry or page, token or slot)"""
+    lin = R.linear_case(B * T, (H + 2 * Hkv) * D, K, (x_dt, 117 if x_dt == U8 else -11, w_dt, None, None, bias), (qkv_u, False, mid), 0)
+    return _placed(lin, (B, T, H, Hkv, D), Rd, rot_u, paged, shift, layout)
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_case(paged=None):
+    """K = 65536 on tests/test_lindec_w8_cpu.py's `extreme_lin`: sixteen sequences of one token, one q, one k and one v head of 32
+    features, so the weight is [96, 65536] and every ROTATE and COPY item holds outputs with |I| = 65536 * 255 * 255 > 2^31"""
+    return _placed(L.extreme_lin(96), (16, 1, 1, 1, 32), 32, True, paged, 0, None)
+
+
+# what `call` hands the op besides the plain operands:
+#   rq_in_qkv      rq is the first H heads of a [B, T, H + 2 Hkv, D] buffer, whose other heads are guard bytes
+#   rq_padded      rq's heads lie D + 16 bytes apart, the 16 bytes behind each are guard bytes
+#   token_major    dense caches stored [B, TMAX, Hkv, D], handed over as their [B, Hkv, TMAX, D] views
+#   wide_table     the block table is the first Mp columns of a [B, Mp + 3] table whose other columns name pages of the NEXT sequence
+#   no_positions   positions=None: every sequence starts at token 0
+LAYOUTS = ("rq_in_qkv", "rq_padded", "token_major", "wide_table", "no_positions")
+
+
+def _placed(lin, dims, Rd, rot_u, paged, shift, layout):
+    """the case of a qkv projection's operands: the tables, the rotation's quantizer, the positions and what lands where"""
+    assert layout is None or layout in LAYOUTS, layout
+    B, T, H, Hkv, D = dims
+    W, K, mid = H + 2 * Hkv, lin[0].shape[1], lin[11]
     qkv = L.reference(dict(lin=lin, res=None)).view(B, T, W, D)
     s_q, z_q = F._act_constants(lin[7], lin[8], *lin[9][2:])
     cos, sin = F.lsq_rope_tables(Rd, P, 10000.0, mid)
-    pos = torch.tensor([(0, TMAX - 1, TMAX, P, -2)[(b + shift) % 5] for b in range(B)], dtype=torch.int32)
+    pos = torch.tensor([0 if layout == "no_positions" else (0, TMAX - 1, TMAX, P, -2)[(b + shift) % 5] for b in range(B)], dtype=torch.int32)
     p = pos.to(torch.int64).reshape(B, 1) + torch.arange(T).reshape(1, T)
     d = ((qkv[:, :, :H + Hkv].to(F32) - z_q.to(F32)) * s_q).to(mid)
     c, s = (t[p.clamp(0, P - 1)].to(mid).unsqueeze(2) for t in (cos, sin))
@@ -39,12 +63,15 @@ def case(B, T, H, Hkv, D, Rd, K, x_dt=U8, w_dt=I8, qkv_u=True, rot_u=True, mid=B
     lv = torch.from_numpy(E.numpy_levels(u.float().numpy(), rsc, rsh, rng))
     lv = lv.to(U8) if rot_u else lv.to(I8)
     R.assert_not_vacuous(lv, rng, (B, T, H, Hkv, D, Rd, K))
-    table = None
+    table, wide = None, None
     shape = (B, Hkv, TMAX, D)
     if paged is not None:
         ps, Mp = paged[0], TMAX // paged[0]
         Np = B * Mp + 3
         table = torch.randperm(Np, generator=torch.Generator().manual_seed(7))[:B * Mp].reshape(B, Mp).to(torch.int32)
+        if layout == "wide_table":      # a kernel that took the rows to lie Mp apart, or read beyond Mp, would write another sequence's page
+            wide = torch.cat((table, table.roll(-1, 0)[:, torch.arange(3) % Mp]), 1)
+            table = wide[:, :Mp]
         if B >= 7:
             table[5, 0], table[6, Mp - 1] = -1, Np + 1       # rows 5 and 6 sit at 0 and TMAX - 1 (shift 0): neither is written
         shape = (Np, Hkv, ps, D)
@@ -65,37 +92,48 @@ def case(B, T, H, Hkv, D, Rd, K, x_dt=U8, w_dt=I8, qkv_u=True, rot_u=True, mid=B
                 kc[outer, :, tok] = lv[b, t, H:]
             if there:
                 vc[outer, :, tok] = qkv[b, t, H + Hkv:]
-    return dict(lin=lin, cos=cos, sin=sin, pos=pos, rot=(rsc, rsh, rng), table=table, dims=(B, T, H, Hkv, D), paged=paged, at=at,
-                want=(rq, kc, vc))
+    return dict(lin=lin, cos=cos, sin=sin, pos=pos, rot=(rsc, rsh, rng), table=table, wide=wide, dims=(B, T, H, Hkv, D), paged=paged, at=at,
+                layout=layout, want=(rq, kc, vc))
 
 
 def call(c, device="cpu", fn=None, row=None, made=None):
     """`fn` (the host function by default) on the case's operands on `device`, into fresh destinations that lie inside larger buffers
     of FILL -> (rq, k, v, the guard bytes' tensors, `made`).  `row` = (b, t): on that row of x alone, as a call of its own.  `made`: the
-    (arguments, destinations, whole buffers) of an earlier call, used again as they are."""
+    (arguments, destinations, whole buffers, guard bytes) of an earlier call, used again as they are."""
     fn = fn or extension.linrope_w8_q
     B, T, H, Hkv, D = c["dims"]
-    lin, pos, table, rq_w, kc_w = c["lin"], c["pos"], c["table"], c["want"][0], c["want"][1]
+    lin, pos, table, rq_w, kc_w, layout = c["lin"], c["pos"], c["table"], c["want"][0], c["want"][1], c["layout"]
     x = lin[0].view(B, T, -1)
+    if c["wide"] is not None:                                   # (a copy of the slice alone would be dense)
+        table = c["wide"].to(device)[:, :table.shape[1]]
     if row is not None:
         b, t = row
         x, pos, table, B, T = x[b:b + 1, t:t + 1].contiguous(), pos[b:b + 1] + t, None if table is None else table[b:b + 1], 1, 1
+    elif layout == "no_positions":
+        pos = None
     if made is None:
         outer = kc_w.shape[0] if c["paged"] is not None else B
+        q_shape = {"rq_in_qkv": (T, H + 2 * Hkv, D), "rq_padded": (T, H, D + 16)}.get(layout, (T, H, D))
         big = [torch.full((n + 2,) + s, FILL, dtype=dt, device=device) for n, s, dt in
-               ((B, (T, H, D), rq_w.dtype), (outer, tuple(kc_w.shape[1:]), kc_w.dtype), (outer, tuple(kc_w.shape[1:]), c["want"][2].dtype))]
-        if c["paged"] is not None and not c["paged"][1]:        # storage [Np, ps, Hkv, D]: the pools are its permuted views
+               ((B, q_shape, rq_w.dtype), (outer, tuple(kc_w.shape[1:]), kc_w.dtype), (outer, tuple(kc_w.shape[1:]), c["want"][2].dtype))]
+        if (c["paged"] is not None and not c["paged"][1]) or layout == "token_major":
+            # storage [Np, ps, Hkv, D] or [B, TMAX, Hkv, D]: the pools or the caches are its permuted views
             big[1:] = [t.reshape(t.shape[0], t.shape[2], t.shape[1], D).permute(0, 2, 1, 3) for t in big[1:]]
+        guards = [t[i] for t in big for i in (0, -1)]
         rq, kc, vc = (t[1:-1] for t in big)
-        dev = R.to(device, x, *lin[1:9], *F._act_constants(lin[7], lin[8], *lin[9][2:]), c["cos"], c["sin"], *c["rot"][:2], pos, table)
-        made = ((*dev[:9], *lin[9], *dev[9:15], *c["rot"][2], lin[11], H, Hkv, kc, vc, dev[15], dev[16]), (rq, kc, vc), big)
-    args, (rq, kc, vc), big = made
-    return fn(*args, out=rq), kc, vc, [t[i] for t in big for i in (0, -1)], made
+        if layout in ("rq_in_qkv", "rq_padded"):
+            guards.append(rq[:, :, H:] if layout == "rq_in_qkv" else rq[..., D:])
+            rq = rq[:, :, :H, :D]
+        dev = R.to(device, x, *lin[1:9], *F._act_constants(lin[7], lin[8], *lin[9][2:]), c["cos"], c["sin"], *c["rot"][:2], pos)
+        made = ((*dev[:9], *lin[9], *dev[9:15], *c["rot"][2], lin[11], H, Hkv, kc, vc, dev[15], None if table is None else table.to(device)),
+                (rq, kc, vc), big, guards)
+    args, (rq, kc, vc), _, guards = made
+    return fn(*args, out=rq), kc, vc, guards, made
 
 
-def assert_row(c, device, b, t):
+def assert_row(c, device, b, t, fn=None):
     """the call on row (b, t) alone writes that row's bytes and nothing else"""
-    got = call(c, device, row=(b, t))[:3]
+    got = call(c, device, fn=fn, row=(b, t))[:3]
     q_on, k_on, v_on, outer, tok = c["at"][b][t]
     want = [torch.full(g.shape, FILL, dtype=g.dtype) for g in got]
     o = outer if c["paged"] is not None else 0
@@ -108,10 +146,17 @@ def assert_row(c, device, b, t):
     assert all(torch.equal(g.cpu(), w) for g, w in zip(got, want)), (b, t)
 
 
-# (B, T, H, Hkv, D, R, K, x, weight, qkv / rot levels unsigned, mid_dtype, bias, paged, shift)
+# (B, T, H, Hkv, D, R, K, x, weight, qkv / rot levels unsigned, mid_dtype, bias, paged, shift, layout)
+LAYOUT_CASES = [(2, 3, 2, 2, 64, 32, 272, U8, I8, True, True, F32, "f32", None, 1, "rq_in_qkv"),
+                (16, 1, 4, 1, 128, 128, 272, I8, U8, False, False, BF16, "f32", None, 0, "rq_padded"),
+                (2, 3, 2, 2, 64, 32, 4112, U8, I8, True, True, BF16, "f32", None, 3, "token_major"),
+                (16, 1, 2, 1, 32, 32, 272, U8, I8, True, True, BF16, "f32", (16, True), 0, "wide_table"),
+                (2, 3, 2, 2, 64, 32, 272, U8, I8, True, False, F16, None, (1, False), 0, "wide_table"),     # (b = 1 at TMAX - 1: row 1 is read)
+                (2, 3, 2, 2, 64, 32, 272, U8, I8, True, True, F32, "f32", None, 0, "no_positions"),
+                (16, 1, 2, 1, 32, 32, 272, I8, U8, False, True, BF16, None, (16, False), 0, "no_positions")]
 CPU_CASES = [(2, 3, 2, 2, 64, 32, 272, U8, I8, True, True, F32, "f32", None, 1),
              (16, 1, 2, 1, 32, 32, 16, I8, U8, False, False, BF16, None, (16, True), 0),
-             (3, 1, 2, 2, 64, 32, 4112, U8, I8, True, False, F16, "f32", (1, False), 0)]
+             (3, 1, 2, 2, 64, 32, 4112, U8, I8, True, False, F16, "f32", (1, False), 0)] + LAYOUT_CASES
 
 
 @pytest.mark.parametrize("spec", CPU_CASES, ids=lambda s: "-".join(str(v).replace("torch.", "") for v in s))
