@@ -879,6 +879,28 @@ def lindec_w8_library():
     return _require_companion(_LINDEC_W8_LIB, "lindec_w8", "the decode-shape W8A8 linears with an 8-bit output need", lindec_w8_error_str)
 
 
+# The decode shape (M <= 16) of the W4A8 / W2A8 linears on packed group-wise codes with an 8-bit output, with an optional levels
+# residual: qlinear_a8's order of the sum with lindec_w8's levels epilogue, one launch (include/lsq_hip_lindec_w4.h): a twenty-ninth
+# companion library; the ABIs above stay as they are.  Its structs are lsq_requant_w8's and lsq_resadd_w8's.
+LINDEC_W4_ABI_VERSION = 1
+LINDEC_W4_MAX_ROWS = 16         # LSQ_LINDEC_W4_MAX_ROWS: rows of x one launch serves
+C_ABI_LINDEC_W4 = {
+    "lsq_lindec_w4_abi_version": (_int, []),
+    "lsq_lindec_w4_last_error": (ctypes.c_char_p, []),
+    "lsq_lindec_w4_linear_levels": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _ROP, _RRP, _RPP,
+                                           _vp, _vp]),
+    "lsq_lindec_w4_plan": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _PLAN8]),
+}
+_LINDEC_W4_LIB, lindec_w4_error_str = _load_companion("liblsq_hip_lindec_w4.so", C_ABI_LINDEC_W4, "lsq_lindec_w4_abi_version",
+                                                      LINDEC_W4_ABI_VERSION)
+
+
+def lindec_w4_library():
+    """The ctypes handle of liblsq_hip_lindec_w4.so (raises if it is missing)."""
+    return _require_companion(_LINDEC_W4_LIB, "lindec_w4", "the decode-shape W4A8 / W2A8 linears with an 8-bit output need",
+                              lindec_w4_error_str)
+
+
 # The gate and up linears of a gated MLP's decode step (M <= 16) with the gated product in their epilogue: one launch, the levels of
 # act(gate) * up out (include/lsq_hip_linglu_w8.h): a twenty-seventh companion library; the ABIs above stay as they are.  Its
 # projections carry lsq_requant_w8's output quantizer, its product lsq_glu_w8's constants.

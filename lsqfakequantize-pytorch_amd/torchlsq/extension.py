@@ -64,13 +64,14 @@ from ._attn_chunk_w8_host import attn_chunk_paged_w8_plan, attn_chunk_paged_w8_q
 from ._glu_w8_host import glu_w8, glu_w8_plan, glu_w8_q  # noqa: F401
 from ._lindec_w8_host import lindec_w8_linear_levels, lindec_w8_linear_levels_add, lindec_w8_plan  # noqa: F401
 from ._linglu_w8_host import linglu_w8_plan, linglu_w8_q  # noqa: F401
+from ._lindec_w4_host import lindec_w4_linear_levels, lindec_w4_linear_levels_add, lindec_w4_plan  # noqa: F401
 from ._linrope_w8_host import linrope_w8_plan, linrope_w8_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_LINGLU_W8_LIB", "_LINROPE_W8_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str", "linglu_w8_error_str", "linrope_w8_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_LINGLU_W8_LIB", "_LINROPE_W8_LIB", "_LINDEC_W4_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str", "linglu_w8_error_str", "linrope_w8_error_str", "lindec_w4_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -191,6 +192,16 @@ _lib_def.define("lsq_linear_w8_q8_dec_q(Tensor x_levels, Tensor s_x, Tensor zx, 
                 "Tensor? bias, %s, ScalarType mid_dtype) -> Tensor" % _OUT_Q)
 _lib_def.define("lsq_linear_w8_q8_dec_add_q(Tensor x_levels, Tensor s_x, Tensor zx, Tensor w_levels, Tensor w_scale, Tensor w_zero, "
                 "Tensor? bias, %s, ScalarType mid_dtype, %s) -> Tensor" % (_OUT_Q, _RES_Q))
+#  * `lsq_linear_packed_q8` with an 8-bit OUTPUT, and with a levels RESIDUAL: activation levels on packed 4- / 2-bit group-wise codes,
+#    the output quantizer's levels out -- the float-output op writing a `mid_dtype` y, (the pre-quantizer, the residual add,) the
+#    select and `lsq_levels_per_tensor` composed, bit for bit.  On the GPU, with `decode`, a call of at most 16 rows on a format of
+#    the matrix-core form runs ONE launch of liblsq_hip_lindec_w4.so (include/lsq_hip_lindec_w4.h); every other call runs the
+#    composition from the existing ops.  Inference only.
+_PACKED_W = "Tensor codes, Tensor scale, Tensor zero_point, Tensor? bias, int group_size, int bits"
+_lib_def.define("lsq_linear_packed_q8_q(Tensor x_levels, Tensor s_x, Tensor zx, %s, %s, ScalarType mid_dtype, bool decode) -> Tensor"
+                % (_PACKED_W, _OUT_Q))
+_lib_def.define("lsq_linear_packed_q8_add_q(Tensor x_levels, Tensor s_x, Tensor zx, %s, %s, ScalarType mid_dtype, %s, bool decode) "
+                "-> Tensor" % (_PACKED_W, _OUT_Q, _RES_Q))
 #  * 2-D pooling on 8-bit LEVELS [B, C, H, W], read channels-last (liblsq_hip_pool_w8.so, include/lsq_hip_pool_w8.h): the max pool
 #    gives levels of the same quantizer; the average pool sums (level - x_zero) exactly, takes (float(S) * x_scale) / float(D)
 #    in fp32 with ATen's divisor D, rounds to `mid_dtype` and gives the levels of the output quantizer (_q) or the floats
@@ -931,6 +942,35 @@ torch.library.register_fake("torchlsq::lsq_linear_w8_q8_dec_q", _fake_linear_w8_
 torch.library.register_fake("torchlsq::lsq_linear_w8_q8_dec_add_q", _fake_linear_w8_q8_add_q, lib=_lib_def)
 _lib_def.impl("lsq_linear_w8_q8_dec_q", _requant_no_grad("lsq_linear_w8_q8_dec_q", (1, 4, 6, 7, 8)), "Autograd")
 _lib_def.impl("lsq_linear_w8_q8_dec_add_q", _requant_no_grad("lsq_linear_w8_q8_dec_add_q", (1, 4, 6, 7, 8, 16, 18, 19)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the levels-out linears on packed codes (_lindec_w4_host.py): GPU tensors -> liblsq_hip_lindec_w4.so for what it serves, the existing
+# ops composed for the rest; CPU tensors -> the same composition; a shape-only kernel each.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_packed_q8_q", lindec_w4_linear_levels)
+    _lib_key.impl("lsq_linear_packed_q8_add_q", lindec_w4_linear_levels_add)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed_q8_q", lib=_lib_def)
+def _fake_linear_packed_q8_q(x_levels, s_x, zx, codes, scale, zero_point, bias, group_size, bits, out_scale, out_shift, out_quant_min,
+                             out_quant_max, out_type_min, out_type_max, relu, mid_dtype, decode):
+    return torch.empty(x_levels.shape[:-1] + (codes.shape[0],), dtype=_fake_level_dtype(out_quant_max, out_type_max),
+                       device=x_levels.device)
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed_q8_add_q", lib=_lib_def)
+def _fake_linear_packed_q8_add_q(x_levels, s_x, zx, codes, scale, zero_point, bias, group_size, bits, out_scale, out_shift, out_quant_min,
+                                 out_quant_max, out_type_min, out_type_max, relu, mid_dtype, res_levels, res_scale, res_zero, pre_scale,
+                                 pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max, decode):
+    return torch.empty(x_levels.shape[:-1] + (codes.shape[0],), dtype=_fake_level_dtype(out_quant_max, out_type_max),
+                       device=x_levels.device)
+
+
+_lib_def.impl("lsq_linear_packed_q8_q", _requant_no_grad("lsq_linear_packed_q8_q", (1, 4, 6, 9, 10)), "Autograd")
+_lib_def.impl("lsq_linear_packed_q8_add_q", _requant_no_grad("lsq_linear_packed_q8_add_q", (1, 4, 6, 9, 10, 18, 20, 21)), "Autograd")
 
 
 # -------------------------------------------------------------------------------------------------

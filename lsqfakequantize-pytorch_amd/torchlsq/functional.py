@@ -983,6 +983,62 @@ def lsq_linear_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTen
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 
+# Whether `lsq_linear_packed_a8_q` / `lsq_linear_packed_a8_add_q` and the modules on them take liblsq_hip_lindec_w4.so when `decode`
+# is None.  The bits are the same either way; it ships True only when every case of tools/exp_lindec_w4_ab.py is faster than the
+# composition beyond the spread (profiles/r38_lindec_w4_ab.txt: all 36 cases, new / composition 0.53 to 0.72).
+W4A8_DECODE_DEFAULT = True
+
+
+def _packed_operands(packed, bias):
+    codes = packed.codes.reshape(packed.shape[0], -1) if packed.codes.dim() != 2 else packed.codes
+    groups = codes.size(0) * codes.size(1) * (8 // packed.bits) // packed.group_size
+    return (codes, packed.scale.reshape(groups), packed.zero_point.reshape(groups), bias, packed.group_size, packed.bits)
+
+
+def _packed_levels_in(what, x):
+    if isinstance(x, Tensor) and x.is_quantized:
+        x = LevelsTensor.from_quantized(x)
+    assert isinstance(x, LevelsTensor), "%s needs x as a LevelsTensor or a per-tensor quantized tensor" % what
+    return x
+
+
+def lsq_linear_packed_a8_q(x, packed: PackedGroupTensor, bias: Tensor = None, out_scale: Tensor = None, out_shift: Tensor = None,
+                           out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                           relu: bool = False, mid_dtype=torch.float32, decode: bool = None) -> LevelsTensor:
+    """`lsq_linear_packed_a8` with an 8-bit output (W4A8 / W2A8, levels from layer to layer): the levels of x on the packed 4- /
+    2-bit codes, the float-output op's fp32 value rounded to `mid_dtype`, an optional ReLU (a select) and the levels of the
+    per-tensor output quantizer -- bit for bit the composition `lsq_linear_packed_a8(..., out_dtype=mid_dtype)`, the select,
+    `lsq_levels_per_tensor` on the same device.  x is a `LevelsTensor` or a per-tensor `torch.quint8` / `torch.qint8` tensor; a
+    `LevelsTensor` is returned and nothing is read back.  `decode`: True takes ONE launch of liblsq_hip_lindec_w4.so when x has at
+    most 16 rows and the format is one of the matrix-core form (every other call composes), False always composes, None follows
+    `W4A8_DECODE_DEFAULT`; the bits are the same either way.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_linear_packed_a8_q"
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
+    x = _packed_levels_in(what, x)
+    dec = W4A8_DECODE_DEFAULT if decode is None else bool(decode)
+    lv = torch.ops.torchlsq.lsq_linear_packed_q8_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *o, mid_dtype, dec)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
+def lsq_linear_packed_a8_add_q(x, packed: PackedGroupTensor, bias: Tensor, residual: LevelsTensor, out_scale: Tensor = None,
+                               out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None,
+                               out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32, pre_scale: Tensor = None,
+                               pre_shift: Tensor = None, pre_quant_min: int = None, pre_quant_max: int = None, pre_type_min: int = None,
+                               pre_type_max: int = None, decode: bool = None) -> LevelsTensor:
+    """`lsq_linear_packed_a8_q` with `residual`, a `LevelsTensor` of the output's shape, added before the ReLU, after the layer's own
+    optional pre-quantizer: `lsq_linear_w8a8_add_q`'s steps on the packed weight's value.  `decode`: as above.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_linear_packed_a8_add_q"
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
+    r = _res_args(what, residual, pre_scale, pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max)
+    x = _packed_levels_in(what, x)
+    dec = W4A8_DECODE_DEFAULT if decode is None else bool(decode)
+    lv = torch.ops.torchlsq.lsq_linear_packed_q8_add_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *o, mid_dtype, *r,
+                                                       dec)
+    return _levels_out(lv, o[0], o[1], o[2:6])
+
+
 def lsq_conv2d_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTensor, stride=1, padding=0, dilation=1, groups: int = 1,
                           out_scale: Tensor = None, out_shift: Tensor = None, out_quant_min: int = None, out_quant_max: int = None,
                           out_type_min: int = None, out_type_max: int = None, relu: bool = False, mid_dtype=torch.float32,
