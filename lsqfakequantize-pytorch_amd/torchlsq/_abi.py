@@ -929,6 +929,33 @@ def linglu_w8_library():
                               linglu_w8_error_str)
 
 
+# The same gate and up linears on PACKED 4- / 2-bit group-wise codes: lindec_w4's order of the sum on a pair of code strips with the
+# gated product in the epilogue, one launch (include/lsq_hip_linglu_w4.h): a thirtieth companion library; the ABIs above stay as
+# they are.  Its projections carry lsq_requant_w8's output quantizer, its product lsq_glu_w8's constants.
+class LsqLingluW4Proj(ctypes.Structure):
+    """lsq_linglu_w4_proj (include/lsq_hip_linglu_w4.h): one projection's codes, per-group constants, bias and output quantizer"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("codes", "qscale", "qzero", "bias")] + [("out", _ROP), ("bias_dtype", ctypes.c_int64)]
+
+
+LINGLU_W4_ABI_VERSION = 1
+LINGLU_W4_MAX_ROWS = 16         # LSQ_LINGLU_W4_MAX_ROWS: rows of x one launch serves
+_LP4 = ctypes.POINTER(LsqLingluW4Proj)
+C_ABI_LINGLU_W4 = {
+    "lsq_linglu_w4_abi_version": (_int, []),
+    "lsq_linglu_w4_last_error": (ctypes.c_char_p, []),
+    "lsq_linglu_w4": (_int, [_int, _vp, _i64, _vp, _vp, _LP4, _LP4, _i64, _i64, _i64, _int, _vp, ctypes.POINTER(LsqGluW8Consts), _vp, _vp]),
+    "lsq_linglu_w4_plan": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _PLAN8]),
+}
+_LINGLU_W4_LIB, linglu_w4_error_str = _load_companion("liblsq_hip_linglu_w4.so", C_ABI_LINGLU_W4, "lsq_linglu_w4_abi_version",
+                                                      LINGLU_W4_ABI_VERSION)
+
+
+def linglu_w4_library():
+    """The ctypes handle of liblsq_hip_linglu_w4.so (raises if it is missing)."""
+    return _require_companion(_LINGLU_W4_LIB, "linglu_w4", "the decode-shape gate and up linears on packed codes with the gated product in "
+                              "their epilogue need", linglu_w4_error_str)
+
+
 # The qkv linear of an attention block's decode step (M <= 16) with the rotary embedding and the KV-cache append in its epilogue: one
 # launch, the rotated q levels out and k and v in a dense cache or a paged pool (include/lsq_hip_linrope_w8.h): a twenty-eighth
 # companion library; the ABIs above stay as they are.  Its projection is the linglu library's struct (the same fields), its rotation

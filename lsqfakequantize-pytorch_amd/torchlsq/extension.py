@@ -66,12 +66,13 @@ from ._lindec_w8_host import lindec_w8_linear_levels, lindec_w8_linear_levels_ad
 from ._linglu_w8_host import linglu_w8_plan, linglu_w8_q  # noqa: F401
 from ._lindec_w4_host import lindec_w4_linear_levels, lindec_w4_linear_levels_add, lindec_w4_plan  # noqa: F401
 from ._linrope_w8_host import linrope_w8_plan, linrope_w8_q  # noqa: F401
+from ._linglu_w4_host import linglu_w4_plan, linglu_w4_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_LINGLU_W8_LIB", "_LINROPE_W8_LIB", "_LINDEC_W4_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str", "linglu_w8_error_str", "linrope_w8_error_str", "lindec_w4_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_LINGLU_W8_LIB", "_LINROPE_W8_LIB", "_LINDEC_W4_LIB", "_LINGLU_W4_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str", "linglu_w8_error_str", "linrope_w8_error_str", "lindec_w4_error_str", "linglu_w4_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -358,6 +359,17 @@ _PROJ_Q = ("Tensor %s_w_levels, Tensor %s_w_scale, Tensor %s_w_zero, Tensor? %s_
 _lib_def.define("lsq_linear_w8_q8_dec_glu_q(Tensor x_levels, Tensor s_x, Tensor zx, %s, %s, Tensor up_scale, Tensor up_zero, Tensor table, "
                 "Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, int out_type_min, int out_type_max, "
                 "ScalarType mid_dtype) -> Tensor" % (_PROJ_Q % (("gate",) * 10), _PROJ_Q % (("up",) * 10)))
+#  * the same DECODE STEP on PACKED 4- / 2-bit group-wise weights: `lsq_linear_packed_q8_q` on the gate codes and on the up codes (each
+#    [C, K * bits / 8] with its per-group constants, optional bias and its own output quantizer, no ReLU, one `group_size` and one
+#    `bits`; the two row halves of a fused [2 C, K] packed weight as two views with one quantizer) and `lsq_glu_w8_q8_q` on their
+#    levels, bit for bit.  On the GPU a call whose flattened x has at most 16 rows (a format of the matrix-core form, 16-byte aligned
+#    levels and codes) is ONE launch of liblsq_hip_linglu_w4.so (include/lsq_hip_linglu_w4.h) and the [.., 2 C] bytes between the
+#    two steps never reach memory; every other call runs the ops it composes.  Inference only.
+_PROJ_P = ("Tensor %s_codes, Tensor %s_scale, Tensor %s_zero_point, Tensor? %s_bias, Tensor %s_out_scale, Tensor %s_out_shift, "
+           "int %s_quant_min, int %s_quant_max, int %s_type_min, int %s_type_max")
+_lib_def.define("lsq_linear_packed_q8_glu_q(Tensor x_levels, Tensor s_x, Tensor zx, %s, %s, int group_size, int bits, Tensor up_scale, "
+                "Tensor up_zero, Tensor table, Tensor out_scale, Tensor out_shift, int out_quant_min, int out_quant_max, "
+                "int out_type_min, int out_type_max, ScalarType mid_dtype) -> Tensor" % (_PROJ_P % (("gate",) * 10), _PROJ_P % (("upw",) * 10)))
 #  * the DECODE STEP of an attention block's first half in one op: `lsq_linear_w8_q8_dec_q` on the qkv weight [(heads + 2 kv_heads) D, K]
 #    (no ReLU), `lsq_rope_w8_q8_q` (the half style) on the q heads of its levels -> the returned [B, T, heads, D] levels, and the cache
 #    append of its k and v heads at `positions[b] + t`: into dense caches [B, kv_heads, Tmax, D] the rotation scattered and
@@ -1426,6 +1438,24 @@ def _fake_linear_w8_q8_dec_glu_q(x_levels, s_x, zx, *args):
 
 
 _lib_def.impl("lsq_linear_w8_q8_dec_glu_q", _requant_no_grad("lsq_linear_w8_q8_dec_glu_q", (1, 4, 6, 7, 8, 14, 16, 17, 18, 23, 25, 26, 27)),
+              "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the same on packed 4- / 2-bit codes (_linglu_w4_host.py): GPU tensors -> liblsq_hip_linglu_w4.so for what it serves (one call, one
+# launch), the ops it composes for the rest; CPU tensors -> the same composition.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_packed_q8_glu_q", linglu_w4_q)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed_q8_glu_q", lib=_lib_def)
+def _fake_linear_packed_q8_glu_q(x_levels, s_x, zx, *args):
+    return torch.empty(x_levels.shape[:-1] + (args[0].shape[0],), dtype=_fake_level_dtype(args[-4], args[-2]), device=x_levels.device)
+
+
+_lib_def.impl("lsq_linear_packed_q8_glu_q", _requant_no_grad("lsq_linear_packed_q8_glu_q", (1, 4, 6, 7, 8, 14, 16, 17, 18, 25, 27, 28, 29)),
               "Autograd")
 
 

@@ -1477,6 +1477,45 @@ def lsq_gated_linear_w8a8_q(x: LevelsTensor, gate_weight_q: Tensor, up_weight_q:
     return lsq_glu_w8_q(gate, up, table, *o[:6], mid_dtype)
 
 
+# Whether `lsq_gated_linear_packed_a8_q` and `GatedMLPPackedA8Q` take the one-launch op (liblsq_hip_linglu_w4.so: the gated product in
+# the epilogue of the decode-shape gate and up linears on packed codes) when `glu_epilogue` is None.  The bits are the same either
+# way; it ships True only when every case of tools/exp_linglu_w4_ab.py is faster than the two-launch route beyond the spread
+# (profiles/r39_linglu_w4_ab.txt: all 19 cases, new / parent 0.70 to 0.90).
+W4A8_GLU_EPILOGUE_DEFAULT = True
+
+
+def lsq_gated_linear_packed_a8_q(x, gate_packed: PackedGroupTensor, up_packed: PackedGroupTensor, table: Tensor, gate_out, up_out=None,
+                                 gate_bias: Tensor = None, up_bias: Tensor = None, out_scale: Tensor = None, out_shift: Tensor = None,
+                                 out_quant_min: int = None, out_quant_max: int = None, out_type_min: int = None, out_type_max: int = None,
+                                 mid_dtype=torch.float32, glu_epilogue: bool = None, decode: bool = None) -> LevelsTensor:
+    """`lsq_gated_linear_w8a8_q` on packed 4- / 2-bit group-wise weights: bit for bit
+    `lsq_glu_w8_q(lsq_linear_packed_a8_q(x, gate_packed, ...), lsq_linear_packed_a8_q(x, up_packed, ...), table, ...)`.  The two
+    `PackedGroupTensor`s have one shape [C, K], one `bits` and one `group_size`; the row halves of a fused [2 C, K] weight are
+    passed as two (views) with `up_out` None.  `gate_out` / `up_out` (None: gate's), `table` and the `out_*` arguments as there.
+    `glu_epilogue`: True takes the one op (`lsq_linear_packed_q8_glu_q`: ONE launch of liblsq_hip_linglu_w4.so when x has at most 16
+    rows and the format is one of the matrix-core form, the ops composed otherwise), False never, None follows
+    `W4A8_GLU_EPILOGUE_DEFAULT`; otherwise the two linears (with `decode`) and the product run one after the other.
+    Inference only."""
+    _assert_has_ops()
+    what = "lsq_gated_linear_packed_a8_q"
+    x = _packed_levels_in(what, x)
+    assert gate_packed.bits == up_packed.bits and gate_packed.group_size == up_packed.group_size and gate_packed.shape == up_packed.shape, \
+        "%s: gate and up must have one shape, one bits and one group_size (mixed formats: two lsq_linear_packed_a8_q and lsq_glu_w8_q)" % what
+    o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, False)
+    g = _out_args(what + " (gate_out)", *gate_out, *([None] * (6 - len(gate_out))), False)
+    u = g if up_out is None else _out_args(what + " (up_out)", *up_out, *([None] * (6 - len(up_out))), False)
+    if _takes_decode(W4A8_GLU_EPILOGUE_DEFAULT if glu_epilogue is None else glu_epilogue, x.levels):
+        s_u, z_u = _act_constants(u[0], u[1], u[4], u[5])
+        gw, uw = _packed_operands(gate_packed, gate_bias), _packed_operands(up_packed, up_bias)
+        lv = torch.ops.torchlsq.lsq_linear_packed_q8_glu_q(x.levels, x.scale, x.zero_point, *gw[:4], *g[:6], *uw[:4], *u[:6], *gw[4:], s_u, z_u,
+                                                           table, *o[:6], mid_dtype)
+        return _levels_out(lv, o[0], o[1], o[2:6])
+    kw = dict(mid_dtype=mid_dtype, decode=decode)
+    gate = lsq_linear_packed_a8_q(x, gate_packed, gate_bias, *g[:6], **kw)
+    up = lsq_linear_packed_a8_q(x, up_packed, up_bias, *u[:6], **kw)
+    return lsq_glu_w8_q(gate, up, table, *o[:6], mid_dtype)
+
+
 def _norm_rows(what, x, weight, bias, normalized_shape, dim):
     """(levels whose LAST axis is the normalised one, as a dense view where x's memory allows it; weight and bias flattened; the
     way back to x's shape and memory format)"""
