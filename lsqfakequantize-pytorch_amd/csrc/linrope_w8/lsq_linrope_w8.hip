@@ -4,8 +4,8 @@
 //
 // Nothing is defined here.  The exact integer is csrc/qlinear_w8/lsq_w8_shared.hpp's w8_exact on the raw sums, the qkv byte is
 // csrc/requant_w8/lsq_requant_w8_tiles.hpp's w8q_byte, the rotation is rope_dequant and rope_pair on two qkv bytes, its level
-// csrc/lsq_w8_out_side.hpp's w8o_byte.  rope_dequant, rope_pair and their constants are TWIN COPIES of those in
-// csrc/rope_w8/lsq_rope_w8.hip, a translation unit: a fix there belongs here too.
+// csrc/lsq_w8_out_side.hpp's w8o_byte.  The rotation's device functions, the placement of the rows, the decoding of an item and
+// the geometry's checks are csrc/linrope_w8/lsq_linrope_shared.hpp's, which csrc/linrope_w4/lsq_linrope_w4.hip compiles too.
 //
 // ONE KERNEL TEXT, linrope_w8_kernel, 1024 threads = 16 waves: csrc/linglu_w8/'s skeleton on a pair of strips of ONE weight.
 //  * ITEMS.  HF's rotate_half pairs feature i with i + R / 2: two different 16-column tiles of the qkv output.  A work item is
@@ -35,8 +35,7 @@
 // behind lsq_qdecode.hpp's opt-in.
 #include "../requant_w8/lsq_requant_w8_tiles.hpp"
 #include "../requant_w8/lsq_requant_w8_checks.hpp"
-#include "../lsq_w8_out_side.hpp"
-#include "../../../include/lsq_hip_linrope_w8.h"
+#include "lsq_linrope_shared.hpp"
 
 static_assert(LSQ_LINROPE_W8_MAX_ROWS == 16, "the rows of x are the 16 rows of one MFMA tile");
 static_assert(LSQ_ROPE_W8_U8 == LSQ_REQUANT_W8_U8 && LSQ_ROPE_W8_I8 == LSQ_REQUANT_W8_I8, "one level type code for the two steps");
@@ -50,67 +49,10 @@ constexpr int kLrRedP = kLrWaves * 256;             // int32 values of one P reg
 constexpr int kLrRedV = kLrWaves * 16;              // ... of the S region and of one C region
 constexpr int kLrRedBytes = (2 * kLrRedP + 3 * kLrRedV) * 4;    // sum a w (strip A, B), sum a, sum w (strip A, B) of every wave
 constexpr int kLrTile = kW8Tile * kW8Tile;          // one byte tile
-constexpr int kLrPlaceBytes = 16 * (4 + 4 + 3 * 8); // p, flags and three offsets of 16 rows
 constexpr int kLrFixedLds = kLrRedBytes + 4 * kLrTile + kLrPlaceBytes;
 constexpr int kLrMaxLds = kLrFixedLds + LSQ_LINROPE_W8_MAX_ROWS * (kLrChunk + kW8RowPad);
-constexpr int kLrQ = 1, kLrK = 2, kLrV = 4;         // the write flags of a row
 static_assert(kLrWaves * kW8Step == kLrChunk, "the waves' steps cover a chunk");
 static_assert(kLrFixedLds % 16 == 0, "the rows of x are read as 16-byte packets");
-
-// ---- TWIN COPIES of csrc/rope_w8/lsq_rope_w8.hip's RopeArg, RopeQ, rope_constants, rope_dequant and rope_pair ----
-struct RopeArg {            // kernel argument: the constants
-    const float* s_x;
-    const int32_t* zx;
-    const float* scale;     // the output quantizer
-    const float* shift;
-    float qmin, qmax, tmin, tmax;
-    int mid;                // LSQ_F32 / LSQ_BF16 / LSQ_F16
-};
-
-struct RopeQ : W8OutSide {  // the constants, read once per thread
-    float s_x, zx, off;     // off: 128.0f for int8 levels, what the flipped byte carries too much; 0.0f for uint8
-};
-
-__device__ __forceinline__ RopeQ rope_constants(const RopeArg& a, uint32_t flip) {
-    RopeQ q;
-    w8o_constants(q, a);
-    q.s_x = a.s_x[0];
-    q.zx = static_cast<float>(a.zx[0]);
-    q.off = flip ? 128.0f : 0.0f;
-    return q;
-}
-
-// LevelsTensor.dequantize(mid) of byte I of a packet's word `w`, flipped by 0x80 per byte for int8 levels so that it holds
-// level + off as an unsigned byte: float(level) = float(byte) - off exactly, then (float(level) - float(zero)) * scale, rounded to mid
-template <int I>
-__device__ __forceinline__ float rope_dequant(uint32_t w, const RopeQ& q) {
-    const float l = __fsub_rn(static_cast<float>((w >> (8 * I)) & 0xffu), q.off);
-    return w8o_round_mid(__fmul_rn(__fsub_rn(l, q.zx), q.s_x), q.mid);
-}
-
-// the pair of the contract: two rounded fp32 products and one rounded fp32 difference / sum, each rounded to mid; never an fma
-__device__ __forceinline__ void rope_pair(float di, float dj, float c, float s, int mid, float& ui, float& uj) {
-    const float ic = w8o_round_mid(__fmul_rn(di, c), mid), js = w8o_round_mid(__fmul_rn(dj, s), mid);
-    const float jc = w8o_round_mid(__fmul_rn(dj, c), mid), is = w8o_round_mid(__fmul_rn(di, s), mid);
-    ui = w8o_round_mid(__fsub_rn(ic, js), mid);
-    uj = w8o_round_mid(__fadd_rn(jc, is), mid);
-}
-// ---- end of the twin copies ----
-
-struct LrGeom {             // kernel argument; the host has checked that every offset fits 63 bits
-    int64_t row_s[3];       // q: batch; k, v: batch (dense) or page (paged)
-    int64_t tok_s[3];       // q: token; k, v: token (dense) or slot (paged)
-    int64_t head_s[3];
-    int T, H, Hkv, D, R, P;
-    int limit;              // tokens a sequence can hold: Tmax (dense) or Mp ps (paged)
-    int paged, Np, ps, bt_ld;
-    int items;
-    uint32_t flip;          // 0x80 for int8 qkv levels (biased by 128 before rope_dequant), 0 for uint8
-};
-
-struct LrDst {              // kernel argument: rq, k, v
-    uint8_t* p[3];
-};
 
 __global__ __launch_bounds__(kLrBlock) void linrope_w8_kernel(W8Act act, int M, W8Weight wt, W8OutArg qkv_out, int64_t K, int row_stride,
                                                              LrGeom g, RopeArg ra, const float* __restrict__ cos_t,
@@ -121,9 +63,10 @@ __global__ __launch_bounds__(kLrBlock) void linrope_w8_kernel(W8Act act, int M, 
     int32_t* redS = redP + 2 * kLrRedP;                     // [wave][row]
     int32_t* redC = redS + kLrRedV;                         // [strip A, B][wave][column]
     unsigned char* tiles = smem + kLrRedBytes;              // [qkv A, qkv B, out A, out B][16][16]
-    int64_t* pl_off = reinterpret_cast<int64_t*>(tiles + 4 * kLrTile);     // [q, k, v][row]
-    int32_t* pl_p = reinterpret_cast<int32_t*>(pl_off + 3 * 16);           // [row]
-    int32_t* pl_flags = pl_p + 16;                                         // [row]
+    const LrPlace place = lr_place_at(tiles + 4 * kLrTile);
+    int64_t* pl_off = place.off;
+    int32_t* pl_p = place.p;
+    int32_t* pl_flags = place.flags;
     unsigned char* xs = smem + kLrFixedLds;
 
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
@@ -134,54 +77,16 @@ __global__ __launch_bounds__(kLrBlock) void linrope_w8_kernel(W8Act act, int M, 
     const int64_t n_chunks = (K + kLrChunk - 1) / kLrChunk;
     const int first_item = static_cast<int>(blockIdx.x);
     const i32x4 ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
-    const int ipd = g.D / 32, ur = g.R / 32;                // items of a head, and those of them that rotate
 
     // where the rows go, once per workgroup
-    if (tid < 16) {
-        int flags = 0, p = 0;
-        int64_t oq = 0, ok = 0, ov = 0;
-        if (tid < M) {
-            const int b = tid / g.T, t = tid - b * g.T;
-            const int64_t pp = (pos ? static_cast<int64_t>(pos[b]) : 0) + t;
-            const bool in_tables = pp >= 0 && pp < g.P;
-            if (in_tables) {
-                flags |= kLrQ;
-                p = static_cast<int>(pp);
-                oq = b * g.row_s[0] + t * g.tok_s[0];
-            }
-            if (pp >= 0 && pp < g.limit) {
-                int64_t outer = b, tok = pp;
-                bool there = true;
-                if (g.paged) {
-                    const int e = bt[static_cast<int64_t>(b) * g.bt_ld + pp / g.ps];
-                    there = e >= 0 && e < g.Np;             // a wrong entry must not land in another sequence's page
-                    outer = e;
-                    tok = pp % g.ps;
-                }
-                if (there) {
-                    flags |= kLrV | (in_tables ? kLrK : 0);
-                    ok = outer * g.row_s[1] + tok * g.tok_s[1];
-                    ov = outer * g.row_s[2] + tok * g.tok_s[2];
-                }
-            }
-        }
-        pl_off[tid] = oq;
-        pl_off[16 + tid] = ok;
-        pl_off[32 + tid] = ov;
-        pl_p[tid] = p;
-        pl_flags[tid] = flags;
-    }
+    if (tid < 16) lr_place_row(g, M, pos, bt, place, tid);
     __syncthreads();                                        // placement written
 
     for (int item = first_item; item < g.items; item += static_cast<int>(gridDim.x)) {
-        const int head = item / ipd, u = item - head * ipd;
-        const int kind = head < g.H ? 0 : (head < g.H + g.Hkv ? 1 : 2);    // q, k, v
-        const int hh = head - (kind == 0 ? 0 : (kind == 1 ? g.H : g.H + g.Hkv));
-        const bool rot = kind < 2 && u < ur;
-        const int fA = rot ? 16 * u : 32 * u;               // (R = 32 ur: the strips beyond R start at 32 u too)
-        const int fB = rot ? fA + g.R / 2 : fA + 16;
-        const int bit = 1 << kind;
-        const int64_t nA = static_cast<int64_t>(head) * g.D + fA, nB = static_cast<int64_t>(head) * g.D + fB;
+        const LrItem it = lr_item(g, item);
+        const int kind = it.kind, hh = it.hh, fA = it.fA, fB = it.fB, bit = it.bit;
+        const bool rot = it.rot;
+        const int64_t nA = it.nA, nB = it.nB;
         const uint8_t* __restrict__ arow = wt.w + (nA + nl) * K;
         const uint8_t* __restrict__ brow = wt.w + (nB + nl) * K;
 
@@ -300,11 +205,7 @@ struct LrPlan {
 inline LrPlan plan_linrope(const lsq_linrope_w8_geom& ge, int64_t K, bool aligned) {
     LrPlan pl = {};
     const int64_t M = ge.B * ge.T;
-    const bool strides = ge.q_sb % 16 == 0 && ge.q_st % 16 == 0 && ge.q_sh % 16 == 0 && ge.k_so % 16 == 0 && ge.k_st % 16 == 0 &&
-                         ge.k_sh % 16 == 0 && ge.v_so % 16 == 0 && ge.v_st % 16 == 0 && ge.v_sh % 16 == 0;
-    if (!(aligned && strides && M >= 1 && M <= LSQ_LINROPE_W8_MAX_ROWS && K > 0 && K % 16 == 0 && K <= kW8MaxK &&
-          ge.style == LSQ_ROPE_W8_HALF && ge.D % 32 == 0 && ge.R % 32 == 0 && ge.R >= 32))
-        return pl;
+    if (!(aligned && lr_geom_served(ge) && K > 0 && K % 16 == 0 && K <= kW8MaxK)) return pl;
     const int64_t cus = device_info().cu_count;
     pl.served = 1;
     pl.block = kLrBlock;
@@ -312,9 +213,7 @@ inline LrPlan plan_linrope(const lsq_linrope_w8_geom& ge, int64_t K, bool aligne
     pl.x_resident = pl.chunks == 1 ? 1 : 0;
     pl.row_stride = static_cast<int>(std::min<int64_t>((K + kW8Step - 1) / kW8Step * kW8Step, kLrChunk)) + kW8RowPad;
     pl.lds = kLrFixedLds + static_cast<int>(M) * pl.row_stride;
-    pl.rotate = static_cast<int>((ge.H + ge.Hkv) * (ge.R / 32));
-    pl.pass = static_cast<int>((ge.H + ge.Hkv) * ((ge.D - ge.R) / 32));
-    pl.copy = static_cast<int>(ge.Hkv * (ge.D / 32));
+    lr_item_counts(ge, pl.rotate, pl.pass, pl.copy);
     pl.grid = std::min<int64_t>(pl.rotate + pl.pass + pl.copy, cus);
     return pl;
 }
@@ -336,100 +235,13 @@ static hipError_t linrope_launch(const LrPlan& pl, const W8Act& act, int M, cons
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int64_t kMaxExtent = INT32_MAX / 4;       // 29 bits, as lsq_hip_rope_w8.h
-constexpr int64_t kMaxOffset = int64_t{1} << 58;
-
-// the (outer, token, head) rows of a destination must not overlap each other: rope_self_overlap of csrc/rope_w8/lsq_rope_w8.hip
-bool rows_overlap(const int64_t (&strides)[3], const int64_t (&extents)[3], int64_t cols) {
-    int64_t st[3] = {strides[0], strides[1], strides[2]}, ex[3] = {extents[0], extents[1], extents[2]};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (st[j] < st[i]) {
-                std::swap(st[i], st[j]);
-                std::swap(ex[i], ex[j]);
-            }
-    int64_t span = cols;
-    for (int i = 0; i < 3; ++i) {
-        if (ex[i] == 1) continue;
-        if (st[i] < span) return true;
-        span += (ex[i] - 1) * st[i];
-    }
-    return false;
-}
-
-struct Dest {               // one destination: its name, strides and extents (outer, token, head) and its bytes
-    const char* name;
-    int64_t st[3], ex[3], bytes;
-};
-
-// the geometry's checks, host only (the plan makes them too); fills the three destinations
-int check_geom(const char* what, const lsq_linrope_w8_geom* g, Dest (&d)[3]) {
-    if (!g) return fail(LSQ_EINVAL, "%s: NULL geometry", what);
-    if (g->B < 1 || g->T < 1 || g->H < 1 || g->Hkv < 1 || g->D < 1)
-        return fail(LSQ_EINVAL, "%s: B = %lld, T = %lld, H = %lld, Hkv = %lld, D = %lld: every extent must be at least 1", what,
-                    static_cast<ll>(g->B), static_cast<ll>(g->T), static_cast<ll>(g->H), static_cast<ll>(g->Hkv), static_cast<ll>(g->D));
-    if (g->B > kMaxExtent || g->T > kMaxExtent || g->H > kMaxExtent || g->Hkv > kMaxExtent || g->D > kMaxExtent ||
-        (g->H + 2 * g->Hkv) * g->D > kMaxExtent)
-        return fail(LSQ_EINVAL, "%s: an extent is beyond 29 bits", what);
-    if (g->style != LSQ_ROPE_W8_HALF && g->style != LSQ_ROPE_W8_INTERLEAVED)
-        return fail(LSQ_EINVAL, "%s: style must be LSQ_ROPE_W8_HALF (0) or LSQ_ROPE_W8_INTERLEAVED (1), got %lld", what, static_cast<ll>(g->style));
-    if (g->P < 1) return fail(LSQ_EINVAL, "%s: the tables hold P = %lld positions, at least 1 is needed", what, static_cast<ll>(g->P));
-    if (g->P > kMaxExtent) return fail(LSQ_EINVAL, "%s: P = %lld is beyond 29 bits", what, static_cast<ll>(g->P));
-    if (g->R < 2 || g->R % 2 != 0 || g->R > g->D)
-        return fail(LSQ_EINVAL, "%s: the rotary dimension R = %lld must be even, at least 2 and at most D = %lld", what, static_cast<ll>(g->R),
-                    static_cast<ll>(g->D));
-    if (g->paged != 0 && g->paged != 1) return fail(LSQ_EINVAL, "%s: paged must be 0 or 1, got %lld", what, static_cast<ll>(g->paged));
-    int64_t outer = g->B, toks = g->Tmax;
-    if (g->paged) {
-        const lsq_attn_paged_w8_pages& pg = g->pages;
-        if (pg.Np < 1 || pg.ps < 1 || pg.Mp < 1)
-            return fail(LSQ_EINVAL, "%s: Np = %lld pages of ps = %lld slots and Mp = %lld table entries: every extent must be at least 1", what,
-                        static_cast<ll>(pg.Np), static_cast<ll>(pg.ps), static_cast<ll>(pg.Mp));
-        if (pg.Np > kMaxExtent || pg.ps > kMaxExtent || pg.Mp > kMaxExtent || pg.Mp > kMaxExtent / pg.ps)
-            return fail(LSQ_EINVAL, "%s: Np, or the Mp ps = %lld x %lld tokens of a sequence, are beyond 29 bits", what, static_cast<ll>(pg.Mp),
-                        static_cast<ll>(pg.ps));
-        if (pg.bt_ld < pg.Mp || pg.bt_ld > kMaxExtent)
-            return fail(LSQ_EINVAL, "%s: the block table's rows are bt_ld = %lld apart, at least Mp = %lld (and at most 2^29) is needed", what,
-                        static_cast<ll>(pg.bt_ld), static_cast<ll>(pg.Mp));
-        outer = pg.Np;
-        toks = pg.ps;
-    } else if (g->Tmax < 1 || g->Tmax > kMaxExtent) {
-        return fail(LSQ_EINVAL, "%s: the caches hold Tmax = %lld tokens, 1 to 2^29 are served", what, static_cast<ll>(g->Tmax));
-    }
-    d[0] = Dest{"rq", {g->q_sb, g->q_st, g->q_sh}, {g->B, g->T, g->H}, 0};
-    d[1] = Dest{"k", {g->k_so, g->k_st, g->k_sh}, {outer, toks, g->Hkv}, 0};
-    d[2] = Dest{"v", {g->v_so, g->v_st, g->v_sh}, {outer, toks, g->Hkv}, 0};
-    for (Dest& t : d) {
-        t.bytes = g->D;
-        for (int i = 0; i < 3; ++i) {
-            if (t.st[i] < 0 || t.st[i] > kMaxOffset / t.ex[i])
-                return fail(LSQ_EINVAL, "%s: the strides (%lld, %lld, %lld) of %s must not be negative and must keep every offset within 2^58",
-                            what, static_cast<ll>(t.st[0]), static_cast<ll>(t.st[1]), static_cast<ll>(t.st[2]), t.name);
-            t.bytes += (t.ex[i] - 1) * t.st[i];
-        }
-        if (rows_overlap(t.st, t.ex, g->D))
-            return fail(LSQ_EINVAL, "%s: under %s's strides (%lld, %lld, %lld) two rows of D = %lld bytes overlap", what, t.name,
-                        static_cast<ll>(t.st[0]), static_cast<ll>(t.st[1]), static_cast<ll>(t.st[2]), static_cast<ll>(g->D));
-    }
-    return LSQ_OK;
-}
-
 // what this library serves; everything else that is legal belongs to lsq_hip_lindec_w8.h, lsq_hip_rope_w8.h and lsq_hip_attn_paged_w8.h
 int check_served(const char* what, const lsq_linrope_w8_geom& g, int64_t K, bool aligned, const Dest (&d)[3]) {
     const char* other = "the composition of lsq_hip_lindec_w8.h, lsq_hip_rope_w8.h and lsq_hip_attn_paged_w8.h serves it";
-    if (g.B * g.T > LSQ_LINROPE_W8_MAX_ROWS)
-        return fail(LSQ_EINVAL, "%s: B T = %lld rows of x, the kernel serves 1 to %d (%s)", what, static_cast<ll>(g.B * g.T),
-                    LSQ_LINROPE_W8_MAX_ROWS, other);
+    if (int rc = check_rows_served(what, g, other)) return rc;
     if (K <= 0 || K % 16 != 0 || K > lsq::kW8MaxK)
         return fail(LSQ_EINVAL, "%s: K = %lld, the kernel serves multiples of 16 up to %d (%s)", what, static_cast<ll>(K), lsq::kW8MaxK, other);
-    if (g.style != LSQ_ROPE_W8_HALF) return fail(LSQ_EINVAL, "%s: the interleaved pairing is not served (%s)", what, other);
-    if (g.D % 32 != 0 || g.R % 32 != 0)
-        return fail(LSQ_EINVAL, "%s: D = %lld and R = %lld, the kernel serves multiples of 32 (%s)", what, static_cast<ll>(g.D),
-                    static_cast<ll>(g.R), other);
-    for (const Dest& t : d)
-        if (t.st[0] % 16 || t.st[1] % 16 || t.st[2] % 16)
-            return fail(LSQ_EINVAL, "%s: the strides (%lld, %lld, %lld) of %s must be multiples of 16 bytes (%s)", what, static_cast<ll>(t.st[0]),
-                        static_cast<ll>(t.st[1]), static_cast<ll>(t.st[2]), t.name, other);
+    if (int rc = check_geom_served(what, g, d, other)) return rc;
     if (!aligned)
         return fail(LSQ_EINVAL, "%s: x_levels, w_levels, cos, sin, rq, k and v must be 16-byte aligned (%s)", what, other);
     return LSQ_OK;
@@ -467,36 +279,10 @@ int lsq_linrope_w8(int level_dtype, const void* x_levels, const void* s_x, const
         return rc;
     // the rotation's sides and tables, said as csrc/rope_w8/ says them
     lsq::RopeArg ra{};
-    int64_t y_elem = 1;
-    if (!qkv || !qkv->s_x || !qkv->zx) return fail(LSQ_EINVAL, "%s: NULL input side of the rotation, s_x or zx", what);
-    if (!rot) return fail(LSQ_EINVAL, "%s: NULL output description of the rotation", what);
-    if (!cos || !sin) return fail(LSQ_EINVAL, "%s: NULL cos or sin", what);
-    if (!aligned_to(qkv->s_x, 4) || !aligned_to(qkv->zx, 4)) return fail(LSQ_EINVAL, "%s: the rotation's s_x and zx must be element-aligned", what);
-    if (!aligned_to(cos, 4) || !aligned_to(sin, 4)) return fail(LSQ_EINVAL, "%s: cos and sin must be element-aligned", what);
-    if (int rc = check_out_side(what, *rot, ra, y_elem)) return rc;
-    if (!rot->out_scale) return fail(LSQ_EINVAL, "%s: NULL out_scale and out_shift: a floating rq is not served (lsq_hip_rope_w8.h)", what);
-    if (rot->mid_dtype != mid) return fail(LSQ_EINVAL, "%s: the projection and the rotation must have one mid_dtype", what);
-    ra.s_x = static_cast<const float*>(qkv->s_x);
-    ra.zx = static_cast<const int32_t*>(qkv->zx);
-    if (positions && !aligned_to(positions, 4)) return fail(LSQ_EINVAL, "%s: positions must be 4-byte aligned", what);
-    if (geom->paged && (!block_table || !aligned_to(block_table, 4)))
-        return fail(LSQ_EINVAL, "%s: a paged call needs a block table, 4-byte aligned", what);
+    if (int rc = check_rotation(what, geom, mid, qkv, rot, cos, sin, positions, block_table, ra)) return rc;
     // the destinations against everything that is read, and against each other
     void* const dp[3] = {rq, k, v};
-    const int64_t t_bytes = geom->P * (geom->R / 2) * 4;
-    const int64_t bt_bytes = geom->paged ? ((geom->B - 1) * geom->pages.bt_ld + geom->pages.Mp) * 4 : 0;
-    struct In { const char* name; const void* p; int64_t bytes; };
-    const In ins[] = {{"x", x_levels, M * K}, {"the weight", proj->w_levels, N * K}, {"cos", cos, t_bytes}, {"sin", sin, t_bytes},
-                      {"positions", positions, 4 * geom->B}, {"the block table", block_table, bt_bytes}};
-    for (int i = 0; i < 3; ++i) {
-        for (const In& in : ins)
-            if (in.p && in.bytes && overlap(dp[i], d[i].bytes, in.p, in.bytes))
-                return fail(LSQ_EINVAL, "%s: %s's %lld bytes overlap %s", what, d[i].name, static_cast<ll>(d[i].bytes), in.name);
-        for (int j = i + 1; j < 3; ++j)
-            if (overlap(dp[i], d[i].bytes, dp[j], d[j].bytes))
-                return fail(LSQ_EINVAL, "%s: %s's %lld bytes overlap %s's %lld", what, d[i].name, static_cast<ll>(d[i].bytes), d[j].name,
-                            static_cast<ll>(d[j].bytes));
-    }
+    if (int rc = check_dest_overlap(what, geom, d, dp, x_levels, M * K, proj->w_levels, N * K, cos, sin, positions, block_table)) return rc;
     const bool aligned = aligned_to(x_levels, 16) && aligned_to(proj->w_levels, 16) && aligned_to(cos, 16) && aligned_to(sin, 16) &&
                          aligned_to(rq, 16) && aligned_to(k, 16) && aligned_to(v, 16);
     if (int rc = check_served(what, *geom, K, aligned, d)) return rc;
@@ -505,26 +291,7 @@ int lsq_linrope_w8(int level_dtype, const void* x_levels, const void* s_x, const
                                         static_cast<int>(proj->bias_dtype));
     const lsq::W8Act act = levels_act(level_dtype, x_levels, s_x, zx);
     const bool qkv_signed = std::max(proj->out->quant_max, proj->out->type_max) <= 127;
-    const int64_t limit = geom->paged ? geom->pages.Mp * geom->pages.ps : geom->Tmax;
-    lsq::LrGeom g{};
-    for (int i = 0; i < 3; ++i) {
-        g.row_s[i] = d[i].st[0];
-        g.tok_s[i] = d[i].st[1];
-        g.head_s[i] = d[i].st[2];
-    }
-    g.T = static_cast<int>(geom->T);
-    g.H = static_cast<int>(geom->H);
-    g.Hkv = static_cast<int>(geom->Hkv);
-    g.D = static_cast<int>(geom->D);
-    g.R = static_cast<int>(geom->R);
-    g.P = static_cast<int>(geom->P);
-    g.limit = static_cast<int>(limit);
-    g.paged = static_cast<int>(geom->paged);
-    g.Np = geom->paged ? static_cast<int>(geom->pages.Np) : 0;
-    g.ps = geom->paged ? static_cast<int>(geom->pages.ps) : 1;
-    g.bt_ld = geom->paged ? static_cast<int>(geom->pages.bt_ld) : 0;
-    g.items = pl.rotate + pl.pass + pl.copy;
-    g.flip = qkv_signed ? 0x80u : 0u;
+    const lsq::LrGeom g = kernel_geom(geom, d, pl.rotate + pl.pass + pl.copy, qkv_signed);
     const lsq::LrDst dst{{static_cast<uint8_t*>(rq), static_cast<uint8_t*>(k), static_cast<uint8_t*>(v)}};
     return hip_status(lsq::linrope_launch(pl, act, static_cast<int>(M), wt, qo, K, g, ra, static_cast<const float*>(cos),
                                           static_cast<const float*>(sin), static_cast<const int32_t*>(positions),

@@ -13,7 +13,7 @@
 //  * GENERIC (every other legal call): one lane per pair, per feature beyond R, or per byte in COPY.  Correct, not tuned.
 //
 // rope_dequant is elt_dequant of ../eltwise_w8/lsq_eltwise_w8.hip and rope_self_overlap is self_overlap of
-// ../attn_w8/lsq_attn_w8_checks.hpp, copied: this file must not depend on those libraries' sources.  RopeArg, RopeQ, rope_constants, rope_dequant and rope_pair have TWIN COPIES in ../linrope_w8/lsq_linrope_w8.hip: a fix here belongs there too.
+// ../attn_w8/lsq_attn_w8_checks.hpp, copied: this file must not depend on those libraries' sources.  RopeArg, RopeQ, rope_constants, rope_dequant and rope_pair have TWIN COPIES in ../linrope_w8/lsq_linrope_shared.hpp (which ../linrope_w8/ and ../linrope_w4/ compile): a fix here belongs there too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -987,6 +987,28 @@ def linrope_w8_library():
                               "in its epilogue needs", linrope_w8_error_str)
 
 
+# The same qkv linear on PACKED 4- / 2-bit group-wise codes: lindec_w4's order of the sum on linrope_w8's items, one launch
+# (include/lsq_hip_linrope_w4.h): a thirty-first companion library; the ABIs above stay as they are.  Its projection is the
+# linglu_w4 library's struct, its geometry the linrope_w8 library's.
+LINROPE_W4_ABI_VERSION = 1
+LINROPE_W4_MAX_ROWS = 16        # LSQ_LINROPE_W4_MAX_ROWS: rows of x one launch serves
+C_ABI_LINROPE_W4 = {
+    "lsq_linrope_w4_abi_version": (_int, []),
+    "lsq_linrope_w4_last_error": (ctypes.c_char_p, []),
+    "lsq_linrope_w4": (_int, [_int, _vp, _vp, _vp, _LP4, _i64, _i64, _i64, _int, _LRG, ctypes.POINTER(LsqRopeW8In),
+                              ctypes.POINTER(LsqRopeW8Out), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsq_linrope_w4_plan": (_int, [_LRG, _i64, _i64, _int, _int, _PLAN9]),
+}
+_LINROPE_W4_LIB, linrope_w4_error_str = _load_companion("liblsq_hip_linrope_w4.so", C_ABI_LINROPE_W4, "lsq_linrope_w4_abi_version",
+                                                        LINROPE_W4_ABI_VERSION)
+
+
+def linrope_w4_library():
+    """The ctypes handle of liblsq_hip_linrope_w4.so (raises if it is missing)."""
+    return _require_companion(_LINROPE_W4_LIB, "linrope_w4", "the decode-shape qkv linear on packed codes with the rotary embedding and the "
+                              "KV-cache append in its epilogue needs", linrope_w4_error_str)
+
+
 # The optional second host layer: torchlsq/_lsq_torch.so, the C++ torch binding of the same C ABI
 # (csrc/torch_binding/lsq_torch_binding.cpp, namespace `torchlsq_native`).  It adds no device code; it only
 # moves the per-call tensor bookkeeping and the autograd node from Python to C++.  `functional.lsq` prefers it

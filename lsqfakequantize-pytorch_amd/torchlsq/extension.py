@@ -67,12 +67,13 @@ from ._linglu_w8_host import linglu_w8_plan, linglu_w8_q  # noqa: F401
 from ._lindec_w4_host import lindec_w4_linear_levels, lindec_w4_linear_levels_add, lindec_w4_plan  # noqa: F401
 from ._linrope_w8_host import linrope_w8_plan, linrope_w8_q  # noqa: F401
 from ._linglu_w4_host import linglu_w4_plan, linglu_w4_q  # noqa: F401
+from ._linrope_w4_host import linrope_w4_plan, linrope_w4_q  # noqa: F401
 
 
 def __getattr__(name):
     # loader state lives in _abi (it changes at run time: set_host_binding, set_library); read it through this module too
-    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_LINGLU_W8_LIB", "_LINROPE_W8_LIB", "_LINDEC_W4_LIB", "_LINGLU_W4_LIB", "_NATIVE_LSQ", "error_str",
-                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str", "linglu_w8_error_str", "linrope_w8_error_str", "lindec_w4_error_str", "linglu_w4_error_str",
+    if name in ("_LIB", "_HAS_OPS", "_CPU_LIB", "_GROUP_LIB", "_PACK_LIB", "_QLINEAR_LIB", "_QLINEAR_A8_LIB", "_QGEMM_LIB", "_QGEMM_A8_LIB", "_QLINEAR_W8_LIB", "_QCONV_W8_LIB", "_REQUANT_W8_LIB", "_RESADD_W8_LIB", "_POOL_W8_LIB", "_DWCONV_W8_LIB", "_ELTWISE_W8_LIB", "_NORM_W8_LIB", "_ATTN_W8_LIB", "_ATTN_FUSED_W8_LIB", "_ATTN_MASK_W8_LIB", "_ROPE_W8_LIB", "_ATTN_DECODE_W8_LIB", "_ATTN_PREFILL_W8_LIB", "_ATTN_DECODE_SPLIT_W8_LIB", "_ATTN_PAGED_W8_LIB", "_ATTN_CHUNK_W8_LIB", "_GLU_W8_LIB", "_LINDEC_W8_LIB", "_LINGLU_W8_LIB", "_LINROPE_W8_LIB", "_LINDEC_W4_LIB", "_LINGLU_W4_LIB", "_LINROPE_W4_LIB", "_NATIVE_LSQ", "error_str",
+                "cpu_error_str", "group_error_str", "pack_error_str", "qlinear_error_str", "qlinear_a8_error_str", "qgemm_error_str", "qgemm_a8_error_str", "qlinear_w8_error_str", "qconv_w8_error_str", "requant_w8_error_str", "resadd_w8_error_str", "pool_w8_error_str", "dwconv_w8_error_str", "eltwise_w8_error_str", "norm_w8_error_str", "attn_w8_error_str", "attn_fused_w8_error_str", "attn_mask_w8_error_str", "rope_w8_error_str", "attn_decode_w8_error_str", "attn_prefill_w8_error_str", "attn_decode_split_w8_error_str", "attn_paged_w8_error_str", "attn_chunk_w8_error_str", "glu_w8_error_str", "lindec_w8_error_str", "linglu_w8_error_str", "linrope_w8_error_str", "lindec_w4_error_str", "linglu_w4_error_str", "linrope_w4_error_str",
                 "native_error_str"):
         return getattr(_abi, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -383,6 +384,16 @@ _lib_def.define("lsq_linear_w8_q8_dec_rope_q(Tensor x_levels, Tensor s_x, Tensor
                 "Tensor qkv_scale, Tensor qkv_zero, Tensor cos, Tensor sin, Tensor rot_scale, Tensor rot_shift, int rot_quant_min, int rot_quant_max, int rot_type_min, "
                 "int rot_type_max, ScalarType mid_dtype, int heads, int kv_heads, Tensor(a!) k_cache, Tensor(b!) v_cache, "
                 "Tensor? positions=None, Tensor? block_table=None) -> Tensor")
+#  * the same DECODE STEP on PACKED 4- / 2-bit group-wise weights: `lsq_linear_packed_q8_q` on the qkv codes [(heads + 2 kv_heads) D,
+#    K * bits / 8] (no ReLU), then the rotation and the cache append exactly as above -- bit for bit.  On the GPU a call that
+#    liblsq_hip_linrope_w4.so's plan serves (B T <= 16, a format of the matrix-core form, D % 32 == 0, R % 32 == 0, 16-byte aligned
+#    buffers and strides) is ONE launch (include/lsq_hip_linrope_w4.h) and the qkv bytes never reach memory; every other call runs
+#    the ops it composes.  `positions` is read, never advanced.  Inference only.
+_lib_def.define("lsq_linear_packed_q8_rope_q(Tensor x_levels, Tensor s_x, Tensor zx, %s, Tensor out_scale, Tensor out_shift, "
+                "int out_quant_min, int out_quant_max, int out_type_min, int out_type_max, Tensor qkv_scale, Tensor qkv_zero, Tensor cos, "
+                "Tensor sin, Tensor rot_scale, Tensor rot_shift, int rot_quant_min, int rot_quant_max, int rot_type_min, int rot_type_max, "
+                "ScalarType mid_dtype, int heads, int kv_heads, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? positions=None, "
+                "Tensor? block_table=None) -> Tensor" % _PACKED_W)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1477,3 +1488,22 @@ def _fake_linear_w8_q8_dec_rope_q(x_levels, s_x, zx, w_levels, *args):
 
 
 _lib_def.impl("lsq_linear_w8_q8_dec_rope_q", _requant_no_grad("lsq_linear_w8_q8_dec_rope_q", (1, 4, 6, 7, 8, 13, 15, 16, 17, 18)), "Autograd")
+
+
+# -------------------------------------------------------------------------------------------------
+# the same on packed 4- / 2-bit codes (_linrope_w4_host.py): GPU tensors -> liblsq_hip_linrope_w4.so for what it serves (one call, one
+# launch), the ops it composes for the rest; CPU tensors -> the same composition.  Inference only.
+# -------------------------------------------------------------------------------------------------
+for _lib_key in (_lib_hip, _lib_cpu):
+    _lib_key.impl("lsq_linear_packed_q8_rope_q", linrope_w4_q)
+del _lib_key
+
+
+@torch.library.register_fake("torchlsq::lsq_linear_packed_q8_rope_q", lib=_lib_def)
+def _fake_linear_packed_q8_rope_q(x_levels, s_x, zx, codes, *args):
+    heads, kv_heads = args[22], args[23]
+    return torch.empty(tuple(x_levels.shape[:2]) + (heads, codes.shape[0] // (heads + 2 * kv_heads)),
+                       dtype=_fake_level_dtype(args[18], args[20]), device=x_levels.device)
+
+
+_lib_def.impl("lsq_linear_packed_q8_rope_q", _requant_no_grad("lsq_linear_packed_q8_rope_q", (1, 4, 6, 9, 10, 15, 17, 18, 19, 20)), "Autograd")

@@ -2138,3 +2138,48 @@ def lsq_qkv_rope_append_w8a8_q(x: LevelsTensor, weight_q: Tensor, cos: Tensor, s
         return rq, LevelsTensor(k_cache, kl.scale, kl.zero_point, *r[2:6]), LevelsTensor(v_cache, vl.scale, vl.zero_point, *g[2:6])
     kl, vl = lsq_kv_append_paged_w8(lsq_rope_w8_q(k, cos, sin, *r[:6], mid_dtype, positions), v, k_cache, v_cache, block_table, positions)
     return rq, kl, vl
+
+
+# Whether `lsq_qkv_rope_append_packed_a8_q` and `QKVRotaryPackedA8Q` take the one-launch op (liblsq_hip_linrope_w4.so: the rotary
+# embedding and the KV-cache append in the epilogue of the decode-shape qkv linear on packed codes) when `rope_epilogue` is None.  The
+# bits are the same either way; it ships True only when every case of tools/exp_linrope_w4_ab.py is faster than the four-launch
+# route beyond the spread (profiles/r40_linrope_w4_ab.txt: all 36 cases, new / parent 0.52 to 0.84).
+W4A8_ROPE_EPILOGUE_DEFAULT = True
+
+
+def lsq_qkv_rope_append_packed_a8_q(x, packed: PackedGroupTensor, cos: Tensor, sin: Tensor, qkv_out, rot_out, heads: int, kv_heads: int,
+                                    k_cache: Tensor, v_cache: Tensor, positions: Tensor = None, block_table: Tensor = None,
+                                    bias: Tensor = None, mid_dtype=torch.float32, rope_epilogue: bool = None, decode: bool = None):
+    """`lsq_qkv_rope_append_w8a8_q` on a packed 4- / 2-bit group-wise qkv weight [(heads + 2 kv_heads) D, K]: bit for bit
+    `lsq_linear_packed_a8_q`, `lsq_rope_w8_q` on the q view, and for k and v `lsq_rope_w8_q(..., out=cache, scatter=True)` +
+    `lsq_kv_append_w8`, or `lsq_rope_w8_q` + `lsq_kv_append_paged_w8`.  `qkv_out`, `rot_out`, the caches, `positions` and
+    `block_table` as there.
+    `rope_epilogue`: True takes the one op (`lsq_linear_packed_q8_rope_q`: ONE launch of liblsq_hip_linrope_w4.so when x has at most
+    16 rows and the format is one of the matrix-core form, the ops composed otherwise), False never, None follows
+    `W4A8_ROPE_EPILOGUE_DEFAULT`; otherwise the ops above run one after the other (the linear with `decode`).
+    Returns `(rq, k_levels, v_levels)`: the rotated q [B, T, heads, D] and the caches as `LevelsTensor`s.  Inference only."""
+    _assert_has_ops()
+    what = "lsq_qkv_rope_append_packed_a8_q"
+    x = _packed_levels_in(what, x)
+    assert x.levels.dim() == 3, "%s needs levels of [B, T, K], got %s" % (what, tuple(x.shape))
+    g = _out_args(what + " (qkv_out)", *qkv_out, *([None] * (6 - len(qkv_out))), False)
+    r = _out_args(what + " (rot_out)", *rot_out, *([None] * (6 - len(rot_out))), False)
+    k_cache, v_cache = (c.levels if isinstance(c, LevelsTensor) else c for c in (k_cache, v_cache))
+    H, Hkv = int(heads), int(kv_heads)
+    if _takes_decode(W4A8_ROPE_EPILOGUE_DEFAULT if rope_epilogue is None else rope_epilogue, x.levels):
+        s_q, z_q = _act_constants(g[0], g[1], g[4], g[5])
+        rq = torch.ops.torchlsq.lsq_linear_packed_q8_rope_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *g[:6], s_q, z_q,
+                                                            cos, sin, *r[:6], mid_dtype, H, Hkv, k_cache, v_cache, positions, block_table)
+        rq = _levels_out(rq, r[0], r[1], r[2:6])
+        return rq, LevelsTensor(k_cache, rq.scale, rq.zero_point, *r[2:6]), LevelsTensor(v_cache, s_q, z_q, *g[2:6])
+    qkv = lsq_linear_packed_a8_q(x, packed, bias, *g[:6], mid_dtype=mid_dtype, decode=decode)
+    B, T = int(x.shape[0]), int(x.shape[1])
+    lv = qkv.levels.view(B, T, H + 2 * Hkv, -1)
+    q, k, v = (LevelsTensor(lv[:, :, a:b], qkv.scale, qkv.zero_point, *g[2:6]) for a, b in ((0, H), (H, H + Hkv), (H + Hkv, H + 2 * Hkv)))
+    rq = lsq_rope_w8_q(q, cos, sin, *r[:6], mid_dtype, positions)
+    if block_table is None:
+        kl = lsq_rope_w8_q(k, cos, sin, *r[:6], mid_dtype, positions, out=k_cache.permute(0, 2, 1, 3), scatter=True)
+        vl = lsq_kv_append_w8(v, v_cache.permute(0, 2, 1, 3), positions, scatter=True)
+        return rq, LevelsTensor(k_cache, kl.scale, kl.zero_point, *r[2:6]), LevelsTensor(v_cache, vl.scale, vl.zero_point, *g[2:6])
+    kl, vl = lsq_kv_append_paged_w8(lsq_rope_w8_q(k, cos, sin, *r[:6], mid_dtype, positions), v, k_cache, v_cache, block_table, positions)
+    return rq, kl, vl

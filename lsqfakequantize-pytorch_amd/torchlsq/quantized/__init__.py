@@ -27,6 +27,7 @@ from .modules.attn_w8 import AttentionCoreW8Q, MatmulW8Q, SoftmaxW8Q  # noqa: F4
 from .modules.rope_w8 import KVCacheW8, RotaryW8Q  # noqa: F401
 from .modules.paged_kv_w8 import PagedKVCacheW8  # noqa: F401
 from .modules.qkv_rope_w8 import QKVRotaryW8Q  # noqa: F401
+from .modules.qkv_rope_packed_a8 import QKVRotaryPackedA8Q  # noqa: F401
 
 
 def _switch(name, method, only_dtype=None):
