@@ -4,7 +4,7 @@
 // Nothing is defined here.  v, the fp32 value before the output side, is csrc/qlinear_a8/lsq_qlinear_a8.hip's matrix-core kernel's:
 // the same exact integer I per group, one conversion, acc + qscale * f, the same assignment of spans to waves, the same order of
 // the sum over the waves, * s_x, + bias.  The byte is csrc/requant_w8/'s w8q_byte or csrc/resadd_w8/'s w8r_byte from their v on
-// (lsq_lindec_w4_shared.hpp's w4q_byte and w4r_byte below: those functions' steps after v, as functions of v; the constants are those
+// (lsq_lindec_w4_shared.hpp's w4q_byte and w4r_byte: those functions' steps after v, as functions of v; the constants are those
 // headers').  What csrc/linglu_w4/ needs too -- the cut of K, the staging of x, the cursor and step structs -- lies in that header.
 //
 // ONE KERNEL TEXT, lindec_w4_kernel<BITS, PAIR, RES>, 1024 threads = 16 waves, a persistent grid of min(ceil(N / 16), CUs)
@@ -45,19 +45,6 @@ namespace lsq {
 
 // LDS: the partial sums, the byte tile (residual in, y out), the rows of x, the table of sum a - G z
 constexpr int kW4MaxLds = kQRedBytes + kW4TileBytes + LSQ_LINDEC_W4_MAX_ROWS * (kQChunk + kQRowPad) + LSQ_LINDEC_W4_MAX_ROWS * (kQChunk / 32) * 4;
-
-// w8r_byte's steps after v (csrc/resadd_w8/lsq_resadd_w8_tiles.hpp): u, the optional p, d, t, the select, the level.  Every step is
-// rounded once: the product d and the sum p + d are NOT one fused multiply-add.
-__device__ __forceinline__ uint8_t w4r_byte(float v, const W8OutQ& oq, const W8PreQ& pq, const W8ResQ& rq, uint8_t lr) {
-    const float u = w8r_round(v, oq.mid);
-    float p = u;
-    if (pq.on) p = w8r_round(dequant<float>(level<float>(u, pq.qp, pq.r), pq.qp), oq.mid);
-    const float lf = rq.is_signed ? static_cast<float>(static_cast<int8_t>(lr)) : static_cast<float>(lr);
-    const float d = w8r_round(__fmul_rn(__fsub_rn(lf, rq.z), rq.s), oq.mid);
-    float t = w8r_round(__fadd_rn(p, d), oq.mid);
-    if (oq.relu) t = (t < 0.0f) ? 0.0f : t;
-    return static_cast<uint8_t>(static_cast<int>(level<float>(t, oq.qp, oq.r)) & 0xff);
-}
 
 template <int BITS, bool PAIR, bool RES>
 __global__ __launch_bounds__(kQBlock) void lindec_w4_kernel(W8Act act, int M, W4Weight wt, W4Geom geo, W8OutArg out, W8ResArg res,
@@ -340,35 +327,6 @@ static hipError_t w4_launch_format(const W4Plan& pl, int bits, const W4Call& c, 
 // the C ABI of include/lsq_hip_lindec_w4.h: validation, error bookkeeping
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-// the residual's and the pre-quantizer's checks, said as csrc/resadd_w8/lsq_resadd_w8.hip and csrc/lindec_w8/lsq_lindec_w8.hip say
-// them (translation units, not headers: a fix there belongs here too); `MN`: the bytes of y and of the residual
-int check_res(const char* what, const lsq_resadd_w8_res* r, const void* y, int64_t MN, lsq::W8ResArg& arg) {
-    if (r->level_dtype != LSQ_REQUANT_W8_U8 && r->level_dtype != LSQ_REQUANT_W8_I8)
-        return fail(LSQ_EINVAL, "%s: the residual's level_dtype must be LSQ_REQUANT_W8_U8 (0) or LSQ_REQUANT_W8_I8 (1), got %lld", what,
-                    static_cast<ll>(r->level_dtype));
-    if (!r->levels || !r->scale || !r->zero_point) return fail(LSQ_EINVAL, "%s: NULL residual levels, scale or zero_point", what);
-    if (!aligned_to(r->scale, 4) || !aligned_to(r->zero_point, 4))
-        return fail(LSQ_EINVAL, "%s: the residual's scale and zero_point must be element-aligned", what);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(r->levels), b = reinterpret_cast<uintptr_t>(y), n = static_cast<uintptr_t>(MN);
-    if (a < b + n && b < a + n)
-        return fail(LSQ_EINVAL, "%s: the residual's %lld bytes overlap y's: an in-place add is not served", what, static_cast<ll>(MN));
-    arg = lsq::W8ResArg{static_cast<const uint8_t*>(r->levels), static_cast<const float*>(r->scale),
-                        static_cast<const int32_t*>(r->zero_point), r->level_dtype == LSQ_REQUANT_W8_I8 ? 1 : 0, 0};
-    return LSQ_OK;
-}
-
-int check_pre(const char* what, const lsq_resadd_w8_pre* p, lsq::W8PreArg& arg) {
-    arg = lsq::W8PreArg{nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (!p) return LSQ_OK;
-    if (!p->scale || !p->shift) return fail(LSQ_EINVAL, "%s: NULL scale or shift of the pre-quantizer", what);
-    if (!aligned_to(p->scale, 4) || !aligned_to(p->shift, 4))
-        return fail(LSQ_EINVAL, "%s: the pre-quantizer's scale and shift must be element-aligned", what);
-    if (int rc = check_byte_range(what, "the pre-quantizer's ", p->quant_min, p->quant_max, p->type_min, p->type_max)) return rc;
-    arg = lsq::W8PreArg{static_cast<const float*>(p->scale), static_cast<const float*>(p->shift), static_cast<float>(p->quant_min),
-                        static_cast<float>(p->quant_max), static_cast<float>(p->type_min), static_cast<float>(p->type_max)};
-    return LSQ_OK;
-}
 
 // what this form serves; everything else that is legal belongs to lsq_hip_qlinear_a8.h and the ops after it
 int check_served(const char* what, const lsq::W4Plan& pl, int64_t M, int64_t K, int64_t G, int bits, bool aligned) {

@@ -1,11 +1,13 @@
 // lsq_lindec_w4_shared.hpp -- what the decode-shape kernels on packed 4- / 2-bit codes with an 8-bit output say the same way:
-// csrc/lindec_w4/lsq_lindec_w4.hip (one weight strip, levels out) and csrc/linglu_w4/lsq_linglu_w4.hip (a gate and an up strip, the
-// gated product's levels out).  The cut of K (which fixes the order of the fp32 sum: include/lsq_hip_lindec_w4.h), the kernel
+// csrc/lindec_w4/lsq_lindec_w4.hip (one weight strip, levels out), csrc/linmid_w4/lsq_linmid_w4.hip (the same for 17 to 64 rows) and
+// csrc/linglu_w4/lsq_linglu_w4.hip (a gate and an up strip, the gated product's levels out).  The cut of K (which fixes the order
+// of the fp32 sum: include/lsq_hip_lindec_w4.h), the kernel
 // arguments, the permuted LDS layout of x with the staging of a chunk, the walk of a wave over its load steps, the hand-over of a
 // group's constants and the byte after v.  The two libraries stay separate; each compiles these pieces into its own kernels.
 #pragma once
 #include "../resadd_w8/lsq_resadd_w8_tiles.hpp"
 #include "../requant_w8/lsq_requant_w8_checks.hpp"
+#include "../../../include/lsq_hip_resadd_w8.h"
 
 namespace lsq {
 
@@ -61,6 +63,19 @@ __device__ __forceinline__ uint8_t w4q_byte(float v, const W8OutQ& oq) {
     float u = w8r_round(v, oq.mid);
     if (oq.relu) u = (u < 0.0f) ? 0.0f : u;         // a select: a NaN stays a NaN and goes to quant_min below
     return static_cast<uint8_t>(static_cast<int>(level<float>(u, oq.qp, oq.r)) & 0xff);
+}
+
+// w8r_byte's steps after v (csrc/resadd_w8/lsq_resadd_w8_tiles.hpp): u, the optional p, d, t, the select, the level.  Every step is
+// rounded once: the product d and the sum p + d are NOT one fused multiply-add.
+__device__ __forceinline__ uint8_t w4r_byte(float v, const W8OutQ& oq, const W8PreQ& pq, const W8ResQ& rq, uint8_t lr) {
+    const float u = w8r_round(v, oq.mid);
+    float p = u;
+    if (pq.on) p = w8r_round(dequant<float>(level<float>(u, pq.qp, pq.r), pq.qp), oq.mid);
+    const float lf = rq.is_signed ? static_cast<float>(static_cast<int8_t>(lr)) : static_cast<float>(lr);
+    const float d = w8r_round(__fmul_rn(__fsub_rn(lf, rq.z), rq.s), oq.mid);
+    float t = w8r_round(__fadd_rn(p, d), oq.mid);
+    if (oq.relu) t = (t < 0.0f) ? 0.0f : t;
+    return static_cast<uint8_t>(static_cast<int>(level<float>(t, oq.qp, oq.r)) & 0xff);
 }
 
 struct W4Cursor {           // a wave's walk over its load steps of one chunk; everything in it is the same for the whole wave
@@ -158,6 +173,36 @@ int check_format(const char* what, int64_t M, int64_t N, int64_t K, int64_t G, i
     if (G % (8 / bits) != 0)
         return fail(LSQ_EINVAL, "%s: group_size %lld is not a multiple of %d, the elements of one byte of %d-bit codes", what,
                     static_cast<ll>(G), 8 / bits, bits);
+    return LSQ_OK;
+}
+
+
+// the residual's and the pre-quantizer's checks, said as csrc/resadd_w8/lsq_resadd_w8.hip and csrc/lindec_w8/lsq_lindec_w8.hip say
+// them (translation units, not headers: a fix there belongs here too); `MN`: the bytes of y and of the residual
+inline int check_res(const char* what, const lsq_resadd_w8_res* r, const void* y, int64_t MN, lsq::W8ResArg& arg) {
+    if (r->level_dtype != LSQ_REQUANT_W8_U8 && r->level_dtype != LSQ_REQUANT_W8_I8)
+        return fail(LSQ_EINVAL, "%s: the residual's level_dtype must be LSQ_REQUANT_W8_U8 (0) or LSQ_REQUANT_W8_I8 (1), got %lld", what,
+                    static_cast<ll>(r->level_dtype));
+    if (!r->levels || !r->scale || !r->zero_point) return fail(LSQ_EINVAL, "%s: NULL residual levels, scale or zero_point", what);
+    if (!aligned_to(r->scale, 4) || !aligned_to(r->zero_point, 4))
+        return fail(LSQ_EINVAL, "%s: the residual's scale and zero_point must be element-aligned", what);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(r->levels), b = reinterpret_cast<uintptr_t>(y), n = static_cast<uintptr_t>(MN);
+    if (a < b + n && b < a + n)
+        return fail(LSQ_EINVAL, "%s: the residual's %lld bytes overlap y's: an in-place add is not served", what, static_cast<ll>(MN));
+    arg = lsq::W8ResArg{static_cast<const uint8_t*>(r->levels), static_cast<const float*>(r->scale),
+                        static_cast<const int32_t*>(r->zero_point), r->level_dtype == LSQ_REQUANT_W8_I8 ? 1 : 0, 0};
+    return LSQ_OK;
+}
+
+inline int check_pre(const char* what, const lsq_resadd_w8_pre* p, lsq::W8PreArg& arg) {
+    arg = lsq::W8PreArg{nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (!p) return LSQ_OK;
+    if (!p->scale || !p->shift) return fail(LSQ_EINVAL, "%s: NULL scale or shift of the pre-quantizer", what);
+    if (!aligned_to(p->scale, 4) || !aligned_to(p->shift, 4))
+        return fail(LSQ_EINVAL, "%s: the pre-quantizer's scale and shift must be element-aligned", what);
+    if (int rc = check_byte_range(what, "the pre-quantizer's ", p->quant_min, p->quant_max, p->type_min, p->type_max)) return rc;
+    arg = lsq::W8PreArg{static_cast<const float*>(p->scale), static_cast<const float*>(p->shift), static_cast<float>(p->quant_min),
+                        static_cast<float>(p->quant_max), static_cast<float>(p->type_min), static_cast<float>(p->type_max)};
     return LSQ_OK;
 }
 

@@ -901,6 +901,27 @@ def lindec_w4_library():
                               lindec_w4_error_str)
 
 
+# lindec_w4's linear for 17 to 64 rows: 2 to 4 sub-tiles of 16 rows against ONE stream of the weight, x staged in windows, one launch
+# (include/lsq_hip_linmid_w4.h): a thirty-second companion library; the ABIs above stay as they are.  Its arguments are lindec_w4's.
+LINMID_W4_ABI_VERSION = 1
+LINMID_W4_MIN_ROWS = 17         # LSQ_LINMID_W4_MIN_ROWS / _MAX_ROWS: rows of x one launch serves
+LINMID_W4_MAX_ROWS = 64
+C_ABI_LINMID_W4 = {
+    "lsq_linmid_w4_abi_version": (_int, []),
+    "lsq_linmid_w4_last_error": (ctypes.c_char_p, []),
+    "lsq_linmid_w4_linear_levels": C_ABI_LINDEC_W4["lsq_lindec_w4_linear_levels"],
+    "lsq_linmid_w4_plan": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _PLAN8]),
+}
+_LINMID_W4_LIB, linmid_w4_error_str = _load_companion("liblsq_hip_linmid_w4.so", C_ABI_LINMID_W4, "lsq_linmid_w4_abi_version",
+                                                      LINMID_W4_ABI_VERSION)
+
+
+def linmid_w4_library():
+    """The ctypes handle of liblsq_hip_linmid_w4.so (raises if it is missing)."""
+    return _require_companion(_LINMID_W4_LIB, "linmid_w4", "the W4A8 / W2A8 linears with an 8-bit output for 17 to 64 rows need",
+                              linmid_w4_error_str)
+
+
 # The gate and up linears of a gated MLP's decode step (M <= 16) with the gated product in their epilogue: one launch, the levels of
 # act(gate) * up out (include/lsq_hip_linglu_w8.h): a twenty-seventh companion library; the ABIs above stay as they are.  Its
 # projections carry lsq_requant_w8's output quantizer, its product lsq_glu_w8's constants.

@@ -16,7 +16,7 @@ import torch
 from ._abi import _DTYPE_CODE, LINGLU_W4_MAX_ROWS, LsqGluW8Consts, LsqLingluW4Proj, _assert_has_ops, linglu_w4_library
 from ._glu_w8_host import glu_w8_q
 from ._hip_host import _check, _on_device, _stream_of
-from ._lindec_w4_host import lindec_w4_linear_levels
+from ._lindec_w4_host import fallback_decode, lindec_w4_linear_levels
 from ._linglu_w8_host import _halves_of_one
 from ._qlinear_a8_host import _LEVEL_CODE, _check_a8_args
 from ._requant_w8_host import _STORES, _check_out, _out_struct
@@ -35,13 +35,14 @@ def _composed(x_levels, s_x, zx, g, u, fmt, g_rng, u_rng, up_scale, up_zero, tab
     product (`out`, GPU only: where it is written)"""
     same_q = g_rng == u_rng and g[4].data_ptr() == u[4].data_ptr() and g[5].data_ptr() == u[5].data_ptr()
     fused = _halves_of_one(g, u) if same_q else None
+    dec = fallback_decode(x_levels)
     if fused is not None:
         C = g[0].shape[0]
-        gu = lindec_w4_linear_levels(x_levels, s_x, zx, *fused, *fmt, g[4], g[5], *g_rng, False, mid_dtype)
+        gu = lindec_w4_linear_levels(x_levels, s_x, zx, *fused, *fmt, g[4], g[5], *g_rng, False, mid_dtype, dec, measured=True)
         gl, ul = gu[..., :C], gu[..., C:]
     else:
-        gl = lindec_w4_linear_levels(x_levels, s_x, zx, *g[:4], *fmt, g[4], g[5], *g_rng, False, mid_dtype)
-        ul = lindec_w4_linear_levels(x_levels, s_x, zx, *u[:4], *fmt, u[4], u[5], *u_rng, False, mid_dtype)
+        gl = lindec_w4_linear_levels(x_levels, s_x, zx, *g[:4], *fmt, g[4], g[5], *g_rng, False, mid_dtype, dec, measured=True)
+        ul = lindec_w4_linear_levels(x_levels, s_x, zx, *u[:4], *fmt, u[4], u[5], *u_rng, False, mid_dtype, dec, measured=True)
     return glu_w8_q(gl, ul, up_scale, up_zero, table, *out_q, mid_dtype, out=out)
 
 

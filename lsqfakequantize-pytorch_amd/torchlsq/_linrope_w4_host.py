@@ -20,7 +20,7 @@ from ._abi import (_DTYPE_CODE, LINROPE_W4_MAX_ROWS, LsqAttnPagedW8Pages, LsqLin
                    _assert_has_ops, linrope_w4_library)
 from ._attn_paged_w8_host import kv_append_paged_w8
 from ._hip_host import _check, _on_device, _stream_of
-from ._lindec_w4_host import lindec_w4_linear_levels
+from ._lindec_w4_host import fallback_decode, lindec_w4_linear_levels
 from ._linrope_w8_host import _strides
 from ._qlinear_a8_host import _LEVEL_CODE, _check_a8_args
 from ._requant_w8_host import _check_out, _out_struct
@@ -47,7 +47,7 @@ def _plan(geom, K, group_size, bits, aligned):
 def _composed(x_levels, s_x, zx, w, fmt, qkv_q, s_q, z_q, cos, sin, rot_q, mid_dtype, H, Hkv, D, k_cache, v_cache, positions, block_table, out):
     """the ops the new one composes, on either device"""
     B, T = int(x_levels.shape[0]), int(x_levels.shape[1])
-    qkv = lindec_w4_linear_levels(x_levels, s_x, zx, *w, *fmt, *qkv_q, False, mid_dtype).view(B, T, H + 2 * Hkv, D)
+    qkv = lindec_w4_linear_levels(x_levels, s_x, zx, *w, *fmt, *qkv_q, False, mid_dtype, fallback_decode(x_levels), measured=True).view(B, T, H + 2 * Hkv, D)
     q, k, v = qkv[:, :, :H], qkv[:, :, H:H + Hkv], qkv[:, :, H + Hkv:]
     rq = rope_w8_q(q, s_q, z_q, cos, sin, *rot_q, mid_dtype, positions, False, out=out)
     if block_table is None:

@@ -4,6 +4,8 @@ Drop-in for reference torchlsq/functional.py:8-97: same name, same argument list
 assertions; the work is done by `torch.ops.torchlsq.lsq` (registered in torchlsq/extension.py on top
 of the gfx950 kernels).
 """
+import contextlib
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -987,6 +989,24 @@ def lsq_linear_w8a8_add_q(x, weight_q: Tensor, bias: Tensor, residual: LevelsTen
 # is None.  The bits are the same either way; it ships True only when every case of tools/exp_lindec_w4_ab.py is faster than the
 # composition beyond the spread (profiles/r38_lindec_w4_ab.txt: all 36 cases, new / composition 0.53 to 0.72).
 W4A8_DECODE_DEFAULT = True
+# The same for calls with MORE than 16 rows, up to `extension.qgemm_a8_min_rows()`: whether `decode=None` (and the GLU and rotary ops'
+# fallbacks) leaves the composition for the measured route -- per block of 64 rows ONE launch of liblsq_hip_linmid_w4.so where that was
+# measured faster (`_lindec_w4_host._linmid_wins`), else liblsq_hip_lindec_w4.so per 16 rows, all into row slices of one output.  The
+# bits are the same either way; it ships True only when every case of tools/exp_linmid_w4_ab.py is faster than the composition beyond
+# the spread (profiles/r41_linmid_w4_ab.txt: all 90 cases, auto / composition 0.46 to 0.91).  `decode=True` is not
+# this route: it takes liblsq_hip_linmid_w4.so wherever it is served, which alone MISSES 10 of the 90.
+W4A8_MID_DEFAULT = True
+
+
+def _w4a8_decode(decode, levels):
+    """(the op's `decode`, the context its call runs in): an explicit `decode` is passed on as it is; None follows the defaults by the
+    number of rows, and beyond 16 rows takes the measured route per block of rows (`_lindec_w4_host.measured_routes`)"""
+    if decode is not None:
+        return bool(decode), contextlib.nullcontext()
+    if levels.numel() // max(1, levels.size(-1)) <= 16:
+        return W4A8_DECODE_DEFAULT, contextlib.nullcontext()
+    from ._lindec_w4_host import measured_routes
+    return W4A8_MID_DEFAULT, measured_routes()
 
 
 def _packed_operands(packed, bias):
@@ -1010,14 +1030,18 @@ def lsq_linear_packed_a8_q(x, packed: PackedGroupTensor, bias: Tensor = None, ou
     per-tensor output quantizer -- bit for bit the composition `lsq_linear_packed_a8(..., out_dtype=mid_dtype)`, the select,
     `lsq_levels_per_tensor` on the same device.  x is a `LevelsTensor` or a per-tensor `torch.quint8` / `torch.qint8` tensor; a
     `LevelsTensor` is returned and nothing is read back.  `decode`: True takes ONE launch of liblsq_hip_lindec_w4.so when x has at
-    most 16 rows and the format is one of the matrix-core form (every other call composes), False always composes, None follows
-    `W4A8_DECODE_DEFAULT`; the bits are the same either way.  Inference only."""
+    most 16 rows and the format is one of the matrix-core form, ONE launch of liblsq_hip_linmid_w4.so with 17 to 64 rows (the weight is
+    streamed once) and one launch per block of 64 rows below `extension.qgemm_a8_min_rows()` rows (every other call composes); False
+    always composes; None follows `W4A8_DECODE_DEFAULT` up to 16 rows and `W4A8_MID_DEFAULT` beyond, where it takes per block of rows
+    the faster of that library and liblsq_hip_lindec_w4.so called per 16 rows, as measured; the bits are the same on every route.
+    Inference only."""
     _assert_has_ops()
     what = "lsq_linear_packed_a8_q"
     o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
     x = _packed_levels_in(what, x)
-    dec = W4A8_DECODE_DEFAULT if decode is None else bool(decode)
-    lv = torch.ops.torchlsq.lsq_linear_packed_q8_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *o, mid_dtype, dec)
+    dec, route = _w4a8_decode(decode, x.levels)
+    with route:
+        lv = torch.ops.torchlsq.lsq_linear_packed_q8_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *o, mid_dtype, dec)
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 
@@ -1027,15 +1051,17 @@ def lsq_linear_packed_a8_add_q(x, packed: PackedGroupTensor, bias: Tensor, resid
                                pre_shift: Tensor = None, pre_quant_min: int = None, pre_quant_max: int = None, pre_type_min: int = None,
                                pre_type_max: int = None, decode: bool = None) -> LevelsTensor:
     """`lsq_linear_packed_a8_q` with `residual`, a `LevelsTensor` of the output's shape, added before the ReLU, after the layer's own
-    optional pre-quantizer: `lsq_linear_w8a8_add_q`'s steps on the packed weight's value.  `decode`: as above.  Inference only."""
+    optional pre-quantizer: `lsq_linear_w8a8_add_q`'s steps on the packed weight's value.  `decode`: as above, 17 to 64 rows and
+    the blocks of 64 rows included.  Inference only."""
     _assert_has_ops()
     what = "lsq_linear_packed_a8_add_q"
     o = _out_args(what, out_scale, out_shift, out_quant_min, out_quant_max, out_type_min, out_type_max, relu)
     r = _res_args(what, residual, pre_scale, pre_shift, pre_quant_min, pre_quant_max, pre_type_min, pre_type_max)
     x = _packed_levels_in(what, x)
-    dec = W4A8_DECODE_DEFAULT if decode is None else bool(decode)
-    lv = torch.ops.torchlsq.lsq_linear_packed_q8_add_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *o, mid_dtype, *r,
-                                                       dec)
+    dec, route = _w4a8_decode(decode, x.levels)
+    with route:
+        lv = torch.ops.torchlsq.lsq_linear_packed_q8_add_q(x.levels, x.scale, x.zero_point, *_packed_operands(packed, bias), *o, mid_dtype,
+                                                           *r, dec)
     return _levels_out(lv, o[0], o[1], o[2:6])
 
 

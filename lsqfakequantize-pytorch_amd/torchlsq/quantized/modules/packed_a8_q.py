@@ -19,8 +19,9 @@ from .w8a8_q import _OutputQuantizer, _as_levels
 
 class PackedLinearA8Q(PackedLinearA8, _OutputQuantizer):
     """`PackedLinearA8` with an 8-bit output.  Extra state: `PackedLinearA8`'s, the output range, `relu`, `mid_dtype`, and `decode`
-    when it is not None (True: liblsq_hip_lindec_w4.so for at most 16 rows; False: never; None: `W4A8_DECODE_DEFAULT`).
-    Inference only."""
+    when it is not None (True: liblsq_hip_lindec_w4.so for at most 16 rows, liblsq_hip_linmid_w4.so for 17 to 64 and blocks of 64 rows
+    below `qgemm_a8_min_rows()`; False: never; None: `W4A8_DECODE_DEFAULT` up to 16 rows, `W4A8_MID_DEFAULT` beyond: the faster of the two
+    libraries per block of rows).  Inference only."""
 
     def __init__(self, in_features, out_features, bits=4, group_size=32, quant_min=-8, bias=True, device=None,
                  input_range=(0, 255, 0, 255), output_range=(0, 255, 0, 255), relu=False, mid_dtype=torch.float32):
